@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the fused 2048 Q-learning step on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (choose -> env.step -> TD update -> reset-on-done,
 Agent/main.py:91-101) over the whole batch: 1,048,576 boards per GPU (BASELINE configs[2] at
 N = 1; configs[3] = 8 x 1,048,576 at N = 8, weak scaling).
+
+Every env learns on private rows of the one device hash table (`independent`: keys salted with the env's
+global id), i.e. the batch is B reference agents side by side: what a run computes depends only on its
+arguments, never on how the lanes were scheduled, so two runs -- and two builds -- can be compared output
+for output.  `--shared-table` runs the lock-free mode instead (one Q row per state for all envs, written
+without locks: scheduling-dependent, checked by invariants); with --full it is also a companion.
 
 With N > 1 and no process group in the environment the script starts its own N ranks (one fresh
 child process per GPU, before anything in the parent touches the GPU) and relays rank 0's line;
@@ -16,18 +22,28 @@ Protocol, per rank:
      (Q2048_FLAG_PLAY_ONLY, eps = 1), so that boards and episode phases are the stationary
      mid-game mix and not 1 M boards five moves from reset;
   2. W warm-up steps of the real loop (table warm, RCCL initialised), untimed;
-  3. the K-step region, timed `--repeats` times back to back on the same run (each region =
-     ceil(K / steps_per_launch) launches + the statistics of the region on the host, bracketed by
-     barrier + synchronize -- with several ranks the closing barrier is the statistics reduction, one
-     collective over all ranks that nobody passes before every rank's steps are in; with one process
-     the statistics are read from the rollout's host-side mirror after the closing synchronize; MAX
-     over ranks): the MEDIAN region is the one reported.  Every region must
-     finish episodes (`stats.episodes > 0`), or the reset / terminal-row path was not measured.
+  3. the K-step region, timed (ceil(K / steps_per_launch) launches + the statistics of the region on
+     the host, bracketed by barrier + synchronize -- with several ranks the closing barrier is the
+     statistics reduction, one collective over all ranks that nobody passes before every rank's steps
+     are in; with one process the statistics are read from the rollout's host-side mirror after the
+     closing synchronize; MAX over ranks).  `--steps K` is the number of timed steps: one region by
+     default; `--repeats R` times R regions back to back on the same run and reports the MEDIAN one.
+     Every region must finish episodes (`stats.episodes > 0`), or the reset / terminal-row path was
+     not measured.
 Boards, aux records and the hash Q-table are resident in HBM throughout.  Rank 0 prints ONE
 JSON line.  The launches go through q2048_fused_rollout_opts: every env's row passes from launch to
 launch through the row cache (`--no-row-cache`: each launch starts from a probe instead), and with one
 process the region's statistics are read from the host-side mirror the launch's last block writes
 (`--stats-by-copy`: a device-to-host copy queued behind the launches, as with several ranks).
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its last step as
+DIR/<name>.npy (float32 / float64): the boards, the aux fields and the Q-values of the current boards
+for a fixed, seeded sample of envs, and the statistics vectors of the last region.  With the same
+arguments the inputs and these outputs are the same from run to run (the float64 statistics sums up to
+the order of their atomic additions); with --shared-table only the inputs are.
+
+A plain run measures only the headline.  `--full` adds what takes runs of its own: the CPU baselines
+(`cpu_baseline`) and the companion runs (`companions`), both below.
 
 Extra objects on the line:
   roofline      HBM roofline of the dominant kernel (k_fused_rollout): algorithmic bytes per
@@ -36,12 +52,12 @@ Extra objects on the line:
                 (and `fabric_frac` = traffic / launch time / peak: how busy the memory system is, next to
                 `frac`, how well it is used, and `physical_minimum`, the run's own useful bytes) only when
                 the committed PMC passes were taken with this run's configuration on these kernel sources.
-  cpu_baseline  the CPU oracle (a C port of the reference loop, oracle/; kind "port") timed on this host's
+  cpu_baseline  (--full) the CPU oracle (a C port of the reference loop, oracle/; kind "port") timed on this host's
                 cores on a bounded sample of the same workload (rank 0, after the GPU regions, at
                 every N): all cores and one thread, with the CPU model; and, under `product_core`, the
                 product's own CPU twin (libq2048_host.so, device "cpu"; kind "product-core") on the same
                 cores: the kernels' per-lane arithmetic and table, one shared table as on the GPU.
-  companions    the same protocol at SURVEY 8(d)'s 2^28-slot table, at eps = 0.01, on 5x5 boards and on a FROZEN
+  companions    (--full) the same protocol at SURVEY 8(d)'s 2^28-slot table, at eps = 0.01, on 5x5 boards and on a FROZEN
                 table -- pre-filled (untimed) to freeze_load 0.5, key set closed (Q2048_FLAG_NO_NEW_ROWS): where a
                 run lives once its table has reached the largest capacity the device holds, i.e. after the first
                 ~4e9 env-steps per GPU; the main line's table is young (N = 1 only).
@@ -79,6 +95,7 @@ FREEZE_LOAD = 0.5           # the frozen companion: BatchedQLearningAgent's defa
 PMC_TRAFFIC_FILES = [os.path.join(REPO, "profiles", f) for f in ("r06_pmc_traffic.json", "r06_pmc_traffic_k20.json",
                                                                  "r06_pmc_traffic_frozen_k20.json")]
 CSRC = os.path.join(REPO, "2048_q-learning_amd", "csrc")
+DUMP_SAMPLE, DUMP_SEED = 1 << 16, 0x2048    # --dump-outputs: envs sampled (fixed seed), about 9 MB of arrays
 KERNEL_SOURCES = ("q2048_kernels.hip", "q2048_core.hpp", "q2048_core5.hpp", "q2048_luts.inc")
 
 
@@ -96,7 +113,8 @@ def parse_args(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=256)
     p.add_argument("--warmup", type=int, default=64)
-    p.add_argument("--repeats", type=int, default=5, help="timed K-step regions; the median is reported")
+    p.add_argument("--repeats", type=int, default=1,
+                   help="timed K-step regions (repeats x K timed steps); the median is reported")
     p.add_argument("--prep-steps", type=int, default=1024,
                    help="input synthesis: untimed steps of random play without a learner (>= 64)")
     p.add_argument("--boards-per-gpu", type=int, default=1 << 20)
@@ -110,7 +128,8 @@ def parse_args(argv=None):
     p.add_argument("--alpha", type=float, default=0.1)
     p.add_argument("--gamma", type=float, default=0.99)
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--cap-log2", type=int, default=0, help="0 = load <= 0.5 and up to half the free device memory")
+    p.add_argument("--cap-log2", type=int, default=0,
+                   help="0 = load <= 0.5 and at least 2^30 slots, at most what the free device memory holds")
     p.add_argument("--prefill-load", type=float, default=0.0,
                    help="measurement runs: fill the table, untimed, with this share of rows that are no states before the "
                         "run (>= the agent's freeze_load 0.5: the key set closes at the first launch -- the frozen "
@@ -119,10 +138,17 @@ def parse_args(argv=None):
                    type=lambda v: v if v in ("auto", "plain", "chunks") else int(v),
                    help="table allocation (agent.place_table): auto | chunks (2 MiB physical chunks, "
                         "q2048_table_alloc) | plain (hipMalloc) | N (best of N probed candidates)")
+    p.add_argument("--shared-table", action="store_true",
+                   help="one Q row per state shared by all envs, written lock-free (scheduling-dependent results) "
+                        "instead of private rows per env")
     p.add_argument("--strict-td", action="store_true",
                    help="TD write by compare-and-swap loop (Q2048_FLAG_TD_CAS) instead of one store; bounded: "
                         "after 16 lost races an update is stored plainly and counted (stats.cas_fallbacks)")
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget; 0 = skip")
+    p.add_argument("--full", action="store_true",
+                   help="also the CPU baselines and the companion runs (not needed for the headline figure)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
+    p.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline budget; 0 = skip")
     p.add_argument("--experiment-bits", type=lambda v: int(v, 0), default=0,
                    help="unstable tuning bits OR-ed into the fused kernel's flags (ablations; not ABI)")
     p.add_argument("--no-row-cache", action="store_true",
@@ -132,7 +158,7 @@ def parse_args(argv=None):
                    help="A/B: a region's statistics come back by a device-to-host copy queued behind the "
                         "launches (StatsAllReduce) instead of the rollout's host-side mirror")
     p.add_argument("--no-companions", action="store_true",
-                   help="skip the 2^28-slot, eps = 0.01 and 5x5 companion runs (N = 1 only anyway)")
+                   help="--full: skip the 2^28-slot, eps = 0.01, 5x5 and frozen-table companion runs (N = 1 only anyway)")
     p.add_argument("--check-shards", action="store_true",
                    help="no timing: play --steps steps at eps = 1 and print per-chunk hashes of boards + aux "
                         "(compare N = 1 with N = 2 over the same global env ids)")
@@ -293,11 +319,46 @@ def cpu_baseline_product_core(pkg, torch, args, seconds: float) -> dict:
             "by_threads": {str(t): r[0] for t, r in sorted(runs.items())}}
 
 
+def timed_path_outputs(pkg, torch, agent, env, si, sf) -> dict:
+    """`--dump-outputs`: what a caller of the timed path holds after its last step, for a fixed, seeded sample of
+    at most DUMP_SAMPLE envs (sorted ids): the boards (log2 tiles), the aux fields, the Q-values of those boards
+    in the table the run trained (and whether a row exists), and the statistics vectors of the last region."""
+    import numpy as np
+
+    B = env.num_envs
+    idx = np.arange(B) if B <= DUMP_SAMPLE else np.sort(np.random.default_rng(DUMP_SEED).choice(B, DUMP_SAMPLE, replace=False))
+    pick = torch.from_numpy(idx).to(env.boards.device)
+    boards = env.boards[pick].contiguous()
+    out = {"env_ids": (idx + env.env_id0).astype(np.float64), "boards": boards.cpu().numpy().astype(np.float32)}
+    aux = env.aux_fields()
+    for name in pkg.AUX_DTYPE.names:
+        out[f"aux_{name}"] = aux[name][idx].astype(np.float64)
+    if isinstance(agent, pkg.BatchedRowTupleAgent):
+        out["q_values"] = agent.q_values(boards).cpu().numpy().astype(np.float32)
+    else:
+        q, found = agent.q_values(env.boards, return_found=True)      # board i in env i's rows (private or shared)
+        q, found = q[pick], found[pick]
+        out["q_values"], out["q_found"] = q.cpu().numpy().astype(np.float32), found.cpu().numpy().astype(np.float32)
+    out["stats_i"], out["stats_f"] = np.asarray(si).astype(np.float64), np.asarray(sf).astype(np.float64)
+    return out
+
+
+def write_outputs(path: str, outputs: dict) -> None:
+    """DIR/<name>.npy for every array of `timed_path_outputs` (float32 / float64 already)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, f"{name}.npy"), arr, allow_pickle=False)
+
+
 def measure(pkg, torch, args, dev, shard, world, *, eps, cap_log2, placement, steps, warmup, repeats,
-            S, reducer, board_size=None, prefill_load=0.0, expect_frozen=False):
+            S, reducer, board_size=None, prefill_load=0.0, expect_frozen=False, outputs=False, shared=None):
     """The protocol of the module docstring for one configuration.  Returns a dict of raw
-    measurements (region times are MAX over ranks)."""
+    measurements (region times are MAX over ranks); with `outputs`, also what the timed path computed
+    (`timed_path_outputs`)."""
     board_size = args.board_size if board_size is None else board_size
+    shared = args.shared_table if shared is None else shared
     env = pkg.BatchedGame2048Env(shard.num_envs, board_size=board_size, seed=args.seed,
                                  env_id0=shard.env_id0, device=dev)
     if args.agent == "row-tuple":
@@ -312,7 +373,8 @@ def measure(pkg, torch, args, dev, shard, world, *, eps, cap_log2, placement, st
                                           exploration_rate=eps, capacity_log2=cap_log2,
                                           seed=args.seed, env_id0=shard.env_id0, device=dev,
                                           strict_td=args.strict_td, board_size=board_size,
-                                          placement=placement, row_cache=not args.no_row_cache)
+                                          placement=placement, row_cache=not args.no_row_cache,
+                                          independent=not shared)
         synth = agent
         agent.experiment_bits = args.experiment_bits
     prefilled_rows = prefill(torch, agent, prefill_load, args.seed) if prefill_load > 0 else 0
@@ -380,6 +442,7 @@ def measure(pkg, torch, args, dev, shard, world, *, eps, cap_log2, placement, st
         mi, mf = agent.mirrored_stats()
         assert (mi == agent.stats_i.cpu().numpy()).all() and (mf == agent.stats_f.cpu().numpy()).all(), \
             "statistics mirror != device vectors"
+    computed = timed_path_outputs(pkg, torch, agent, env, si, sf) if outputs else None
     worst = pkg.dist.max_over_ranks_many([r["wall_s"] for r in regions] + [r["kernel_ms"] for r in regions],
                                          device=dev)
     for k, r in enumerate(regions):
@@ -394,7 +457,7 @@ def measure(pkg, torch, args, dev, shard, world, *, eps, cap_log2, placement, st
     torch.cuda.empty_cache()
     return {"regions": regions, "table_rows": table_rows, "status": status, "mirrored": mirrored,
             "placement": placement_report, "prep_episodes_per_env": prep_episodes_per_env,
-            "prefilled_rows": prefilled_rows, "frozen": frozen}
+            "prefilled_rows": prefilled_rows, "frozen": frozen, "outputs": computed}
 
 
 def summarise(m, shard, steps, algo_bytes):
@@ -439,10 +502,20 @@ def run_rank(args):
     # every step may create a row: load <= 0.5 at the end of the run, and at least 2^30 slots (32 GiB,
     # mapped from 2 MiB chunks: as fast as a table spanning 128 GiB, DESIGN.md 4 "table placement")
     cap_log2 = args.cap_log2 or pkg.auto_capacity_log2(B * max(learn_steps, 1), dev, max_log2=32)
+    capped = False
+    if not args.cap_log2:
+        # (auto_capacity_log2 does not cap the size it asks for: beyond ~4000 steps of 1 Mi boards that is more than the
+        # device holds.  Such a run gets the largest table that fits beside 8 GiB for the rest, and the table closes
+        # its key set at the agent's freeze_load once it is full -- what a long run does on the largest table)
+        free, _ = torch.cuda.mem_get_info(dev)
+        while cap_log2 > 20 and (pkg._native.SIZEOF_SLOT << cap_log2) > free - (8 << 30):
+            cap_log2 -= 1
+            capped = True
+    new_rows = 0.75 if args.shared_table else 0.9      # rows created per board-step at the most (measured 0.74 / 0.85)
     if args.agent == "hash" and args.cap_log2:
-        # a table given by hand must still end the run below load ~0.6 (0.75 new rows per board-step
+        # a table given by hand must still end the run below load ~0.6 (`new_rows` per board-step
         # at the most), or every region is slower than the one before it: fewer regions, then
-        budget = int(0.6 * (1 << cap_log2) / (0.75 * B))
+        budget = int(0.6 * (1 << cap_log2) / (new_rows * B))
         while args.repeats > 1 and args.warmup + args.repeats * args.steps > budget:
             args.repeats -= 1
         if args.warmup + args.repeats * args.steps > budget:
@@ -456,7 +529,7 @@ def run_rank(args):
     m = measure(pkg, torch, args, dev, shard, world, eps=args.eps, cap_log2=cap_log2,
                 placement=args.placement, steps=args.steps, warmup=args.warmup,
                 repeats=args.repeats, S=S, reducer=reducer, prefill_load=args.prefill_load,
-                expect_frozen=args.prefill_load >= FREEZE_LOAD)
+                expect_frozen=args.prefill_load >= FREEZE_LOAD, outputs=rank == 0 and args.dump_outputs is not None)
     s = summarise(m, shard, args.steps, algo_bytes)
     st = s["median_region"]["stats"]
 
@@ -488,6 +561,8 @@ def run_rank(args):
                "board_size": args.board_size, "eps": args.eps, "strict_td": bool(args.strict_td)}
         if args.prefill_load:
             cfg["prefill_load"] = args.prefill_load
+        if not args.shared_table:
+            cfg["independent"] = True                   # (the committed counter passes are of the shared table)
         per_step, source, other = committed_pmc_traffic(cfg)
         if per_step is not None:
             roofline["traffic"] = per_step * shard.num_envs * (args.steps / s["launches"])
@@ -506,19 +581,24 @@ def run_rank(args):
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
         "data": "synthetic",
         "config": {"workload": f"{B} parallel {args.board_size}x{args.board_size} boards per GPU (uint8 "
-                               f"log2), {'device open-addressed hash Q-table' if args.agent == 'hash' else 'flat-array row-tuple Q (4 MiB)'}, fused step+select+TD kernel "
+                               f"log2), {('device open-addressed hash Q-table, ' + ('one row per state shared by all envs' if args.shared_table else 'private rows per env')) if args.agent == 'hash' else 'flat-array row-tuple Q (4 MiB)'}, fused step+select+TD kernel "
                                f"(BASELINE configs[{(2 if args.board_size == 4 else 4) if args.agent == 'hash' else 1}]"
                                f"{'' if world == 1 else '/[3] sharded, one Q replica per GPU'})",
                    "boards_per_gpu": B, "total_boards": shard.total_envs,
                    "steps_per_launch": S, "table_capacity_log2": cap_log2,
                    "table_bytes_per_gpu": (1 << cap_log2) * 32, "epsilon": args.eps,
+                   # the run needs more rows than the device holds: the table closes its key set at freeze_load
+                   # (`frozen`) and the later steps are those of a frozen table
+                   "table_capped_to_device_memory": capped,
                    "alpha": args.alpha, "gamma": args.gamma, "seed": args.seed,
                    "td_write": "compare-and-swap" if args.strict_td else "store (last writer wins)",
+                   "q_rows": None if args.agent != "hash" else (
+                       "one per state, shared by all envs (lock-free)" if args.shared_table else "private per env"),
                    "table_placement": m["placement"], "experiment_bits": args.experiment_bits,
                    "row_cache": not args.no_row_cache, "prefill_load": args.prefill_load, "frozen": m["frozen"],
                    "region_statistics": "host-side mirror written by the launch's last block" if m["mirrored"] else (
                        "all-gather (one collective)" if torch.distributed.is_initialized() else "copy to pinned host memory"),
-                   "prep_steps": args.prep_steps, "repeats": args.repeats,
+                   "prep_steps": args.prep_steps, "repeats": args.repeats, "full": args.full,
                    "timing": "median of `repeats` K-step regions after `prep_steps` of random play "
                              "and `warmup` learning steps",
                    "parallelism": f"env-batch x{world}, RCCL all-reduce of statistics only "
@@ -537,7 +617,10 @@ def run_rank(args):
         "kernel_ms_total": sum(r["kernel_ms"] for r in m["regions"]),
     }
 
-    if world == 1 and args.agent == "hash" and not args.no_companions:
+    if rank == 0 and args.dump_outputs is not None:
+        write_outputs(args.dump_outputs, m["outputs"])
+
+    if args.full and world == 1 and args.agent == "hash" and not args.no_companions:
         # the 2^28-slot table the survey specified, the exploit-heavy eps = 0.01 run,
         # and BASELINE configs[4] (5x5 boards, 156 algorithmic bytes per env-step); each sized so
         # that its table ends below load 0.5
@@ -546,20 +629,25 @@ def run_rank(args):
         # runs on one box, round 4: 63.0 / 65.4 / 65.2 us per step on 2^30 slots in chunks against 65.0 / 64.5 /
         # 64.9 on 2^32 -- profiles/r04_5x5_capacity_ab.txt -- so it runs on the main line's table size)
         cap5 = cap_log2
-        for name, c_eps, c_cap, c_n, c_fill in (
-                ("capacity 2^28 (SURVEY 8(d))", args.eps, 28, args.board_size, 0.0),
-                ("epsilon 0.01 (argmax path)", 0.01, cap_log2, args.board_size, 0.0),
-                ("5x5 boards (BASELINE configs[4])", args.eps, cap5, 5, 0.0),
+        sh = args.shared_table
+        for name, c_eps, c_cap, c_n, c_fill, c_shared in (
+                ("capacity 2^28 (SURVEY 8(d))", args.eps, 28, args.board_size, 0.0, sh),
+                ("epsilon 0.01 (argmax path)", 0.01, cap_log2, args.board_size, 0.0, sh),
+                ("5x5 boards (BASELINE configs[4])", args.eps, cap5, 5, 0.0, sh),
                 # the main line runs on a YOUNG table (load < 0.1 at the driver's K = 20): this is the same workload
                 # on the table of a LONG run -- one that has reached its largest capacity and closed its key set at
                 # freeze_load (pre-filled, untimed, to just above it: the agent's own policy freezes it at its first
                 # launch): existing rows learn, absent states read as zeros, their updates are dropped and counted
                 (f"frozen table: pre-filled to load {FREEZE_LOAD}, key set closed (Q2048_FLAG_NO_NEW_ROWS)", args.eps,
-                 cap_log2, args.board_size, FREEZE_LOAD + 0.002)):
-            if c_n == args.board_size and name.startswith("5x5"):
+                 cap_log2, args.board_size, FREEZE_LOAD + 0.002, sh),
+                # the main line's workload on ONE row per state for all envs, written lock-free (scheduling-dependent)
+                ("shared table: one row per state for all envs, lock-free writes", args.eps, cap_log2, args.board_size,
+                 0.0, True)):
+            if (c_n == args.board_size and name.startswith("5x5")) or (sh and name.startswith("shared")):
                 continue
+            c_rows = 0.75 if c_shared else 0.9
             # learning steps the table can take: up to load 0.5 (the frozen one takes no rows: no limit)
-            budget = int(0.5 * (1 << c_cap) / (0.75 * B)) if not c_fill else args.warmup + 4 * args.steps
+            budget = int(0.5 * (1 << c_cap) / (c_rows * B)) if not c_fill else args.warmup + 4 * args.steps
             c_rep = 3
             c_steps = max(1, min(args.steps, budget // (c_rep + 1)))
             c_warm = max(1, min(args.warmup, budget - c_rep * c_steps))
@@ -567,10 +655,12 @@ def run_rank(args):
             c_bytes = ALGO_BYTES_FUSED_4X4 if c_n == 4 else ALGO_BYTES_FUSED_5X5
             cm = measure(pkg, torch, args, dev, shard, world, eps=c_eps, cap_log2=c_cap,
                          placement=args.placement, steps=c_steps, warmup=c_warm, repeats=c_rep, S=c_S,
-                         reducer=reducer, board_size=c_n, prefill_load=c_fill, expect_frozen=bool(c_fill))
+                         reducer=reducer, board_size=c_n, prefill_load=c_fill, expect_frozen=bool(c_fill),
+                         shared=c_shared)
             cs = summarise(cm, shard, c_steps, c_bytes)
             cst = cs["median_region"]["stats"]
             comps.append({"name": name, "epsilon": c_eps, "table_capacity_log2": c_cap, "board_size": c_n,
+                          "shared_table": c_shared,
                           "steps": c_steps, "warmup": c_warm, "repeats": c_rep,
                           "steps_per_launch": c_S, "value": cs["value"],
                           "ms_per_step": cs["ms_per_step"], "region_ms": cs["region_ms"],
@@ -585,6 +675,8 @@ def run_rank(args):
                 # the frozen workload has counter passes of its own (bench.py --prefill-load, tools/sessions/r06_final_a.sh)
                 c_cfg = {"boards": shard.num_envs, "steps_per_launch": c_S, "cap_log2": c_cap, "board_size": c_n,
                          "eps": c_eps, "strict_td": bool(args.strict_td), "prefill_load": c_fill}
+                if not c_shared:
+                    c_cfg["independent"] = True         # (the committed counter passes are of the shared table)
                 c_per_step, c_source, _ = committed_pmc_traffic(c_cfg)
                 if c_per_step is not None:
                     comps[-1]["traffic_bytes_per_env_step"] = c_per_step
@@ -602,7 +694,7 @@ def run_rank(args):
             out["config"]["rank0_cpu_affinity"] = {"numa_node": pinned[0], "cpus": len(pinned[1])}
             os.sched_setaffinity(0, cpus_before)
         # the reference's CPU path next to the GPU number, on this node's cores, at every N
-        out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds) if args.cpu_seconds > 0 else None
+        out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds) if args.full and args.cpu_seconds > 0 else None
         if out["cpu_baseline"] is not None:
             # ... and what the same cores do with the product's own code (the CPU twin): both figures on the line
             out["cpu_baseline"]["product_core"] = cpu_baseline_product_core(pkg, torch, args, args.cpu_seconds)

@@ -12,7 +12,8 @@ tabular path is imported unmodified:
     four calls to return the decisions of the build's counter RNG (oracle.draws), i.e. the
     reference is driven by injected draws and its outputs are recorded.
 
-Usage:  python tests/golden/generate_golden.py        (writes *.npz next to this file)
+Usage:  python tests/golden/generate_golden.py        (writes the vectors next to this file;
+                                                       --only-g8 / --only-g9: G8 / G9 + G10 alone)
 """
 from __future__ import annotations
 
@@ -604,9 +605,150 @@ def gen_g8(dqn_mod, count=6000, transcript_steps=4000):
           "| transcript", transcript_steps, "steps,", episode, "episodes")
 
 
+def _g9_u32(rng, n):
+    """u32 draws, one in ten from the edges (0, 1, 2^31, 2^32 - 1)."""
+    v = rng.integers(0, 1 << 32, n, dtype=np.uint64)
+    edge = rng.random(n) < 0.1
+    v[edge] = rng.choice(np.array([0, 1, 1 << 31, (1 << 32) - 1], dtype=np.uint64), int(edge.sum()))
+    return v
+
+
+def _g9_boards(rng, n, hi=15, lo=0):
+    """[n, 16] log2 tiles in lo..hi; with lo = 0, no board is all zeros."""
+    b = rng.integers(lo, hi + 1, (n, 16)).astype(np.uint8)
+    for i in np.flatnonzero(~b.any(axis=1)):
+        b[i, rng.integers(0, 16)] = rng.integers(1, hi + 1)
+    return b
+
+
+def gen_g9(env_mod, agent_mod, dqn_mod, count=3000, loops=120):
+    """Random cases for the live property tests of test_reference_live.py (the same input ranges), each
+    recorded with the reference's answer, so that those tests need only the oracle and this file."""
+    rng = np.random.default_rng(0x2048_9)
+    feed = Feed()
+    out = {}
+
+    # move + spawn: any board, any action, any draw pair
+    boards, actions, dpos, dval = _g9_boards(rng, count), rng.integers(0, 4, count), _g9_u32(rng, count), _g9_u32(rng, count)
+    w_board, w_score, w_moved = [], [], []
+    with Injected(env_mod, feed):
+        for i in range(count):
+            feed.env_q = [0] * 4
+            g = env_mod.Game2048()
+            g.board = raw(boards[i]).astype(int)
+            feed.env_q = [int(dpos[i]), int(dval[i])]
+            moved, score = g.move(int(actions[i]))
+            w_board.append(lg(g.board)); w_score.append(int(score)); w_moved.append(bool(moved))
+    out.update(mv_board=boards, mv_action=actions.astype(np.uint8), mv_dpos=dpos, mv_dval=dval,
+               mv_want_board=np.array(w_board, dtype=np.uint8), mv_want_score=np.array(w_score, dtype=np.int64),
+               mv_want_moved=np.array(w_moved, dtype=np.uint8))
+
+    # game over on full boards (tiles 1..4: merges are likely)
+    full = _g9_boards(rng, count, hi=4, lo=1)
+    w_over = []
+    with Injected(env_mod, feed):
+        for i in range(count):
+            feed.env_q = [0] * 4
+            g = env_mod.Game2048()
+            g.board = raw(full[i]).astype(int)
+            w_over.append(bool(g.is_game_over()))
+    out.update(go_board=full, go_want=np.array(w_over, dtype=np.uint8))
+
+    # env step: reward, done and the shaping state, from arbitrary shaping states
+    boards, actions = _g9_boards(rng, count), rng.integers(0, 4, count)
+    dpos, dval = _g9_u32(rng, count), _g9_u32(rng, count)
+    prev, cons_action = rng.integers(1, 13, count), rng.integers(-1, 4, count)
+    cons_count, score0 = rng.integers(0, 131, count), rng.integers(0, 5001, count)
+    want = {k: [] for k in ("board", "reward", "done", "max", "score", "prev", "count", "penalty")}
+    with Injected(env_mod, feed):
+        for i in range(count):
+            pen = -1.0
+            for _ in range(max(0, int(cons_count[i]) - 10)):
+                pen = max(pen * 1.1, -10)
+            feed.env_q = [0] * 4
+            e = env_mod.Game2048_env()
+            e.game.board = raw(boards[i]).astype(int)
+            e.score, e.previous_max = int(score0[i]), 1 << int(prev[i])
+            e.consecutive_action = None if cons_action[i] < 0 else int(cons_action[i])
+            e.consecutive_count, e.last_consecutive_penalty = int(cons_count[i]), pen
+            feed.env_q = [int(dpos[i]), int(dval[i])]
+            b, r, d, m = e.step(int(actions[i]))
+            for k, v in (("board", lg(b)), ("reward", float(r)), ("done", bool(d)), ("max", int(m)),
+                         ("score", int(e.score)), ("prev", int(np.log2(e.previous_max))),
+                         ("count", int(e.consecutive_count)), ("penalty", float(e.last_consecutive_penalty))):
+                want[k].append(v)
+    out.update(es_board=boards, es_action=actions.astype(np.uint8), es_dpos=dpos, es_dval=dval,
+               es_prev=prev.astype(np.int64), es_cons_action=cons_action.astype(np.int64),
+               es_cons_count=cons_count.astype(np.int64), es_score0=score0.astype(np.int64),
+               es_want_board=np.array(want["board"], dtype=np.uint8),
+               es_want_reward=np.array(want["reward"], dtype=np.float64),
+               es_want_done=np.array(want["done"], dtype=np.uint8), es_want_max=np.array(want["max"], dtype=np.int64),
+               es_want_score=np.array(want["score"], dtype=np.int64), es_want_prev=np.array(want["prev"], dtype=np.int64),
+               es_want_count=np.array(want["count"], dtype=np.int64),
+               es_want_penalty=np.array(want["penalty"], dtype=np.float64))
+
+    # short training loops: 120 steps of Agent/main.py:91-101 with injected draws, the whole dict at the end
+    seeds = rng.integers(0, 1 << 32, loops, dtype=np.uint64)
+    env_ids = rng.integers(0, (1 << 40) + 1, loops, dtype=np.int64)
+    epss = rng.choice(np.array([0.0, 0.2, 0.9, 1.0]), loops)
+    cols = {k: [] for k in ("actions", "rewards", "dones", "final_boards", "q_keys", "q_vals", "n_keys")}
+    for i in range(loops):
+        tr = run_loop(env_mod, agent_mod, B=1, seed=int(seeds[i]), env_id0=int(env_ids[i]), total_steps=120, E=1000,
+                      eps0=float(epss[i]), gamma=0.95, decay=False)
+        for k in ("actions", "rewards", "dones", "final_boards", "q_keys", "q_vals"):
+            cols[k].append(tr[k])
+        cols["n_keys"].append(len(tr["q_keys"]))
+    out.update(tl_seed=seeds, tl_env_id=env_ids, tl_eps=epss, tl_actions=np.stack(cols["actions"]),
+               tl_rewards=np.stack(cols["rewards"]), tl_dones=np.stack(cols["dones"]),
+               tl_final_boards=np.concatenate(cols["final_boards"]), tl_q_keys=np.concatenate(cols["q_keys"]),
+               tl_q_vals=np.concatenate(cols["q_vals"]), tl_n_keys=np.array(cols["n_keys"], dtype=np.int64))
+
+    # the DQN path's env: boards weighted towards full ones (is_game_over's own moves only happen there)
+    kind = rng.integers(0, 3, count)
+    boards = np.where((kind == 0)[:, None], _g9_boards(rng, count),
+                      np.where((kind == 1)[:, None], _g9_boards(rng, count, hi=5, lo=1), _g9_boards(rng, count, hi=3, lo=1)))
+    actions, score0 = rng.integers(0, 4, count), rng.integers(0, 5001, count)
+    draws4 = np.stack([_g9_u32(rng, count) for _ in range(4)], axis=1)
+    want = {k: [] for k in ("board", "reward", "done", "max", "score")}
+    with InjectedDqn(dqn_mod, feed):
+        for i in range(count):
+            feed.env_q = [0] * 4
+            e = dqn_mod.Game2048_env()
+            e.game.board = raw(boards[i]).astype(int)
+            e.score = int(score0[i])
+            feed.env_q, feed.over_q = [int(draws4[i, 0]), int(draws4[i, 1])], [int(draws4[i, 2]), int(draws4[i, 3])]
+            b, r, d, m = e.step(int(actions[i]))
+            for k, v in (("board", lg(b)), ("reward", float(r)), ("done", bool(d)), ("max", int(m)),
+                         ("score", int(e.score))):
+                want[k].append(v)
+    out.update(dq_board=boards.astype(np.uint8), dq_action=actions.astype(np.uint8), dq_draws=draws4,
+               dq_score0=score0.astype(np.int64), dq_want_board=np.array(want["board"], dtype=np.uint8),
+               dq_want_reward=np.array(want["reward"], dtype=np.float64),
+               dq_want_done=np.array(want["done"], dtype=np.uint8), dq_want_max=np.array(want["max"], dtype=np.int64),
+               dq_want_score=np.array(want["score"], dtype=np.int64))
+    np.savez_compressed(os.path.join(HERE, "g9_live_properties.npz"), **out)
+    print("G9 live properties:", count, "cases per env property,", loops, "training loops,",
+          int(out["tl_n_keys"].sum()), "Q rows")
+
+
+def gen_g10():
+    """The reference's own run summary (plots/summary_statistics_cleaned.csv, a result file), kept as it is: its
+    header is the layout summary.py writes."""
+    with open(os.path.join(REF, "QLearningBase", "plots", "summary_statistics_cleaned.csv")) as fh:
+        text = fh.read()
+    with open(os.path.join(HERE, "g10_summary_statistics_cleaned.csv"), "w") as fh:
+        fh.write(text)
+    print("G10 summary layout:", text.splitlines()[0])
+
+
 def main():
     if "--only-g8" in sys.argv:
         gen_g8(import_reference_dqn_env())
+        return
+    if "--only-g9" in sys.argv:
+        env_mod, agent_mod = import_reference()
+        gen_g9(env_mod, agent_mod, import_reference_dqn_env())
+        gen_g10()
         return
     env_mod, agent_mod = import_reference()
     gen_g8(import_reference_dqn_env())
@@ -616,6 +758,8 @@ def main():
     gen_g4(env_mod)
     gen_g5(env_mod, agent_mod)
     gen_g6(env_mod, agent_mod)
+    gen_g9(env_mod, agent_mod, import_reference_dqn_env())
+    gen_g10()
 
 
 if __name__ == "__main__":

@@ -2857,17 +2857,68 @@ def test_bench_self_launched_two_ranks_share_one_gpu():
     assert rec["n_gpus"] == 2 and rec["scaling"] == "weak" and rec["steps"] == K and rec["warmup"] == 8
     assert rec["config"]["total_boards"] == 2 * B and rec["config"]["boards_per_gpu"] == B
     assert rec["stats"]["episodes"] > 0 and rec["stats"]["drops"] == 0 and rec["stats"]["status"] == 0
-    assert rec["cpu_baseline"] is None and "companions" not in rec          # --cpu-seconds 0
+    assert rec["cpu_baseline"] is None and "companions" not in rec          # a plain run: the headline only
     assert len(rec["region_ms"]) == 3 and rec["value"] > 0
     assert abs(rec["value"] - 2 * B * K / (rec["ms_per_step"] * K / 1e3)) < 1e-6 * rec["value"]
     # the CPU path is timed beside the GPU number at N > 1 too (rank 0, after the GPU regions)
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "8",
                         "--warmup", "4", "--boards-per-gpu", str(1 << 14), "--cap-log2", "22", "--prep-steps", "256",
-                        "--repeats", "2", "--cpu-seconds", "1.5"], capture_output=True, text=True, timeout=600, env=env)
+                        "--repeats", "2", "--cpu-seconds", "1.5", "--full"], capture_output=True, text=True, timeout=600,
+                       env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     rec = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][0])
     assert rec["n_gpus"] == 2 and rec["cpu_baseline"]["kind"] == "port" and rec["cpu_baseline"]["value"] > 1e5
     assert rec["cpu_baseline"]["cores"] >= 1 and "single_thread" in rec["cpu_baseline"]
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps in one region, measures nothing but the headline, and with
+    --dump-outputs writes what the timed path computed (float32 / float64 .npy, a fixed sample of envs, well under
+    64 MB).  Every env learns on private rows, so two runs with the same arguments compute the same arrays (the float64
+    statistics sums up to the order of their additions); --shared-table switches to one lock-free row per state."""
+    release_cached_device_memory()
+    import subprocess
+    import sys
+
+    from conftest import REPO
+
+    B, K = 1 << 17, 12
+    recs = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(K),
+                            "--warmup", "3", "--boards-per-gpu", str(B), "--cap-log2", "24", "--prep-steps", "128",
+                            "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+    for rec in recs:
+        assert rec["steps"] == K and len(rec["region_ms"]) == 1 and rec["stats"]["episodes"] > 0
+        assert rec["ms_per_step"] == pytest.approx(rec["region_ms"][0] / K, rel=1e-3)
+        assert rec["metric"] == "env_steps_per_sec" and rec["higher_is_better"] is True and rec["dtype"] == "u8"
+        assert rec["cpu_baseline"] is None and "companions" not in rec and rec["config"]["full"] is False
+        assert rec["config"]["q_rows"] == "private per env"
+    a = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    b = {f.stem: np.load(f) for f in (tmp_path / "b").glob("*.npy")}
+    assert sorted(a) == sorted(b) and {"boards", "q_values", "q_found", "stats_i", "stats_f", "env_ids"} <= set(a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) < 64e6
+    n = len(a["env_ids"])
+    assert n == 1 << 16 and np.all(np.diff(a["env_ids"]) > 0) and a["boards"].shape == (n, 16)
+    assert a["q_values"].shape == (n, 4) and a["stats_i"][0] == B * K            # ST_STEPS: the last region's steps
+    assert a["q_found"].mean() > 0.5 and (a["q_values"] != 0).any()            # the envs have learnt rows
+    for k in a:
+        if k == "stats_f":
+            assert np.allclose(a[k], b[k], rtol=1e-12, atol=0), k
+        else:
+            assert np.array_equal(a[k], b[k]), k
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", "3",
+                        "--boards-per-gpu", str(B), "--cap-log2", "24", "--prep-steps", "128", "--shared-table"],
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    rec = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][0])
+    assert rec["config"]["q_rows"].startswith("one per state") and rec["stats"]["episodes"] > 0
 
 
 def test_check_shards_across_processes():

@@ -101,6 +101,26 @@ def test_bench_traffic_comes_only_from_a_matching_pmc_profile(tmp_path, monkeypa
             assert len(json.load(open(path))["kernel_sources_sha16"]) == 16, path
 
 
+def test_bench_options_plain_run_and_output_dump(tmp_path):
+    """A plain bench run times --steps steps in one region and nothing else (the CPU baselines and the companion
+    runs are --full's); --dump-outputs writes every array it is given as DIR/<name>.npy."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.steps == 20 and a.warmup == 5 and a.repeats == 1 and not a.full and a.dump_outputs is None
+    assert not a.shared_table                                     # private rows per env: reproducible runs
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path / "o")])
+    assert a.full and a.dump_outputs == str(tmp_path / "o")
+    arrays = {"boards": np.arange(32, dtype=np.float32).reshape(2, 16), "stats_f": np.ones(4)}
+    bench.write_outputs(str(tmp_path / "o"), arrays)
+    for name, arr in arrays.items():
+        got = np.load(tmp_path / "o" / f"{name}.npy")
+        assert got.dtype == arr.dtype and np.array_equal(got, arr)
+
+
 def test_header_structs_match_numpy_layout(pkg):
     assert pkg.AUX_DTYPE.itemsize == 16
     assert [pkg.AUX_DTYPE.fields[k][1] for k in pkg.AUX_DTYPE.names] == [0, 4, 8, 9, 10, 12]
@@ -245,10 +265,8 @@ def test_run_summary_has_the_reference_layout(pkg, tmp_path):
     pkg.write_summary([row, row], str(out))
     lines = out.read_text().strip().splitlines()
     assert lines[0] == ",".join(pkg.SUMMARY_HEADER) and len(lines) == 3
-    ref = "/root/reference/QLearningBase/plots/summary_statistics_cleaned.csv"
-    if os.path.exists(ref):                       # only where the reference is mounted
-        with open(ref) as fh:
-            assert fh.readline().strip() == lines[0]
+    with open(os.path.join(REPO, "tests", "golden", "g10_summary_statistics_cleaned.csv")) as fh:   # the reference's own
+        assert fh.readline().strip() == lines[0]
     with pytest.raises(ValueError):
         pkg.summarize_episodes("x", [0, 4], [0.0, 1.0], [2, 4])
     with pytest.raises(ValueError):

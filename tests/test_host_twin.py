@@ -137,8 +137,9 @@ def test_train_two_ranks_on_the_cpu_device_equal_one_rank(tmp_path):
     import subprocess
 
     common = ["--device", "cpu", "--epsilon", "1.0", "--max-steps", "64", "--steps-per-launch", "32", "--episodes", "50"]
+    env = dict(os.environ, Q2048_DIST_BACKEND="gloo")              # (a GPU on the box would make the group RCCL's)
     run = lambda *a: subprocess.run([sys.executable, os.path.join(REPO, "train.py"), *common, *a],   # noqa: E731
-                                    capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+                                    capture_output=True, text=True, timeout=600, cwd=str(tmp_path), env=env)
     p2 = run("--gpus", "2", "--num-envs", "2048", "--capacity-log2", "20", "--log", "two.csv")
     assert p2.returncode == 0, p2.stderr[-2000:]
     assert (p2.stdout + p2.stderr).count("table check passed") == 2   # both ranks checked their replica (rank 1 reports on stderr)
@@ -196,7 +197,7 @@ def test_eight_ranks_on_the_cpu_device_equal_one_rank(tmp_path):
     import json
     import subprocess
 
-    env = dict(os.environ, Q2048_HOST_THREADS="1")
+    env = dict(os.environ, Q2048_HOST_THREADS="1", Q2048_DIST_BACKEND="gloo")   # (gloo even where a GPU is visible)
     def shards(gpus, per):
         p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--check-shards", "--device", "cpu", "--gpus",
                             str(gpus), "--boards-per-gpu", str(per), "--steps", "24", "--steps-per-launch", "8"],

@@ -20,19 +20,19 @@ cat "$OUT/smoke.log" | tee -a "$OUT/session.log"
 ok $rc || exit 1
 
 echo "== bench (short)" | tee -a "$OUT/session.log"
-timeout -k 10 600 python bench.py --steps 64 --warmup 32 --cpu-seconds 6 > "$OUT/bench_short.json" 2> "$OUT/bench_short.err"; rc=$?
+timeout -k 10 600 python bench.py --full --repeats 5 --steps 64 --warmup 32 --cpu-seconds 6 > "$OUT/bench_short.json" 2> "$OUT/bench_short.err"; rc=$?
 cat "$OUT/bench_short.json" | tee -a "$OUT/session.log"; tail -n 5 "$OUT/bench_short.err"
 ok $rc || exit 1
 [ $rc -eq 0 ] || exit 1
 
 echo "== bench (default)" | tee -a "$OUT/session.log"
-timeout -k 10 900 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
+timeout -k 10 900 python bench.py --full --repeats 5 > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
 cat "$OUT/bench.json" | tee -a "$OUT/session.log"; tail -n 5 "$OUT/bench.err"
 ok $rc || exit 1
 
 echo "== rocprofv3 kernel trace" | tee -a "$OUT/session.log"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -- \
-    python3 bench.py --steps 64 --warmup 32 --cpu-seconds 0 > "$OUT/prof_bench.json" 2> "$OUT/prof.err"; rc=$?
+    python3 bench.py --full --repeats 5 --steps 64 --warmup 32 --cpu-seconds 0 > "$OUT/prof_bench.json" 2> "$OUT/prof.err"; rc=$?
 echo "rocprof rc=$rc" | tee -a "$OUT/session.log"
 find "$OUT/prof" -name "*kernel_stats.csv" | head -n 3 | while read -r f; do echo "-- $f"; head -n 12 "$f"; done | tee -a "$OUT/session.log"
 exit 0

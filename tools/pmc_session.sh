@@ -1,6 +1,7 @@
 #!/usr/bin/env bash
 # rocprofv3 counter passes on a short bench run (each --pmc set in its own pass, never combined
 # with a trace domain other than --kernel-trace).  Usage: bash tools/pmc_session.sh <tag> [bench args]
+# (the committed passes under profiles/ are of the shared table: pass --shared-table to take them again)
 set -u
 TAG=${1:-r02}
 shift || true
