@@ -45,7 +45,7 @@ class RolloutOpts(C.Structure):
     """q2048_rollout_opts (include/q2048.h): the optional extras of q2048_fused_rollout_opts."""
     _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32), ("log", C.c_void_p),
                 ("log_capacity", C.c_int64), ("log_count", C.c_void_p), ("row_cache", C.c_void_p),
-                ("stats_mirror", C.c_void_p), ("mirror_ticket", C.c_void_p)]
+                ("stats_mirror", C.c_void_p), ("mirror_ticket", C.c_void_p), ("line_summary", C.c_void_p)]
 
     def __init__(self, **kw):
         super().__init__(size=C.sizeof(RolloutOpts), **kw)
@@ -196,6 +196,7 @@ _SIGNATURES = {
     "q2048_table_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_uint64, C.c_void_p]),
     "q2048_table_count": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "q2048_table_summarise": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "q2048_table_summarise_side": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "q2048_det_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int]),
     "q2048_det_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int,
                                     C.c_int64, C.c_double, C.c_double, C.c_double, C.c_uint64,

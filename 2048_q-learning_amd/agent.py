@@ -390,6 +390,11 @@ class BatchedQLearningAgent:
         # a 4x4 table with a closed key set carries LINE SUMMARIES (q2048_table_summarise, Q2048_FLAG_LINE_SUMMARY): one
         # request per lookup of an absent state instead of 2.35 -- written by the first launch after the key set closed
         self.line_summaries, self._summarised = True, False
+        # a 5x5 slot has no spare word: its summaries live BESIDE the table (q2048_table_summarise_side: 8 bytes per
+        # 128-byte line, 1/16 of the table), allocated and written by the first learning launch after the key set
+        # closed.  `_side`: the array while it describes this table's key set, else None (`side_summarised`);
+        # `_side_refused`: the capacity whose array the device had no room for (slot by slot from then on)
+        self._side, self._side_refused = None, None
         if self.growable:
             if not 0.05 <= self.load_limit <= 0.9:
                 raise ValueError("load_limit must be in [0.05, 0.9]")
@@ -472,6 +477,35 @@ class BatchedQLearningAgent:
             c = self._row_cache = torch.zeros((B, int(self._L.q2048_sizeof_rowcache(self.board_size))),
                                               dtype=torch.uint8, device=self.device)
         return c
+
+    @property
+    def side_summarised(self) -> bool:
+        """A 5x5 table's line summaries (the array beside it) describe its key set as it is now."""
+        return self._side is not None
+
+    def _alloc_side_summaries(self, words: int) -> torch.Tensor:
+        """The side array of a 5x5 table: `words` 8-byte words on the agent's device."""
+        return torch.empty(words, dtype=torch.int64, device=self.device)
+
+    def _side_summaries(self):
+        """The line summaries of a 5x5 table whose key set is closed, for a learning launch of `fused_rollout`: the
+        array beside the table, allocated (2^(capacity_log2-2) words) and written -- one streaming pass, queued ahead of
+        the launch -- when there is none that describes this key set.  None when the launch has to probe slot by slot:
+        `line_summaries` off, or the device had no room for the array (one warning, no further attempt)."""
+        if not self.line_summaries or self._side_refused == self.capacity_log2:
+            return None
+        if self._side is None:
+            try:
+                side = self._alloc_side_summaries(1 << (self.capacity_log2 - 2))
+            except (RuntimeError, MemoryError) as exc:    # (torch.OutOfMemoryError is a RuntimeError)
+                self._side_refused = self.capacity_log2
+                warnings.warn(f"no room for the line summaries of the 5x5 Q-table ({8 << (self.capacity_log2 - 2)} bytes "
+                              f"beside 2^{self.capacity_log2} slots: {exc}); lookups go on slot by slot (same results)")
+                return None
+            N.check(self._L.q2048_table_summarise_side(_ptr(self.table), self.capacity_log2, 2, _ptr(side),
+                                                       _stream(self.device)), "table_summarise_side")
+            self._side = side
+        return self._side
 
     def invalidate_row_cache(self) -> None:
         """After the table was changed by anything but choose_action / update_q_value."""
@@ -566,16 +600,22 @@ class BatchedQLearningAgent:
         # the row every env carries goes from launch to launch (and to choose_action / update_q_value)
         # through the row cache; a learner-less launch touches neither the table nor the cache
         cache = None if play_only else self._cache(env.num_envs)
+        flags, side = self.flags, None
+        if learn and not play_only:
+            flags = self._learn_flags()
+            if self.frozen and self.board_size == 5:      # (4x4: in the slots, `_learn_flags`)
+                side = self._side_summaries()
+                flags |= N.FLAG_LINE_SUMMARY if side is not None else 0
         opts = N.RolloutOpts(
             log=_ptr(log.records) if log is not None else None, log_capacity=log.capacity if log is not None else 0,
             log_count=_ptr(log.count) if log is not None else None, row_cache=_ptr(cache),
             stats_mirror=self._mirror.data_ptr() if self.stats_i is not None and self.stats_f is not None else None,
-            mirror_ticket=_ptr(self._mirror_ticket))
+            mirror_ticket=_ptr(self._mirror_ticket), line_summary=_ptr(side))
         N.check(self._L.q2048_fused_rollout_opts(
             _ptr(env.boards), _ptr(env.aux), _ptr(self.table), self.capacity_log2, env.num_envs,
             self.board_size, int(steps), float(self.epsilon), float(self.lr), float(self.gamma), self.seed,
             self.env_id0, self.ctr & 0xFFFFFFFF,
-            (self._learn_flags() if learn and not play_only else self.flags) | self.experiment_bits | env.env_flags |
+            flags | self.experiment_bits | env.env_flags |
             (N.FLAG_PLAY_ONLY if play_only else 0) | (0 if learn else N.FLAG_NO_LEARN),
             _ptr(self.stats_i), _ptr(self.stats_f), _ptr(self.status), C.byref(opts), _stream(self.device)),
             "fused_rollout")
@@ -645,9 +685,11 @@ class BatchedQLearningAgent:
     def _learn_flags(self) -> int:
         """The agent's flags for a call that may create rows: with the key set closed, Q2048_FLAG_NO_NEW_ROWS -- and,
         on a 4x4 table, Q2048_FLAG_LINE_SUMMARY once the summaries of THIS key set are written (one streaming pass,
-        queued ahead of the first launch that uses them; a call that may create rows ends their validity)."""
+        queued ahead of the first launch that uses them; a call that may create rows ends their validity).  A 5x5
+        table's summaries lie beside it and only `fused_rollout` reads them (`_side_summaries`: pointer and flag are its
+        business); what ends their validity is the same and is noted here."""
         if not self.frozen:
-            self._summarised = False
+            self._summarised, self._side = False, None
             return self.flags
         if self.board_size == 4 and self.line_summaries and not self._summarised:
             N.check(self._L.q2048_table_summarise(_ptr(self.table), self.capacity_log2, _stream(self.device)),
@@ -659,7 +701,7 @@ class BatchedQLearningAgent:
         """`rows` rows are in the table now (a count, an import): the new base of the row bookkeeping."""
         if table_changed:
             self.frozen = False                           # (decided again by the next `_room_for`)
-            self._summarised = False                      # (line summaries describe a key set that is gone)
+            self._summarised, self._side = False, None    # (line summaries describe a key set that is gone)
         self._rows_base = int(rows)
         self._inserts_at_base = self._inserts_seen = self._cumulative_inserts()
         self._steps_at_read, self._steps_unseen = self._steps_launched, 0
@@ -797,6 +839,7 @@ class BatchedQLearningAgent:
                        "at_step": self.ctr, "host_ms": round((time.perf_counter() - t0) * 1e3, 3), "events": ev})
         self.capacity_log2 = g.new_capacity_log2
         self.invalidate_row_cache()                       # slots changed
+        self._side = None                                 # (and lines: another table, another size)
         self._growth, self._retiring = None, g
         if self.prefetch_growth:
             self._begin_growth()
@@ -872,6 +915,7 @@ class BatchedQLearningAgent:
                              "ms": round(t0[0].elapsed_time(t0[1]), 3), "at_step": self.ctr})
         self.capacity_log2 = new
         self.invalidate_row_cache()
+        self._side = None
         if moved != expected:
             raise RuntimeError(f"Q-table self-check failed at the growth to 2^{new}: {moved} occupied slots moved, "
                                f"{expected} rows created according to the kernels' counters")
@@ -887,6 +931,7 @@ class BatchedQLearningAgent:
         self.table = torch.zeros((1 << new, N.SIZEOF_SLOT), dtype=torch.uint8, device=self.device)
         old, self.capacity_log2 = self.capacity_log2, new
         self.invalidate_row_cache()
+        self._side = None
         if len(q):
             tk = torch.from_numpy(np.ascontiguousarray(keys).view(np.int64).reshape(len(q), -1))
             self.import_rows_device(tk.reshape(-1) if self.board_size == 4 else tk, torch.from_numpy(q))
@@ -1067,7 +1112,7 @@ class BatchedQLearningAgent:
             return
         keys, q = keys.to(self.device).contiguous(), q.to(self.device).contiguous()
         self.invalidate_row_cache()
-        self._summarised = False                          # (rows arrive: line summaries stop describing the table)
+        self._summarised, self._side = False, None        # (rows arrive: line summaries stop describing the table)
         N.check(self._L.q2048_table_import(_ptr(self.table), self.capacity_log2, _ptr(keys), _ptr(q), rows, words,
                                            _ptr(self.status), _stream(self.device)), "table_import")
 

@@ -485,6 +485,38 @@ Q_HD uint64_t mix64(uint64_t h) {
 // independent-learners mode: every env owns private rows of the shared table
 Q_HD uint64_t lane_salt(uint64_t env_id) { return mix64(env_id + 0x2048ull) | 1ull; }
 
+// ------------------------------------------------------------------------------------------
+// LINE SUMMARIES of a table whose key set is closed (include/q2048.h, Q2048_FLAG_LINE_SUMMARY): one 64-bit
+// word per 128-byte line of four slots, bits 16r..16r+15 = 0 when slot r is empty, else the fingerprint of
+// its key (bits 48..63 of the key's hash, | 1: never 0).  4x4 tables keep the word in the slots' spare
+// field, 5x5 tables in an array beside the table (q2048_table_summarise_side).
+// summary_decode turns a word into the slots a lookup still has to look at, in the order of the key's
+// probe sequence (which enters the line at slot `off`): bit j of `ev` = the slot at position j, slot
+// (off + j) & 3, is empty or carries the key's fingerprint; bit r of `empty` = slot r is empty.
+// summary_pop takes them one by one: `absent` = the sequence ends at slot r (the key has no row),
+// otherwise slot r is a candidate whose key words settle it.  The 5x5 kernels and the CPU twin both
+// decide their closed-key-set lookups through these two functions.
+// ------------------------------------------------------------------------------------------
+Q_HD uint64_t summary_fp(uint64_t hash) { return ((hash >> 48) & 0xffffull) | 1ull; }   // never 0
+struct SummaryHits { uint32_t ev, empty; };
+Q_HD SummaryHits summary_decode(uint64_t word, uint64_t fp, uint32_t off) {
+  uint32_t e = 0u, m = 0u;
+#pragma unroll
+  for (uint32_t r = 0; r < 4u; ++r) {
+    const uint64_t f = (word >> (16u * r)) & 0xffffull;
+    e |= (uint32_t)(f == 0ull) << r;
+    m |= (uint32_t)(f == fp) << r;
+  }
+  return SummaryHits{(((e | m) | ((e | m) << 4)) >> (off & 3u)) & 15u, e};
+}
+Q_HD bool summary_pop(SummaryHits& h, uint32_t off, uint32_t& r, bool& absent) {
+  if (h.ev == 0u) return false;
+  r = (off + (uint32_t)__builtin_ctz(h.ev)) & 3u;
+  absent = ((h.empty >> r) & 1u) != 0u;
+  h.ev &= h.ev - 1u;
+  return true;
+}
+
 // np.argmax: first maximum (Agent/main.py:38,41)
 Q_HD int argmax4(float q0, float q1, float q2, float q3) {
   int b = 0;

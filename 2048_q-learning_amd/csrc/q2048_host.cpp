@@ -22,6 +22,7 @@
 //   g++ -O3 -std=c++17 -fPIC -shared -pthread -I include -I 2048_q-learning_amd/csrc \
 //       -o 2048_q-learning_amd/csrc/libq2048_host.so 2048_q-learning_amd/csrc/q2048_host.cpp
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -134,6 +135,32 @@ inline int64_t probe_find(const q2048_slot* table, u64 mask, const Key& key, Row
     if (k == key.k0 && slot_is(&table[i], key)) { row = ld_row(&table[i]); return (int64_t)i; }
   }
   return kNoSlot;
+}
+// The lookup of a 5x5 table with a closed key set from its side array of LINE SUMMARIES (q2048_table_summarise_side):
+// the kernel's probe_find_summary, through the very decode it uses (q2048_core.hpp: summary_decode / summary_pop) --
+// one word per line of the sequence says where the sequence ends (absent) or which slots can hold the key.  Visits the
+// slots probe_find visits, in its order, under the same limit; no wait for a second key word (the key set is closed).
+inline int64_t probe_find_summary(const q2048_slot* table, const uint64_t* side, u64 mask, const Geo<5>::Key& key, Row& row,
+                                  uint32_t maxp = kRolloutProbe) {
+  const u64 hash = key_hash(key);
+  const Seq sq = seq_of(hash, mask);
+  const u64 fp = summary_fp(hash);
+  row = Row{0.f, 0.f, 0.f, 0.f};
+  for (uint32_t p = 0, lim = probe_limit(mask, maxp); p < lim; p += 4u) {
+    const u64 line = (sq.line0 + (u64)(p >> 2)) & sq.lmask;
+    SummaryHits hits = summary_decode(ld_u64(&side[line]), fp, sq.off);
+    uint32_t r;
+    bool absent;
+    while (summary_pop(hits, sq.off, r, absent)) {
+      const u64 i = (line << 2) | (u64)r;
+      if (absent) return ~(int64_t)i;
+      if (ld_u64(&table[i].key) == key.k0 && ld_u64(&table[i].reserved) == key.k1) { row = ld_row(&table[i]); return (int64_t)i; }
+    }
+  }
+  return kNoSlot;
+}
+inline int64_t probe_find_summary(const q2048_slot* table, const uint64_t*, u64 mask, const Geo<4>::Key& key, Row& row) {
+  return probe_find(table, mask, key, row);   // (4x4: the in-slot summaries are written, not read, by this library)
 }
 // find-or-create from slot `start` of the key's sequence on
 template <class Key>
@@ -293,8 +320,9 @@ inline int check_table(const void* table, int cap_log2) {
 }
 constexpr uint32_t kAbiFlags = Q2048_FLAG_INDEPENDENT | Q2048_FLAG_SINGLE_ENV | Q2048_FLAG_TD_CAS | Q2048_FLAG_ENV_DQN |
                                Q2048_FLAG_RESET_SHAPING | Q2048_FLAG_PLAY_ONLY | Q2048_FLAG_NO_LEARN |
-                               Q2048_FLAG_NO_NEW_ROWS | Q2048_FLAG_LINE_SUMMARY;   // (the last one: accepted, not used --
-                                                                                   // this library probes slot by slot; same results)
+                               Q2048_FLAG_NO_NEW_ROWS | Q2048_FLAG_LINE_SUMMARY;   // (the last one: 4x4 accepted, not used --
+                                                                                   // slot by slot, same results; 5x5 with a side
+                                                                                   // array: used, fused_rollout_n)
 inline int check_flags(uint32_t flags, uint32_t refused = 0u) {
   return ((flags & ~kAbiFlags) || (flags & refused)) ? Q2048_ERR_FLAGS : Q2048_OK;
 }
@@ -508,7 +536,7 @@ template <int N>
 void fused_rollout_n(uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mask, int64_t B, int steps, double eps,
                      double lr, double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
                      int64_t* stats_i, double* stats_f, uint32_t* status, q2048_episode* log, int64_t log_cap,
-                     uint64_t* log_count, void* cache) {
+                     uint64_t* log_count, void* cache, const uint64_t* side) {
   using BoardT = typename Geo<N>::BoardT;
   using Key = typename Geo<N>::Key;
   struct Lane {
@@ -519,10 +547,15 @@ void fused_rollout_n(uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mas
   const bool play_only = (flags & Q2048_FLAG_PLAY_ONLY) != 0, no_learn = (flags & Q2048_FLAG_NO_LEARN) != 0;
   const bool learns = !play_only && !no_learn, frozen = (flags & Q2048_FLAG_NO_NEW_ROWS) != 0;
   const bool creates = learns && !frozen, cas = (flags & Q2048_FLAG_TD_CAS) != 0;
+  // 5x5, key set closed, Q2048_FLAG_LINE_SUMMARY and a side array: the lookups are decided from it, as on the device
+  const bool summary = N == 5 && learns && frozen && (flags & Q2048_FLAG_LINE_SUMMARY) != 0 && side != nullptr;
   const int T = threads_for(B);
   std::vector<Stats> parts((size_t)T);
   Stats* sp = parts.data();
   const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+    auto find = [=](const Key& key, Row& row) {
+      return summary ? probe_find_summary(table, side, mask, key, row) : probe_find(table, mask, key, row);
+    };
     Stats& st = sp[tid];
     TdCounters tdc;
     bool any_drop = false;
@@ -540,7 +573,7 @@ void fused_rollout_n(uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mas
         // the row of the current state: read when the state is reached and carried (as the kernel carries it in
         // registers); created at its first update (the defaultdict creates q_table[state] at :43)
         L.q = Row{0.f, 0.f, 0.f, 0.f};
-        L.slot_s = play_only ? kNoSlot : probe_find(table, mask, L.key_s, L.q);
+        L.slot_s = play_only ? kNoSlot : find(L.key_s, L.q);
         if (frozen && learns && L.slot_s < 0) visit_get<N>(cache, i, table, mask, L.key_s, L.q);   // the visit row goes on
         L.reward_sum = 0.0;
       }
@@ -567,7 +600,7 @@ void fused_rollout_n(uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mas
           if (!L.same) {
             if (play_only) { qn = Row{0.f, 0.f, 0.f, 0.f}; slot_n = kNoSlot; }
             else if (creates) slot_n = find_or_create(table, mask, L.key_n, qn, ins_n);
-            else slot_n = probe_find(table, mask, L.key_n, qn);
+            else slot_n = find(L.key_n, qn);
           }
           const float max_next = max4(qn.q0, qn.q1, qn.q2, qn.q3);
           const bool updated = L.slot_s >= 0;
@@ -603,7 +636,7 @@ void fused_rollout_n(uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mas
             begin_episode(L.b, L.a, seed, L.id, (env & kEnvResetShaping) != 0);                  // :81
             L.key_s = state_key(L.b, L.salt, status);
             L.q = Row{0.f, 0.f, 0.f, 0.f};
-            L.slot_s = play_only ? kNoSlot : probe_find(table, mask, L.key_s, L.q);
+            L.slot_s = play_only ? kNoSlot : find(L.key_s, L.q);
           } else if (L.same) {           // invalid move: same state, its row just changed (:100)
             if ((updated || (frozen && learns)) && !no_learn) row_set(L.q, act, nq);
             else if (!updated) L.slot_s = kNoSlot;
@@ -885,14 +918,16 @@ int q2048_fused_rollout_opts(uint8_t* boards, q2048_aux* aux, q2048_slot* table,
                              const q2048_rollout_opts* opts, void*) {
   q2048_rollout_opts o = {};
   if (opts != nullptr) {
-    if (opts->size != sizeof(q2048_rollout_opts)) return Q2048_ERR_SIZE;
-    o = *opts;
+    // the 56-byte layout shipped before `line_summary` (no side array) or this one
+    if (opts->size != sizeof(q2048_rollout_opts) && opts->size != offsetof(q2048_rollout_opts, line_summary)) return Q2048_ERR_SIZE;
+    std::memcpy(&o, opts, opts->size);
   }
   if (int e = check_batch(B, n)) return e;
   if (int e = check_flags(flags)) return e;
   if (o.log != nullptr && (o.log_count == nullptr || o.log_capacity < 0)) return Q2048_ERR_NULL;
   if (o.log != nullptr && !aligned16(o.log)) return Q2048_ERR_ALIGN;
   if (o.row_cache != nullptr && !aligned16(o.row_cache)) return Q2048_ERR_ALIGN;
+  if (reinterpret_cast<uintptr_t>(o.line_summary) & 7u) return Q2048_ERR_ALIGN;
   if (o.stats_mirror != nullptr && (o.mirror_ticket == nullptr || stats_i == nullptr || stats_f == nullptr))
     return Q2048_ERR_NULL;
   if (o.stats_mirror != nullptr && (reinterpret_cast<uintptr_t>(o.stats_mirror) & 7u)) return Q2048_ERR_ALIGN;
@@ -904,9 +939,9 @@ int q2048_fused_rollout_opts(uint8_t* boards, q2048_aux* aux, q2048_slot* table,
   if (B == 0 || steps == 0) return Q2048_OK;
   const u64 mask = (1ull << cap_log2) - 1ull;
   if (n == 4) fused_rollout_n<4>(boards, aux, table, mask, B, (int)steps, eps, lr, gamma, seed, env_id0, ctr0, flags,
-                                 stats_i, stats_f, status, o.log, o.log_capacity, o.log_count, o.row_cache);
+                                 stats_i, stats_f, status, o.log, o.log_capacity, o.log_count, o.row_cache, nullptr);
   else fused_rollout_n<5>(boards, aux, table, mask, B, (int)steps, eps, lr, gamma, seed, env_id0, ctr0, flags, stats_i,
-                          stats_f, status, o.log, o.log_capacity, o.log_count, o.row_cache);
+                          stats_f, status, o.log, o.log_capacity, o.log_count, o.row_cache, o.line_summary);
   if (o.stats_mirror != nullptr) {               // the statistics as they stand after this call, and its number
     uint64_t* m = static_cast<uint64_t*>(o.stats_mirror);
     std::memcpy(m, stats_i, sizeof(int64_t) * Q2048_NSTAT_I);
@@ -1016,6 +1051,28 @@ int q2048_table_summarise(q2048_slot* table, int cap_log2, void*) {
       for (int r = 0; r < 4; ++r)
         if (s[r].key != 0ull) sum |= (((mix64(s[r].key) >> 48) & 0xffffull) | 1ull) << (16 * r);
       for (int r = 0; r < 4; ++r) s[r].reserved = sum;
+    }
+  });
+  return Q2048_OK;
+}
+// the device's side array, byte for byte (k_table_summarise_side): the same words beside the table, which is only read
+int q2048_table_summarise_side(const q2048_slot* table, int cap_log2, int key_words, uint64_t* summary, void*) {
+  if (table == nullptr || summary == nullptr) return Q2048_ERR_NULL;
+  if (key_words != 1 && key_words != 2) return Q2048_ERR_SIZE;
+  if (reinterpret_cast<uintptr_t>(summary) & 7u) return Q2048_ERR_ALIGN;
+  if (int e = check_table(table, cap_log2)) return e;
+  const int64_t lines = (int64_t)((1ull << cap_log2) >> 2);
+  parallel_ranges(lines, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t l = lo; l < hi; ++l) {
+      const q2048_slot* s = table + (l << 2);
+      u64 sum = 0ull;
+      for (int r = 0; r < 4; ++r) {
+        const u64 k = s[r].key;
+        if (k == 0ull) continue;
+        const u64 hash = key_words == 2 ? key_hash(Geo<5>::Key{k, (u64)s[r].reserved}) : key_hash(Geo<4>::Key{k});
+        sum |= summary_fp(hash) << (16 * r);
+      }
+      summary[l] = sum;
     }
   });
   return Q2048_OK;

@@ -18,6 +18,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <ctime>
 #include <condition_variable>
 #include <deque>
@@ -363,7 +364,7 @@ __device__ __forceinline__ int64_t probe_find(const q2048_slot* table, u64 mask,
 // that request and nothing else).  Written by one streaming pass when the key set closes; meaningless as soon as a row
 // is created (the caller's contract, include/q2048.h).
 // ---------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ u64 summary_fp(u64 hash) { return ((hash >> 48) & 0xffffull) | 1ull; }   // never 0
+// (summary_fp, summary_decode, summary_pop: q2048_core.hpp, shared with the CPU twin)
 __global__ __launch_bounds__(kBlock) void k_table_summarise(q2048_slot* table, u64 lines) {
   for (u64 l = (u64)blockIdx.x * kBlock + threadIdx.x; l < lines; l += (u64)gridDim.x * kBlock) {
     q2048_slot* s = table + (l << 2);
@@ -414,9 +415,67 @@ __device__ __forceinline__ int64_t probe_find_summary(const q2048_slot* table, u
   }
   return kNoSlot;
 }
+// 5x5 (and any table whose summaries live BESIDE it: q2048_table_summarise_side): a 5x5 slot has no spare word, so
+// the line's word is side[line] -- 8 bytes per 128-byte line, 1/16 of the table.  The writer is one streaming pass:
+// one lane per line, four 16-byte reads of the key words (5x5: both halves of each slot), one coalesced 8-byte
+// store.  It never writes the table.
+template <int KEY_WORDS>
+__global__ __launch_bounds__(kBlock) void k_table_summarise_side(const q2048_slot* table, u64 lines, u64* side) {
+  for (u64 l = (u64)blockIdx.x * kBlock + threadIdx.x; l < lines; l += (u64)gridDim.x * kBlock) {
+    const uint4* s = reinterpret_cast<const uint4*>(table + (l << 2));   // slot r = s[2r] {key, q0, q1}, s[2r+1] {q2, q3, reserved}
+    u64 sum = 0ull;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const uint4 a = s[2 * r];
+      const u64 k = (u64)a.x | ((u64)a.y << 32);
+      u64 h = k;
+      if constexpr (KEY_WORDS == 2) {
+        const uint4 b = s[2 * r + 1];
+        h = k ^ (((u64)b.z | ((u64)b.w << 32)) * 0x9E3779B97F4A7C15ull);   // key_hash(Geo<5>::Key)
+      }
+      if (k != 0ull) sum |= summary_fp(mix64(h)) << (16 * r);
+    }
+    side[l] = sum;
+  }
+}
+// The lookup: ONE 8-byte agent-scope request per line of the sequence (side[line]), then nothing more for an absent
+// state; a slot with the key's fingerprint costs its head {key, q0, q1} and, on a first-word match, its second half
+// {q2, q3, second word}.  Visits the slots probe_find visits, in its order, under the same probe limit: same result.
+// No await_second: the key set is closed and the pass ran after the last creating launch, so every occupied slot
+// has its second word.
+__device__ __forceinline__ int64_t probe_find_summary(const q2048_slot* table, const u64* side, u64 mask,
+                                                      const Geo<5>::Key& key, Row& row, bool& created,
+                                                      uint32_t maxp = kRolloutProbe) {
+  const u64 hash = key_hash(key);
+  const Seq sq = seq_of(hash, mask);
+  const u64 fp = summary_fp(hash);
+  created = false;
+  row = Row{0.f, 0.f, 0.f, 0.f};
+  for (uint32_t p = 0, lim = probe_limit(mask, maxp); p < lim; p += 4u) {
+    const u64 line = (sq.line0 + (u64)(p >> 2)) & sq.lmask;
+    SummaryHits hits = summary_decode(ld_u64(&side[line]), fp, sq.off);
+    uint32_t r;
+    bool absent;
+    while (summary_pop(hits, sq.off, r, absent)) {
+      const u64 i = (line << 2) | (u64)r;
+      if (absent) return ~(int64_t)i;                                       // the sequence ends here
+      const u32x4 a = ld16_agent(&table[i]);                                // a candidate: its head ...
+      if (((u64)a.x | ((u64)a.y << 32)) == key.k0) {
+        const u32x4 b = ld16_agent(&table[i].q[2]);                         // ... and its second half settle it
+        if (((u64)b.z | ((u64)b.w << 32)) == key.k1) {
+          row = Row{bits_f32(a.z), bits_f32(a.w), bits_f32(b.x), bits_f32(b.y)};
+          return (int64_t)i;
+        }
+      }
+    }
+  }
+  return kNoSlot;
+}
 template <bool SUMMARY, class Key>
-__device__ __forceinline__ int64_t probe_find_as(const q2048_slot* table, u64 mask, const Key& key, Row& row, bool& created) {
+__device__ __forceinline__ int64_t probe_find_as(const q2048_slot* table, const u64* side, u64 mask, const Key& key,
+                                                 Row& row, bool& created) {
   if constexpr (SUMMARY && sizeof(Key) == sizeof(u64)) return probe_find_summary(table, mask, key, row, created);
+  else if constexpr (SUMMARY) return probe_find_summary(table, side, mask, key, row, created);
   else return probe_find(table, mask, key, row, created);
 }
 
@@ -1110,7 +1169,8 @@ __global__ __launch_bounds__(kUpdateBlock) void k_q_update(q2048_slot* table, u6
 // kModeFrozen (a bit, with kModeLearn or kModeCas): Q2048_FLAG_NO_NEW_ROWS -- the key set is closed: no claim is ever
 // issued (the Claim pipeline, the insert of an episode's opening state and of a terminal state compile away), a
 // state without a row reads as zeros and its update is dropped and counted.
-constexpr int kModeLearn = 0, kModeCas = 1, kModeEval = 2, kModeFrozen = 4, kModeSummary = 8;   // (kModeSummary: with kModeFrozen, 4x4)
+constexpr int kModeLearn = 0, kModeCas = 1, kModeEval = 2, kModeFrozen = 4, kModeSummary = 8;   // (kModeSummary: with kModeFrozen;
+                                                        // 4x4: summaries in the slots, 5x5: in the side array `side`)
 // Lanes per workgroup of the fused rollout: 512 for batches that fill the chip more than twice over at that
 // size (>= 786 432 boards), 256 below.  Nine alternating pairs of the driver's command at 1 Mi boards: 47.2 us
 // per step against 48.3 (8 of 9 pairs; 5x5: 64.4 against 66.4; profiles/r04_block512_*.txt) -- half as many
@@ -1139,7 +1199,7 @@ __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
     uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mask, int64_t B, int steps, double eps,
     double lr, double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
     int64_t* stats_i, double* stats_f, uint32_t* status, q2048_episode* log, int64_t log_cap,
-    u64* log_count, void* row_cache, u64* mirror, uint32_t* ticket) {
+    u64* log_count, void* row_cache, u64* mirror, uint32_t* ticket, const u64* side) {
   RowCache<N>* const cache = static_cast<RowCache<N>*>(row_cache);
   __shared__ BlockStats bs;
   __shared__ Stage<N, BLOCK / 64> st;
@@ -1158,7 +1218,7 @@ __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
     constexpr bool play_only = (ENV & kEnvPlayOnly) != 0;
     constexpr bool no_learn = MODE == kModeEval;
     constexpr bool frozen = (MODE & kModeFrozen) != 0;
-    constexpr bool summary = (MODE & kModeSummary) != 0 && N == 4;   // line summaries: Q2048_FLAG_LINE_SUMMARY
+    constexpr bool summary = (MODE & kModeSummary) != 0;   // line summaries: Q2048_FLAG_LINE_SUMMARY
 #ifdef Q2048_EXPERIMENTS   // bits 8..11 write mode, 12 no row creation, 13 no next-state probe, 14 no deferral, 16..23 CAS attempts
     const uint32_t td_mode = no_learn ? (uint32_t)kTdNone : td_mode_of(flags);
     const bool x_noclaim = ((flags >> 12) & 1u) || play_only || no_learn || frozen, x_noprobe = ((flags >> 13) & 1u) || play_only;
@@ -1179,7 +1239,7 @@ __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
     // scattered 128-byte request per lane: 21.5 us of every launch at 1 Mi boards)
     int64_t slot_s = kNoSlot;
     if (!play_only && (cache == nullptr || !cache_get(cache, i, key_s, cache_tag(table, mask), q, slot_s, frozen)))
-      slot_s = probe_find_as<summary>(table, mask, key_s, q, made0);
+      slot_s = probe_find_as<summary>(table, side, mask, key_s, q, made0);
     Claim claim{0ull, 0ull, false};
     // wave-uniform counters (ballots) and rare per-lane ones
     uint32_t n_valid = 0, n_explore = 0, n_done = 0, n_insert = wave_count(made0), n_drop = 0;
@@ -1206,7 +1266,7 @@ __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
       int64_t slot_n = slot_s;
       if (!same) {
         if (x_noprobe) { qn = Row{0.f, 0.f, 0.f, 0.f}; slot_n = ~(int64_t)key_home(key_n, mask); }
-        else slot_n = probe_find_as<summary>(table, mask, key_n, qn, ins_n);
+        else slot_n = probe_find_as<summary>(table, side, mask, key_n, qn, ins_n);
       }
       const float max_next = max4(qn.q0, qn.q1, qn.q2, qn.q3);
       float nq = 0.f;
@@ -1247,7 +1307,7 @@ __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
         key_s = state_key(b, salt, status);
         bool made = false;
         q = Row{0.f, 0.f, 0.f, 0.f};
-        slot_s = play_only ? kNoSlot : probe_find_as<summary>(table, mask, key_s, q, made);
+        slot_s = play_only ? kNoSlot : probe_find_as<summary>(table, side, mask, key_s, q, made);
         ins_n = ins_n || made;
       } else if (same) {            // invalid move: same state, its row just changed (:100)
         if ((updated || frozen) && !no_learn) row_set(q, act, nq);   // (evaluation: the stored row stays as it is)
@@ -2118,21 +2178,16 @@ inline int check_table(const void* table, int cap_log2) {
       else Q2048_LAUNCH_FUSED_ONE(5, E, M, kFusedBlockSmall, B, stream, __VA_ARGS__);             \
     }                                                                                             \
     break;
-#define Q2048_LAUNCH_FUSED_CASE4(E, M, B, stream, ...)   /* 4x4 only (fused_mode never asks for it on 5x5) */ \
-  case (E) * 16 + (M):                                                                            \
-    if ((B) >= kFusedBigBatch) Q2048_LAUNCH_FUSED_ONE(4, E, M, kFusedBlockBig, B, stream, __VA_ARGS__);       \
-    else Q2048_LAUNCH_FUSED_ONE(4, E, M, kFusedBlockSmall, B, stream, __VA_ARGS__);               \
-    break;
 #define Q2048_LAUNCH_FUSED_ENV(E, n, B, stream, ...)                                              \
   Q2048_LAUNCH_FUSED_CASE(E, kModeLearn, n, B, stream, __VA_ARGS__)                               \
   Q2048_LAUNCH_FUSED_CASE(E, kModeCas, n, B, stream, __VA_ARGS__)                                 \
   Q2048_LAUNCH_FUSED_CASE(E, kModeEval, n, B, stream, __VA_ARGS__)                                \
   Q2048_LAUNCH_FUSED_CASE(E, kModeFrozen, n, B, stream, __VA_ARGS__)                              \
   Q2048_LAUNCH_FUSED_CASE(E, kModeFrozen + kModeCas, n, B, stream, __VA_ARGS__)                   \
-  Q2048_LAUNCH_FUSED_CASE4(E, kModeFrozen + kModeSummary, B, stream, __VA_ARGS__)                 \
-  Q2048_LAUNCH_FUSED_CASE4(E, kModeFrozen + kModeSummary + kModeCas, B, stream, __VA_ARGS__)
-#define Q2048_LAUNCH_FUSED(flags, n, B, stream, ...)                                              \
-  switch (env_bits(flags) * 16 + fused_mode(flags, n)) {                                          \
+  Q2048_LAUNCH_FUSED_CASE(E, kModeFrozen + kModeSummary, n, B, stream, __VA_ARGS__)               \
+  Q2048_LAUNCH_FUSED_CASE(E, kModeFrozen + kModeSummary + kModeCas, n, B, stream, __VA_ARGS__)
+#define Q2048_LAUNCH_FUSED(flags, n, side, B, stream, ...)                                        \
+  switch (env_bits(flags) * 16 + fused_mode(flags, n, side)) {                                        \
     Q2048_LAUNCH_FUSED_ENV(0, n, B, stream, __VA_ARGS__)                                          \
     Q2048_LAUNCH_FUSED_ENV(1, n, B, stream, __VA_ARGS__)                                          \
     Q2048_LAUNCH_FUSED_ENV(2, n, B, stream, __VA_ARGS__)                                          \
@@ -2146,17 +2201,19 @@ inline int env_bits(uint32_t flags) {
   return ((flags & Q2048_FLAG_ENV_DQN) ? kEnvDqn : 0) | ((flags & Q2048_FLAG_RESET_SHAPING) ? kEnvResetShaping : 0) |
          ((flags & Q2048_FLAG_PLAY_ONLY) ? kEnvPlayOnly : 0);
 }
-inline int fused_mode(uint32_t flags, int n) {   // play-only launches touch no table: one instantiation
+inline int fused_mode(uint32_t flags, int n, const void* side) {   // play-only launches touch no table: one instantiation
   if (flags & Q2048_FLAG_PLAY_ONLY) return kModeLearn;
   if (flags & Q2048_FLAG_NO_LEARN) return kModeEval;   // (evaluation creates nothing anyway)
   const bool frozen = (flags & Q2048_FLAG_NO_NEW_ROWS) != 0u;
   return ((flags & Q2048_FLAG_TD_CAS) ? kModeCas : kModeLearn) | (frozen ? kModeFrozen : 0) |
-         ((frozen && n == 4 && (flags & Q2048_FLAG_LINE_SUMMARY)) ? kModeSummary : 0);
+         ((frozen && (n == 4 || side != nullptr) && (flags & Q2048_FLAG_LINE_SUMMARY)) ? kModeSummary : 0);   // (5x5: only with a side array)
 }
 // flag bits outside the ABI are an argument error (experiment builds also take bits 8..23)
 constexpr uint32_t kAbiFlags = Q2048_FLAG_INDEPENDENT | Q2048_FLAG_SINGLE_ENV | Q2048_FLAG_TD_CAS |
                                Q2048_FLAG_ENV_DQN | Q2048_FLAG_RESET_SHAPING | Q2048_FLAG_PLAY_ONLY |
                                Q2048_FLAG_NO_LEARN | Q2048_FLAG_NO_NEW_ROWS | Q2048_FLAG_LINE_SUMMARY;
+constexpr size_t kOptsSizeNoSide = offsetof(q2048_rollout_opts, line_summary);   // the layout before `line_summary`
+static_assert(kOptsSizeNoSide == 56 && sizeof(q2048_rollout_opts) == 64, "ABI layout");
 inline int check_flags(uint32_t flags, uint32_t refused = 0u) {
   uint32_t allowed = kAbiFlags;
 #ifdef Q2048_EXPERIMENTS
@@ -2448,14 +2505,16 @@ int q2048_fused_rollout_opts(uint8_t* boards, q2048_aux* aux, q2048_slot* table,
                              const q2048_rollout_opts* opts, void* stream) {
   q2048_rollout_opts o = {};
   if (opts != nullptr) {
-    if (opts->size != sizeof(q2048_rollout_opts)) return Q2048_ERR_SIZE;   // a caller built against another header
-    o = *opts;
+    // the layout shipped so far (56 bytes: no side array) or this one; anything else was built against another header
+    if (opts->size != sizeof(q2048_rollout_opts) && opts->size != kOptsSizeNoSide) return Q2048_ERR_SIZE;
+    memcpy(&o, opts, opts->size);
   }
   if (int e = check_batch(B, n)) return e;
   if (int e = check_flags(flags)) return e;
   if (o.log != nullptr && (o.log_count == nullptr || o.log_capacity < 0)) return Q2048_ERR_NULL;
   if (o.log != nullptr && !aligned16(o.log)) return Q2048_ERR_ALIGN;
   if (o.row_cache != nullptr && !aligned16(o.row_cache)) return Q2048_ERR_ALIGN;
+  if (reinterpret_cast<uintptr_t>(o.line_summary) & 7u) return Q2048_ERR_ALIGN;
   // the mirror is a copy of both vectors, taken by the launch's last block: it needs both, and its ticket
   if (o.stats_mirror != nullptr && (o.mirror_ticket == nullptr || stats_i == nullptr || stats_f == nullptr))
     return Q2048_ERR_NULL;
@@ -2466,10 +2525,11 @@ int q2048_fused_rollout_opts(uint8_t* boards, q2048_aux* aux, q2048_slot* table,
   if (steps < 0 || steps > (1 << 30)) return Q2048_ERR_SIZE;
   if (!(eps >= 0.0 && eps <= 1.0) || !(lr == lr) || !(gamma == gamma)) return Q2048_ERR_RANGE;
   if (B == 0 || steps == 0) return Q2048_OK;
-  Q2048_LAUNCH_FUSED(flags, n, B, stream, boards, aux, table,
+  const u64* side = n == 5 ? reinterpret_cast<const u64*>(o.line_summary) : nullptr;   // (4x4: in the slots)
+  Q2048_LAUNCH_FUSED(flags, n, side, B, stream, boards, aux, table,
                      (u64)((1ull << cap_log2) - 1ull), B, (int)steps, eps, lr, gamma, seed, env_id0, ctr0,
                      flags, stats_i, stats_f, status, o.log, o.log_capacity, reinterpret_cast<u64*>(o.log_count),
-                     o.row_cache, reinterpret_cast<u64*>(o.stats_mirror), o.mirror_ticket);
+                     o.row_cache, reinterpret_cast<u64*>(o.stats_mirror), o.mirror_ticket, side);
   return launch_status();
 }
 
@@ -3350,6 +3410,23 @@ int q2048_table_summarise(q2048_slot* table, int cap_log2, void* stream) {
   const u64 blocks = (lines + kBlock - 1) / kBlock;
   hipLaunchKernelGGL(k_table_summarise, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0,
                      (hipStream_t)stream, table, lines);
+  return launch_status();
+}
+
+int q2048_table_summarise_side(const q2048_slot* table, int cap_log2, int key_words, uint64_t* summary, void* stream) {
+  if (table == nullptr || summary == nullptr) return Q2048_ERR_NULL;
+  if (key_words != 1 && key_words != 2) return Q2048_ERR_SIZE;
+  if (reinterpret_cast<uintptr_t>(summary) & 7u) return Q2048_ERR_ALIGN;
+  if (int e = check_table(table, cap_log2)) return e;
+  const u64 lines = (1ull << cap_log2) >> 2;
+  const u64 blocks = (lines + kBlock - 1) / kBlock;
+  const dim3 grid((unsigned)(blocks < 8192 ? blocks : 8192));
+  if (key_words == 1)
+    hipLaunchKernelGGL(k_table_summarise_side<1>, grid, dim3(kBlock), 0, (hipStream_t)stream, table, lines,
+                       reinterpret_cast<u64*>(summary));
+  else
+    hipLaunchKernelGGL(k_table_summarise_side<2>, grid, dim3(kBlock), 0, (hipStream_t)stream, table, lines,
+                       reinterpret_cast<u64*>(summary));
   return launch_status();
 }
 

@@ -57,7 +57,11 @@ extern "C" {
                                _commit / _finish / _abort)
                                6: Q2048_FLAG_NO_NEW_ROWS (a table that has stopped taking new rows)
                                7: Q2048_FLAG_LINE_SUMMARY + q2048_table_summarise, q2048_det_rollout_cached,
-                               q2048_rowcache_rebind */
+                               q2048_rowcache_rebind
+                               still 7, backward compatible additions: q2048_table_summarise_side and the trailing
+                               field q2048_rollout_opts.line_summary (line summaries of 5x5 tables in an array beside
+                               the table); q2048_fused_rollout_opts accepts both the 56-byte layout shipped before and
+                               the 64-byte one, so a caller built against the earlier header runs unchanged */
 
 /* return codes */
 #define Q2048_OK 0
@@ -149,9 +153,10 @@ extern "C" {
                                      The host decides when: BatchedQLearningAgent(freeze_load=0.5) sets it on every
                                      launch once a table at its largest capacity holds that share of rows */
 
-#define Q2048_FLAG_LINE_SUMMARY (1u << 24) /* with Q2048_FLAG_NO_NEW_ROWS, 4x4 tables: the table carries LINE SUMMARIES
-                                     (q2048_table_summarise ran after its last row was created) and the fused rollout
-                                     may decide a lookup from them.  A 4x4 slot has 8 spare bytes (`reserved`: the second
+#define Q2048_FLAG_LINE_SUMMARY (1u << 24) /* with Q2048_FLAG_NO_NEW_ROWS: the table carries LINE SUMMARIES -- 4x4: in its
+                                     slots (q2048_table_summarise ran after its last row was created); 5x5: in the array
+                                     q2048_rollout_opts.line_summary names (q2048_table_summarise_side ran after the last
+                                     row was created; below) -- and the fused rollout may decide a lookup from them.  A 4x4 slot has 8 spare bytes (`reserved`: the second
                                      key word of 5x5); a summary is four 16-bit fingerprints, one per slot of the
                                      128-byte line (0 = empty), the same word in all four slots.  The lookup reads the
                                      second half of the first slot of its sequence -- {q2, q3, summary}: ONE request --
@@ -164,9 +169,16 @@ extern "C" {
                                      ran.  Creating a row afterwards (any call without Q2048_FLAG_NO_NEW_ROWS, an import)
                                      makes them stale, and a stale summary HIDES rows: summarise again before the flag is
                                      passed again.  Ignored by every entry point but q2048_fused_rollout*, and there for
-                                     5x5 tables, evaluation and play-only launches (they probe slot by slot; the extra
-                                     word never disturbs them: 4x4 lookups, export with key_words 1, count, import and the
-                                     growth's move neither read nor write it).
+                                     5x5 tables WITHOUT a side array, evaluation and play-only launches (they probe slot
+                                     by slot; the extra word never disturbs them: 4x4 lookups, export with key_words 1,
+                                     count, import and the growth's move neither read nor write it).
+                                     5x5: a slot has no spare word (`reserved` is the second key word), so the summaries
+                                     live BESIDE the table: one 8-byte word per 128-byte line, 1/16 of the table's size
+                                     (2 GiB beside a 32 GiB table), same format.  With Q2048_FLAG_NO_NEW_ROWS, this flag
+                                     and a non-NULL q2048_rollout_opts.line_summary the fused rollout reads side[line] --
+                                     one request -- per line of the sequence; an absent state is settled by it alone, a
+                                     slot with the key's fingerprint costs its head and, on a first-word match, its second
+                                     half.  Without the pointer the flag is ignored on 5x5; on 4x4 the pointer is ignored.
                                      (bits 8..23 belong to the measurement build's experiment switches) */
 
 /* per-env state, Game2048_env.__init__ (Game2048_env.py:81-95) + episode bookkeeping */
@@ -399,7 +411,9 @@ int q2048_fused_rollout_log(uint8_t *boards, q2048_aux *aux, q2048_slot *table, 
  *               anyway (hipStreamSynchronize) reads its statistics from host memory with no copy queued
  *               behind the kernel.  mirror_ticket: device uint32[2], zero before its first use, private to
  *               one stream of launches (two launches that share it must not overlap).
- * `size` = sizeof(q2048_rollout_opts): a caller built against another layout is refused (Q2048_ERR_SIZE). */
+ *   line_summary   the line summaries of a 5x5 table with a closed key set (Q2048_FLAG_LINE_SUMMARY above).
+ * `size` = sizeof(q2048_rollout_opts) as the caller was built: 64, or the 56 bytes of the layout without
+ * `line_summary`; a caller built against any other layout is refused (Q2048_ERR_SIZE). */
 #define Q2048_MIRROR_SEQ 36 /* = Q2048_NSTAT_I + Q2048_NSTAT_F */
 #define Q2048_MIRROR_WORDS 37
 typedef struct q2048_rollout_opts {
@@ -411,6 +425,10 @@ typedef struct q2048_rollout_opts {
   void *row_cache;
   void *stats_mirror;
   uint32_t *mirror_ticket;
+  const uint64_t *line_summary; /* 5x5, Q2048_FLAG_NO_NEW_ROWS | Q2048_FLAG_LINE_SUMMARY: the side array
+                                   q2048_table_summarise_side wrote for THIS table and key set (2^(cap_log2-2) words,
+                                   8-byte aligned, else Q2048_ERR_ALIGN); NULL = none (slot-by-slot probe).  Trailing field,
+                                   added after the 56-byte layout: `size` = 56 is accepted and means NULL */
 } q2048_rollout_opts;
 int q2048_fused_rollout_opts(uint8_t *boards, q2048_aux *aux, q2048_slot *table, int cap_log2,
                              int64_t B, int n, int64_t steps, double eps, double lr, double gamma,
@@ -575,8 +593,23 @@ int q2048_table_probe(q2048_slot *table, int cap_log2, int64_t lanes, int steps,
 /* Writes the LINE SUMMARIES of a 4x4 table whose key set is closed (Q2048_FLAG_LINE_SUMMARY above): one streaming pass
  * over the table (reads every key, writes every slot's `reserved` word; 19.7 ms per 32 GiB), stream-ordered.  Run it
  * after the last row was created and before the first launch that carries the flag; run it again if rows were created
- * since.  Never on a 5x5 table (its `reserved` words are key words). */
+ * since.  MUST NOT be called on a 5x5 table: its `reserved` words are the second key words, and this pass overwrites
+ * them (every row of the table is lost, silently).  For 5x5 use q2048_table_summarise_side. */
 int q2048_table_summarise(q2048_slot *table, int cap_log2, void *stream);
+
+/* The LINE SUMMARIES of a table in caller-owned memory BESIDE it -- the form for 5x5 tables (key_words = 2), whose slots
+ * have no spare word: one streaming pass that reads the table and writes 2^(cap_log2-2) words to `summary`; the table is
+ * never written.  Word l describes line l (slots 4l .. 4l+3): bits 16r .. 16r+15 are 0 when slot 4l+r is empty
+ * (key == 0), else ((hash >> 48) & 0xffff) | 1 with `hash` the table's own hash of the slot's key (key_words 1:
+ * mix64(key); 2: mix64(key ^ reserved * 0x9E3779B97F4A7C15)) -- the format of the in-slot summaries, so with
+ * key_words = 1 the words equal what q2048_table_summarise puts into the slots.  Memory: 8 bytes per 128-byte line,
+ * 1/16 of the table (2 GiB beside 32 GiB, 8 GiB beside 2^32 slots).  Stream-ordered.
+ * Same contract as the in-slot summaries: the words describe the key set as it was when the pass ran.  Run it when no
+ * call that creates rows is in flight (queued behind the last one on the same stream), and again after anything that
+ * may have created rows, before q2048_rollout_opts.line_summary is passed with Q2048_FLAG_LINE_SUMMARY again.
+ * Errors: table or summary NULL -> Q2048_ERR_NULL; key_words not 1 or 2 -> Q2048_ERR_SIZE; summary not 8-byte aligned
+ * -> Q2048_ERR_ALIGN; then cap_log2 / the table's alignment as everywhere. */
+int q2048_table_summarise_side(const q2048_slot *table, int cap_log2, int key_words, uint64_t *summary, void *stream);
 
 /* len(agent.q_table): adds the number of occupied slots to *count (device int64). */
 int q2048_table_count(const q2048_slot *table, int cap_log2, int64_t *count, void *stream);
