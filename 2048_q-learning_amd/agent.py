@@ -1116,6 +1116,63 @@ class BatchedQLearningAgent:
         N.check(self._L.q2048_table_import(_ptr(self.table), self.capacity_log2, _ptr(keys), _ptr(q), rows, words,
                                            _ptr(self.status), _stream(self.device)), "table_import")
 
+    _MERGE_MODES = {"add": N.MERGE_ADD, "blend": N.MERGE_BLEND, "maxabs": N.MERGE_MAXABS}
+
+    def merge_from(self, other: "BatchedQLearningAgent", mode: str = "add", weight: float = 1.0) -> dict:
+        """Combines `other`'s table into this one on the device (q2048_table_merge): every row of `other` finds or
+        creates its row here -- the replicas of a job, or two checkpoints, become one table without a trip through
+        the host.  `other` is only read.
+          "add"     q = q + weight * q_other; a state without a row is the defaultdict's zero row (Agent/main.py:16).
+                    weight 1: the sum; K merges with weight 1/K into an empty agent: the mean over K replicas.
+          "blend"   a state both have: q = (1 - weight) * q + weight * q_other; a state only `other` has: its row as
+                    it is.  weight in [0, 1]: 0 keeps this agent's rows and adds the missing ones, 1 takes `other`'s.
+          "maxabs"  per action the value of larger magnitude (an untrained entry is exactly 0).
+        float32 with every product and sum rounded on its own: a float32 numpy model gives the same bits.
+        Sizing follows `import_rows`: a table that can grow grows first until both tables' rows fit half of it; one
+        that cannot raises ValueError when they would pass load 0.9 (nothing is launched then).  A destination whose
+        key set is closed (`frozen`) is refused: its visit rows and line summaries describe a key set the merge would
+        change.  The row bookkeeping stays exact without a counting pass (rows before + rows created).
+        Returns the call's counters: {"read", "created", "combined", "dropped"}; read == other's rows."""
+        if not isinstance(other, BatchedQLearningAgent) or other is self:
+            raise ValueError("merge_from takes another BatchedQLearningAgent")
+        if other.device != self.device:
+            raise ValueError("the two agents live on different devices")
+        if other.board_size != self.board_size:
+            raise ValueError("the two agents have different board sizes")
+        if mode not in self._MERGE_MODES:
+            raise ValueError(f"mode must be one of {sorted(self._MERGE_MODES)}")
+        weight = float(weight)
+        if not np.isfinite(weight) or (mode == "blend" and not 0.0 <= weight <= 1.0):
+            raise ValueError("weight must be finite, and in [0, 1] for mode 'blend'")
+        if self.frozen:
+            raise ValueError("this agent's key set is closed (frozen): a merge would create rows its visit rows and "
+                             "line summaries do not know")
+        self.finish_growth()
+        other.finish_growth()
+        rows, rows_other = self._rows_exact(), other._rows_exact()
+        total = rows + rows_other                         # (an upper bound of the rows afterwards: keys may be shared)
+        while self.growable and total * 2 > (1 << self.capacity_log2) and self.capacity_log2 < self.max_capacity_log2:
+            self.grow_table(min(self.max_capacity_log2, max(self.capacity_log2 + 1, int(np.ceil(np.log2(2.0 * total))))),
+                            _rows=rows)
+        if total > 0.9 * (1 << self.capacity_log2):
+            raise ValueError("table too small for the merge (load factor could exceed 0.9)")
+        self.invalidate_row_cache()
+        self._summarised, self._side = False, None        # (rows arrive: line summaries stop describing the table)
+        counters = torch.zeros(4, dtype=torch.int64, device=self.device)
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)    # this call's own word (the agent's is sticky)
+        N.check(self._L.q2048_table_merge(_ptr(self.table), self.capacity_log2, _ptr(other.table), other.capacity_log2,
+                                          1 if self.board_size == 4 else 2, self._MERGE_MODES[mode], weight,
+                                          _ptr(counters), _ptr(status), _stream(self.device)), "table_merge")
+        read, created, combined, dropped = (int(v) for v in counters.tolist())
+        code = int(status.item())
+        self._rebase_rows(rows + created)
+        if code & N.STATUS_TABLE_FULL:
+            raise RuntimeError(f"table_merge dropped {dropped} rows (probe limit)")
+        if code & N.STATUS_DEEP_ROW:
+            warnings.warn("table_merge placed rows deeper than the learning paths probe (2^10 slots): q_values finds "
+                          "them, choose / update / rollouts read them as absent -- merge into a larger table")
+        return {"read": read, "created": created, "combined": combined, "dropped": dropped}
+
     def recount_rows(self) -> int:
         """Counts the occupied slots (one streaming pass, synchronising) and makes that the base of the row
         bookkeeping: after anything but this class's own methods has written rows."""

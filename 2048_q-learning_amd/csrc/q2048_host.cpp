@@ -22,6 +22,7 @@
 //   g++ -O3 -std=c++17 -fPIC -shared -pthread -I include -I 2048_q-learning_amd/csrc \
 //       -o 2048_q-learning_amd/csrc/libq2048_host.so 2048_q-learning_amd/csrc/q2048_host.cpp
 #include <algorithm>
+#include <chrono>
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
@@ -109,6 +110,14 @@ inline u64 await_second(const q2048_slot* s) {   // the owner of the first key w
     const u64 hi = ld_u64(&s->reserved);
     if (hi != 0ull) return hi;
     if ((spin & 1023) == 1023) std::this_thread::yield();
+  }
+  // the owner is a host thread: on a machine with more runnable threads than CPUs it can lose its time slice between
+  // its compare-and-swap and its store, for milliseconds.  A count of spins says nothing about that; wait on the clock
+  // (still bounded: a protocol error ends here after two seconds, counted)
+  for (const auto give_up = std::chrono::steady_clock::now() + std::chrono::seconds(2); std::chrono::steady_clock::now() < give_up;) {
+    std::this_thread::sleep_for(std::chrono::microseconds(50));
+    const u64 hi = ld_u64(&s->reserved);
+    if (hi != 0ull) return hi;
   }
   __atomic_fetch_add(&g_claim_timeouts, 1ull, __ATOMIC_RELAXED);
   return 0ull;
@@ -1107,6 +1116,75 @@ int q2048_table_import(q2048_slot* table, int cap_log2, const uint64_t* keys, co
       for (int a = 0; a < 4; ++a) st_f32(&table[slot].q[a], q[4 * i + a]);
     }
   });
+  return Q2048_OK;
+}
+
+// the device's merge (k_table_merge), value for value: float32, the product rounded before the sum sees it (the
+// volatile keeps a compiler that contracts by default from fusing the two), slots of `src` split over the threads
+namespace {
+inline float mul_rn(float a, float b) { volatile float p = a * b; return p; }
+inline float merge_value(int mode, float d, float s, float w, float one_minus_w) {
+  if (mode == Q2048_MERGE_ADD) return d + mul_rn(w, s);
+  if (mode == Q2048_MERGE_BLEND) { const float keep = mul_rn(one_minus_w, d); return keep + mul_rn(w, s); }
+  return std::fabs(s) > std::fabs(d) ? s : d;
+}
+}  // namespace
+int q2048_table_merge(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, int src_cap_log2, int key_words,
+                      int mode, float w, uint64_t* counters, uint32_t* status, void*) {
+  if (!dst || !src || !counters) return Q2048_ERR_NULL;
+  if (dst_cap_log2 < 4 || dst_cap_log2 > 40 || src_cap_log2 < 4 || src_cap_log2 > 40) return Q2048_ERR_SIZE;
+  if (key_words != 1 && key_words != 2) return Q2048_ERR_SIZE;
+  if (!aligned16(dst) || !aligned16(src)) return Q2048_ERR_ALIGN;
+  if (mode != Q2048_MERGE_ADD && mode != Q2048_MERGE_BLEND && mode != Q2048_MERGE_MAXABS) return Q2048_ERR_FLAGS;
+  if (!std::isfinite(w) || (mode == Q2048_MERGE_BLEND && !(w >= 0.0f && w <= 1.0f))) return Q2048_ERR_RANGE;
+  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), s0 = reinterpret_cast<uintptr_t>(src);
+  const uintptr_t d1 = d0 + (sizeof(q2048_slot) << dst_cap_log2), s1 = s0 + (sizeof(q2048_slot) << src_cap_log2);
+  if (s0 < d1 && d0 < s1) return Q2048_ERR_RANGE;
+  const int64_t cap = (int64_t)1 << src_cap_log2;
+  const u64 mask = (1ull << dst_cap_log2) - 1ull;
+  const float one_minus_w = 1.0f - w;
+  struct Part { uint64_t created = 0, combined = 0, dropped = 0; uint32_t bits = 0; };
+  std::vector<Part> parts((size_t)threads_for(cap));
+  Part* part = parts.data();
+  const int used = parallel_ranges(cap, [=](int64_t lo, int64_t hi, int t) {
+    Part p;
+    for (int64_t i = lo; i < hi; ++i) {
+      const q2048_slot& s = src[i];
+      if (s.key == 0ull) continue;
+      bool inserted;
+      int64_t slot;
+      u64 hash;
+      if (key_words == 1) {
+        const Geo<4>::Key key{(u64)s.key};
+        hash = key_hash(key);
+        slot = probe_insert(dst, mask, key, hash & mask, inserted, kMaxProbe);
+      } else {
+        const Geo<5>::Key key{(u64)s.key, (u64)s.reserved};
+        hash = key_hash(key);
+        slot = probe_insert(dst, mask, key, hash & mask, inserted, kMaxProbe);
+      }
+      if (slot < 0) { ++p.dropped; p.bits |= Q2048_STATUS_TABLE_FULL; continue; }
+      if (inserted) {
+        ++p.created;
+        if (seq_pos(seq_of(hash, mask), (u64)slot) >= probe_limit(mask, kRolloutProbe)) p.bits |= Q2048_STATUS_DEEP_ROW;
+        for (int a = 0; a < 4; ++a) st_f32(&dst[slot].q[a], mode == Q2048_MERGE_ADD ? mul_rn(w, s.q[a]) : s.q[a]);
+      } else {
+        ++p.combined;
+        for (int a = 0; a < 4; ++a) st_f32(&dst[slot].q[a], merge_value(mode, ld_f32(&dst[slot].q[a]), s.q[a], w, one_minus_w));
+      }
+    }
+    part[t] = p;
+  });
+  uint32_t bits = 0u;
+  for (int t = 0; t < used; ++t) {
+    const Part& p = parts[(size_t)t];
+    counters[0] += p.created + p.combined + p.dropped;
+    counters[1] += p.created;
+    counters[2] += p.combined;
+    counters[3] += p.dropped;
+    bits |= p.bits;
+  }
+  if (bits && status != nullptr) status_or(status, bits);
   return Q2048_OK;
 }
 

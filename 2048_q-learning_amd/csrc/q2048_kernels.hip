@@ -2102,6 +2102,91 @@ __global__ __launch_bounds__(kBlock) void k_table_rehash(const q2048_slot* old_t
   }
 }
 
+// Merge (q2048_table_merge): the growth's move with a destination that may already hold the key.  Every occupied row
+// of `src` finds or creates its row in `dst` -- the same streaming read, the same claiming compare-and-swap at the
+// key's home -- and a created row takes the source's values (ADD: w * q_src, the defaultdict's zero row + w * q_src),
+// a row that was there is read (two 8-byte loads), combined and written back (two 8-byte stores).  Keys of one table
+// are distinct, so no two lanes ever meet on a dst row: the only races are the slot claims `probe_insert` / `confirm`
+// resolve.  float32, product and sum rounded separately (no contraction: Q2048_NO_CONTRACT, checked in the ISA -- v_pk_mul_f32 + v_pk_add_f32, no fma): a numpy model
+// in float32 gives the same bits.  counters[0..3] += rows read / created / combined / dropped, ONE atomic per counter
+// and block (k_table_export above says why); the status bits likewise.
+template <int MODE>
+__device__ __forceinline__ float merge_value(float d, float s, float w, float one_minus_w) {
+  // plain * and + under the pragma: it binds the operators written HERE (the header's __fmul_rn / __fadd_rn are
+  // functions of their own, compiled with contraction allowed, and came out as v_pk_fma_f32 once inlined)
+  Q2048_NO_CONTRACT
+  if constexpr (MODE == Q2048_MERGE_ADD) {
+    const float ws = w * s;
+    return d + ws;
+  } else if constexpr (MODE == Q2048_MERGE_BLEND) {
+    const float keep = one_minus_w * d, take = w * s;
+    return keep + take;
+  } else {
+    return fabsf(s) > fabsf(d) ? s : d;
+  }
+}
+template <int WORDS, int MODE>
+__global__ __launch_bounds__(kBlock) void k_table_merge(const q2048_slot* src, u64 src_cap, q2048_slot* dst, u64 dst_mask,
+                                                        float w, float one_minus_w, u64* counters, uint32_t* status) {
+  const u32x4* t16 = reinterpret_cast<const u32x4*>(src);
+  u64 created = 0ull, combined = 0ull, dropped = 0ull;
+  uint32_t bits = 0u;
+  for (u64 i = (u64)blockIdx.x * kBlock + threadIdx.x; i < src_cap; i += (u64)gridDim.x * kBlock) {
+    const u32x4 a = __builtin_nontemporal_load(&t16[2ull * i]);          // {key, q0, q1}
+    const u64 k = (u64)a.x | ((u64)a.y << 32);
+    if (k == 0ull) continue;
+    const u32x4 b = __builtin_nontemporal_load(&t16[2ull * i + 1ull]);   // {q2, q3, second key word}
+    typename Geo<WORDS == 1 ? 4 : 5>::Key key;
+    key.k0 = k;
+    if constexpr (WORDS == 2) key.k1 = (u64)b.z | ((u64)b.w << 32);
+    bool inserted;
+    const int64_t slot = probe_insert(dst, dst_mask, key, key_home(key, dst_mask), inserted, kMaxProbe);
+    if (slot < 0) { ++dropped; bits |= Q2048_STATUS_TABLE_FULL; continue; }
+    const float s0 = bits_f32(a.z), s1 = bits_f32(a.w), s2 = bits_f32(b.x), s3 = bits_f32(b.y);
+    float r0, r1, r2, r3;
+    if (inserted) {
+      ++created;
+      // beyond the learning paths' probe limit: as q2048_table_import tells its caller
+      if (seq_pos(seq_of(key_hash(key), dst_mask), (u64)slot) >= probe_limit(dst_mask, kRolloutProbe)) bits |= Q2048_STATUS_DEEP_ROW;
+      if constexpr (MODE == Q2048_MERGE_ADD) { r0 = __fmul_rn(w, s0); r1 = __fmul_rn(w, s1); r2 = __fmul_rn(w, s2); r3 = __fmul_rn(w, s3); }
+      else { r0 = s0; r1 = s1; r2 = s2; r3 = s3; }
+    } else {
+      ++combined;
+      const u64 lo = ld_u64(&dst[slot].q[0]), hi = ld_u64(&dst[slot].q[2]);
+      r0 = merge_value<MODE>(bits_f32((uint32_t)lo), s0, w, one_minus_w);
+      r1 = merge_value<MODE>(bits_f32((uint32_t)(lo >> 32)), s1, w, one_minus_w);
+      r2 = merge_value<MODE>(bits_f32((uint32_t)hi), s2, w, one_minus_w);
+      r3 = merge_value<MODE>(bits_f32((uint32_t)(hi >> 32)), s3, w, one_minus_w);
+    }
+    uint2* q = reinterpret_cast<uint2*>(dst[slot].q);                    // 8-byte aligned (offset 8 of a 32-B slot)
+    q[0] = make_uint2(f32_bits(r0), f32_bits(r1));
+    q[1] = make_uint2(f32_bits(r2), f32_bits(r3));
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    created += __shfl_xor(created, d); combined += __shfl_xor(combined, d); dropped += __shfl_xor(dropped, d);
+    bits |= __shfl_xor(bits, d);
+  }
+  __shared__ u64 wc[3][kBlock / 64];
+  __shared__ uint32_t wb[kBlock / 64];
+  if ((threadIdx.x & 63u) == 0u) {
+    const uint32_t wv = threadIdx.x >> 6;
+    wc[0][wv] = created; wc[1][wv] = combined; wc[2][wv] = dropped; wb[wv] = bits;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 c = 0ull, m = 0ull, f = 0ull;
+    uint32_t sb = 0u;
+#pragma unroll
+    for (int v = 0; v < kBlock / 64; ++v) { c += wc[0][v]; m += wc[1][v]; f += wc[2][v]; sb |= wb[v]; }
+    if (c + m + f) atomicAdd(&counters[0], c + m + f);
+    if (c) atomicAdd(&counters[1], c);
+    if (m) atomicAdd(&counters[2], m);
+    if (f) atomicAdd(&counters[3], f);
+    if (sb && status != nullptr) atomicOr(status, sb);
+  }
+}
+
 // Placement probe: `steps` scattered device-scope atomic ORs of 0 per lane into key words chosen
 // like the rollout chooses rows -- the table's write-side request pattern with no effect on its
 // contents (x | 0 == x).  The host times it: where in device memory a table lies moves the
@@ -2736,6 +2821,38 @@ int q2048_table_import(q2048_slot* table, int cap_log2, const uint64_t* keys, co
   else
     hipLaunchKernelGGL(k_table_import<2>, dim3(grid_for(rows)), dim3(kBlock), 0, (hipStream_t)stream,
                        table, mask, reinterpret_cast<const u64*>(keys), q, rows, status);
+  return launch_status();
+}
+
+#define Q2048_LAUNCH_MERGE(WORDS)                                                                                     \
+  do {                                                                                                                \
+    if (mode == Q2048_MERGE_ADD)                                                                                      \
+      hipLaunchKernelGGL((k_table_merge<WORDS, Q2048_MERGE_ADD>), grid, dim3(kBlock), 0, (hipStream_t)stream, src,    \
+                         cap, dst, mask, w, one_minus_w, reinterpret_cast<u64*>(counters), status);                   \
+    else if (mode == Q2048_MERGE_BLEND)                                                                               \
+      hipLaunchKernelGGL((k_table_merge<WORDS, Q2048_MERGE_BLEND>), grid, dim3(kBlock), 0, (hipStream_t)stream, src,  \
+                         cap, dst, mask, w, one_minus_w, reinterpret_cast<u64*>(counters), status);                   \
+    else                                                                                                              \
+      hipLaunchKernelGGL((k_table_merge<WORDS, Q2048_MERGE_MAXABS>), grid, dim3(kBlock), 0, (hipStream_t)stream, src, \
+                         cap, dst, mask, w, one_minus_w, reinterpret_cast<u64*>(counters), status);                   \
+  } while (0)
+int q2048_table_merge(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, int src_cap_log2, int key_words,
+                      int mode, float w, uint64_t* counters, uint32_t* status, void* stream) {
+  if (!dst || !src || !counters) return Q2048_ERR_NULL;
+  if (dst_cap_log2 < 4 || dst_cap_log2 > 40 || src_cap_log2 < 4 || src_cap_log2 > 40) return Q2048_ERR_SIZE;
+  if (key_words != 1 && key_words != 2) return Q2048_ERR_SIZE;
+  if (!aligned16(dst) || !aligned16(src)) return Q2048_ERR_ALIGN;
+  if (mode != Q2048_MERGE_ADD && mode != Q2048_MERGE_BLEND && mode != Q2048_MERGE_MAXABS) return Q2048_ERR_FLAGS;
+  if (!std::isfinite(w) || (mode == Q2048_MERGE_BLEND && !(w >= 0.0f && w <= 1.0f))) return Q2048_ERR_RANGE;
+  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), s0 = reinterpret_cast<uintptr_t>(src);
+  const uintptr_t d1 = d0 + (sizeof(q2048_slot) << dst_cap_log2), s1 = s0 + (sizeof(q2048_slot) << src_cap_log2);
+  if (s0 < d1 && d0 < s1) return Q2048_ERR_RANGE;                      // the two tables overlap (src == dst included)
+  const u64 cap = 1ull << src_cap_log2, mask = (1ull << dst_cap_log2) - 1ull;
+  const u64 want = (cap + kBlock - 1) / kBlock;
+  const dim3 grid((unsigned)(want < 2048 ? want : 2048));              // the growth's move: 8 blocks of 4 waves per CU
+  const float one_minus_w = 1.0f - w;
+  if (key_words == 1) Q2048_LAUNCH_MERGE(1);
+  else Q2048_LAUNCH_MERGE(2);
   return launch_status();
 }
 

@@ -61,7 +61,9 @@ extern "C" {
                                still 7, backward compatible additions: q2048_table_summarise_side and the trailing
                                field q2048_rollout_opts.line_summary (line summaries of 5x5 tables in an array beside
                                the table); q2048_fused_rollout_opts accepts both the 56-byte layout shipped before and
-                               the 64-byte one, so a caller built against the earlier header runs unchanged */
+                               the 64-byte one, so a caller built against the earlier header runs unchanged;
+                               q2048_table_merge (combine two tables on the device) arrived without a bump as well: a
+                               caller detects it by its symbol */
 
 /* return codes */
 #define Q2048_OK 0
@@ -658,6 +660,41 @@ int q2048_rt_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weights, int6
  * overwritten; a row that finds no slot within the probe limit sets Q2048_STATUS_TABLE_FULL. */
 int q2048_table_import(q2048_slot *table, int cap_log2, const uint64_t *keys, const float *q,
                        int64_t rows, int key_words, uint32_t *status, void *stream);
+
+/* Combines two tables on the device: every occupied row of `src` finds or creates its row in `dst` and is combined with
+ * it -- the replicas of a job (one table per rank, dist.py) or two checkpoints become the one table they trained,
+ * without a trip through the host.  No reference counterpart (its q_table is one dict in one process); the reading of
+ * a state WITHOUT a row is the defaultdict's (Agent/main.py:16): the zero row.  One streaming pass over `src` (the
+ * growth's move: 16-byte head of every slot, second half of the occupied ones, find-or-create at the key's home in
+ * `dst`); a row that was already in `dst` costs one more read of its values.  key_words as q2048_table_export.
+ *   mode, w   Q2048_MERGE_ADD     q_dst = q_dst + w * q_src; a created row holds w * q_src.  w = 1: the sum; K calls
+ *                                 with w = 1/K into an empty table: the mean over K replicas.  Any finite w.
+ *             Q2048_MERGE_BLEND   key in both: q_dst = (1 - w) * q_dst + w * q_src; key only in src: q_src as it is.
+ *                                 w in [0, 1]; 0 keeps the rows dst has and adds the ones it lacks, 1 takes src's.
+ *             Q2048_MERGE_MAXABS  per action the value of larger magnitude (q_src if |q_src| > |q_dst|, else q_dst:
+ *                                 an untrained entry is exactly 0); a created row holds q_src; w is not used.
+ *             Arithmetic: float32, every product and every sum rounded on its own (no fused multiply-add), 1 - w
+ *             computed once on the host in float32 -- a float32 model on the host gives the same bits.  (0 * x and
+ *             x + 0 are x's own bits for every finite x but -0.0, which comes out as +0.0.)
+ *   counters  device uint64[4], ADDED to: [0] occupied src rows read, [1] rows created in dst, [2] rows combined with
+ *             an existing dst row, [3] rows dropped (no slot within the probe limit); [0] = [1] + [2] + [3].
+ *   status    may be NULL.  Q2048_STATUS_TABLE_FULL when a row was dropped, Q2048_STATUS_DEEP_ROW when a created row
+ *             lies beyond the learning paths' probe limit (as q2048_table_import).
+ * Stream-ordered.  Nothing else may write `src` or touch `dst` while the call is in flight; `src` is never written.
+ * The call creates rows in `dst`: its line summaries, in the slots or beside the table, are stale afterwards and must be
+ * written again before Q2048_FLAG_LINE_SUMMARY is passed again.  The `reserved` words of 4x4 slots (key_words = 1) are
+ * neither read nor written: a summary word in `src` is ignored, the word of a created row stays what it was (0 in a
+ * table without summaries).  Keys salted by Q2048_FLAG_INDEPENDENT merge key by key like any others, which is rarely
+ * meaningful: the same env id has to mean the same learner in both tables.
+ * Errors, in this order: dst, src or counters NULL -> Q2048_ERR_NULL; a cap_log2 outside 4..40 or key_words not 1 or 2
+ * -> Q2048_ERR_SIZE; a table not 16-byte aligned -> Q2048_ERR_ALIGN; an unknown mode -> Q2048_ERR_FLAGS; w not finite,
+ * or outside [0, 1] with Q2048_MERGE_BLEND -> Q2048_ERR_RANGE; the two tables' byte ranges overlap (src == dst
+ * included) -> Q2048_ERR_RANGE. */
+#define Q2048_MERGE_ADD 0
+#define Q2048_MERGE_BLEND 1
+#define Q2048_MERGE_MAXABS 2
+int q2048_table_merge(q2048_slot *dst, int dst_cap_log2, const q2048_slot *src, int src_cap_log2,
+                      int key_words, int mode, float w, uint64_t *counters, uint32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

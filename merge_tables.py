@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""merge_tables.py -- combine the Q-tables of several saved learners into one, on the device.
+
+A multi-GPU job trains one Q-table replica per rank and reduces only the statistics, so
+`train.py --save q.pt` in a job writes q.pt.rank0 ... q.pt.rankR.  This script turns them -- or any files written by
+`train.py --save`: two seeds, a run resumed on another table -- into the one file `evaluate.py --model` and
+`train.py --resume` load.  Every input is loaded into a scratch table and merged into the destination by one streaming
+kernel (q2048_table_merge, `BatchedQLearningAgent.merge_from`): at most two tables are resident at a time and no row
+travels through a Python dict.
+
+  --mode mean (default)   the average over the K inputs, a state an input never saw counting as the zero row the
+                          reference's defaultdict would hold for it (Agent/main.py:16): q = sum_k q_k / K
+         sum              q = sum_k q_k
+         maxabs           per action the value of largest magnitude (an untrained entry is exactly 0)
+         first / last     where inputs share a state, the first / the last input's row wins; other rows are copied
+
+    python train.py --gpus 8 --num-envs 8388608 --episodes 40 --save models/q.pt
+    python merge_tables.py --out models/q_merged.pt models/q.pt.rank*
+    python evaluate.py --model models/q_merged.pt
+
+Hyper-parameters, epsilon schedule, seed and training progress come from the first input; the statistics vectors are
+summed and the draw counter is the largest of the inputs'.  Prints one JSON line.
+"""
+from __future__ import annotations
+
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.abspath(__file__))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+FLAG_INDEPENDENT = 1
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("inputs", nargs="+", help="files written by train.py --save (q.pt.rank0 q.pt.rank1 ...)")
+    p.add_argument("--out", required=True, help="the merged learner (loads like any file of train.py --save)")
+    p.add_argument("--mode", choices=["mean", "sum", "maxabs", "first", "last"], default="mean")
+    p.add_argument("--device", default="cuda", help='"cuda[:i]", or "cpu" for the host twin of the kernels')
+    return p.parse_args(argv)
+
+
+def _capacity_for(rows: int) -> int:
+    """The smallest table that holds `rows` rows at load <= 0.5 (at least 2^16 slots): evaluate.py's own sizing."""
+    return max(16, (2 * max(rows, 1) - 1).bit_length())
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    import torch
+
+    pkg = importlib.import_module("2048_q-learning_amd")
+    t0 = time.time()
+    K = len(args.inputs)
+    # pass 1, headers only: one board size, shared tables, and an upper bound of the rows the result can hold
+    first, rows_in, stats_i, stats_f, ctr = None, [], None, None, 0
+    for path in args.inputs:
+        sd = torch.load(path, map_location="cpu", weights_only=False)
+        if first is None:
+            first = {k: v for k, v in sd.items() if k not in ("keys", "q", "table", "env", "visit_rows")}
+        if int(sd["board_size"]) != int(first["board_size"]):
+            raise SystemExit(f"{path}: board size {sd['board_size']}, {args.inputs[0]} has {first['board_size']}")
+        if int(sd["flags"]) & FLAG_INDEPENDENT:
+            raise SystemExit(f"{path} was trained with private rows per env (Q2048_FLAG_INDEPENDENT): its keys are "
+                             "salted by env id and mean nothing in another learner's table")
+        rows_in.append(len(sd["q"]) if "q" in sd else int((sd["table"].view(torch.int64).reshape(-1, 4)[:, 0] != 0).sum()))
+        stats_i = sd["stats_i"].clone() if stats_i is None else stats_i + sd["stats_i"]
+        stats_f = sd["stats_f"].clone() if stats_f is None else stats_f + sd["stats_f"]
+        ctr = max(ctr, int(sd["ctr"]))
+        del sd
+    n = int(first["board_size"])
+
+    def agent_of(capacity_log2):
+        return pkg.BatchedQLearningAgent(1, learning_rate=first["lr"], discount_factor=first["gamma"],
+                                         capacity_log2=capacity_log2, device=args.device, board_size=n,
+                                         placement="plain", freeze_load=None, row_cache=False)
+
+    dst = agent_of(_capacity_for(sum(rows_in)))
+    mode, weight = {"mean": ("add", 1.0 / K), "sum": ("add", 1.0), "maxabs": ("maxabs", 1.0),
+                    "first": ("blend", 0.0), "last": ("blend", 1.0)}[args.mode]
+    merges = []
+    for path, rows in zip(args.inputs, rows_in):
+        sd = torch.load(path, map_location="cpu", weights_only=False)
+        sd.pop("visit_rows", None)                    # (the envs' visit rows belong to the run, not to the table)
+        scratch = agent_of(int(sd["capacity_log2"]) if "table" in sd else _capacity_for(rows))
+        scratch.load_state_dict(sd)
+        del sd
+        merges.append(dst.merge_from(scratch, mode=mode, weight=weight))
+        if dst.on_gpu:
+            torch.cuda.synchronize(dst.device)
+        del scratch                                   # at most two tables at a time
+    check = dst.verify_table()
+    out = dst.state_dict(compact=True)
+    out.update(first)                                 # hyper-parameters, schedule, seed, progress: the first input's
+    out.update({"capacity_log2": dst.capacity_log2, "stats_i": stats_i, "stats_f": stats_f, "ctr": ctr,
+                "merged": {"inputs": [os.path.basename(p) for p in args.inputs], "mode": args.mode}})
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    torch.save(out, args.out, pickle_protocol=4)      # (protocol 4: rows of a long run pass 4 GiB, as train.py --save)
+    print(json.dumps({"out": args.out, "mode": args.mode, "device": args.device, "board_size": n, "inputs": args.inputs,
+                      "rows_in": rows_in, "merges": merges, "rows_out": check["rows"],
+                      "capacity_log2": dst.capacity_log2, "seconds": round(time.time() - t0, 3)}))
+    return out
+
+
+if __name__ == "__main__":
+    main()
