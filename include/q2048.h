@@ -617,9 +617,17 @@ int q2048_table_summarise_side(const q2048_slot *table, int cap_log2, int key_wo
 int q2048_table_count(const q2048_slot *table, int cap_log2, int64_t *count, void *stream);
 
 /* Export occupied rows (for conversion to the reference's dict{state -> 4 floats},
- * Agent/main.py:16): writes up to max_rows (key, q[4]) pairs in unspecified order and adds the
- * number of occupied slots to *count (rows beyond max_rows are counted, not written).
- * key_words = 1 (4x4: keys_out[max_rows]) or 2 (5x5: keys_out[max_rows][2] = key, reserved). */
+ * Agent/main.py:16): writes (key, q[4]) pairs in unspecified order and adds the number of occupied
+ * slots to *count.
+ * *count IS THE WRITE CURSOR of the export, as log_count is for the episode log: the records of this call
+ * go to indices [count0, count0 + occupied) of keys_out / q_out, count0 being the value of *count when the
+ * call starts, and max_rows is the capacity of the buffers -- an index bound, not a number of rows of this
+ * call: a record whose index is >= max_rows is counted, not written (which rows those are is unspecified).
+ * A caller that wants the rows from index 0 zeroes *count first; tables exported one after the other into
+ * the same buffers with the same cursor end up side by side.  Nothing outside [count0, max_rows) is touched.
+ * key_words = 1 (4x4: keys_out[max_rows]; the `reserved` words -- 0 or line summaries -- are not exported)
+ * or 2 (5x5: keys_out[max_rows][2] = key, reserved).  keys_out and q_out are both NULL (count only) or
+ * both given; q_out 16-byte aligned.  The table is only read. */
 int q2048_table_export(const q2048_slot *table, int cap_log2, uint64_t *keys_out, float *q_out,
                        int64_t max_rows, int key_words, int64_t *count, void *stream);
 
@@ -657,7 +665,14 @@ int q2048_rt_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weights, int6
 
 /* Inverse of q2048_table_export (resume / load a table trained elsewhere): inserts `rows`
  * (key, q[4]) pairs into the table, key_words as above.  A key already present has its row
- * overwritten; a row that finds no slot within the probe limit sets Q2048_STATUS_TABLE_FULL. */
+ * overwritten in place (its slot and key words stay, the four values change); a row that finds no slot
+ * within the probe limit (2^14 positions of its sequence, or the whole table) sets Q2048_STATUS_TABLE_FULL
+ * and is left out, the others are placed.
+ * THE SAME KEY MORE THAN ONCE IN ONE CALL leaves exactly one row.  The rows of a call are inserted
+ * concurrently and a row's four values are written one by one, so each of the four values of that row is
+ * the corresponding value of ONE of the duplicates -- not necessarily all four of the same one, and not
+ * necessarily the last in the input.  A caller that needs a particular duplicate to win removes the others
+ * first (or imports them in separate calls on one stream: the later call overwrites). */
 int q2048_table_import(q2048_slot *table, int cap_log2, const uint64_t *keys, const float *q,
                        int64_t rows, int key_words, uint32_t *status, void *stream);
 
