@@ -45,27 +45,69 @@ struct Draws { uint32_t x0, x1, x2, x3; };
 #ifndef Q2048_PHILOX_ROUNDS
 #define Q2048_PHILOX_ROUNDS 10
 #endif
+// one round on the counter words; the caller steps the key (Weyl sequence) between rounds
+Q_HD void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0, uint32_t k1) {
+  const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+  const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+  c1 = (uint32_t)p1;
+  c3 = (uint32_t)p0;
+  c0 = n0;
+  c2 = n2;
+}
+constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
+
 Q_HD Draws philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                          uint32_t k1) {
 #pragma unroll
   for (int r = 0; r < Q2048_PHILOX_ROUNDS; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1;
-    c3 = (uint32_t)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
+    philox_round(c0, c1, c2, c3, k0, k1);
+    k0 += kPhiloxW0;
+    k1 += kPhiloxW1;
   }
   return Draws{c0, c1, c2, c3};
 }
 
+// THE DEFINITION of the draws of (seed, env id, counter, stream); everything below must equal it
 Q_HD Draws draws(uint64_t seed, uint64_t env_id, uint32_t ctr, uint32_t stream) {
   return philox4x32_10((uint32_t)env_id, (uint32_t)(env_id >> 32), ctr, stream, (uint32_t)seed,
                        (uint32_t)(seed >> 32));
+}
+
+// The same draws for a loop over the counter: of the four counter words only c2 = ctr changes from step to
+// step, so round 1's 0xD2511F53 * c0 and -- its high half being all of round 2's c2 -- round 2's
+// 0xCD9E8D57 * c2 are the same on every step.  draws_prepare does those two products once per env,
+// draws_at the other 2 * ROUNDS - 2 (the one on ctr alone is the same for every env of a launch: on the
+// device it is scalar arithmetic).  draws_at(draws_prepare(seed, id, stream), ctr) == draws(seed, id, ctr, stream).
+static_assert(Q2048_PHILOX_ROUNDS >= 2, "draws_prepare folds the first two rounds");
+struct DrawPrep {
+  uint32_t a;        // c1 ^ k0: round 1's c0 but for hi(M1 * ctr)
+  uint32_t b;        // hi(M1 * n2) ^ (k0 + W0): round 2's c0 but for lo(M1 * ctr)
+  uint32_t c;        // lo(M0 * c0) ^ (k1 + W1): round 2's c2 but for hi(M0 * round 1's c0)
+  uint32_t d;        // lo(M1 * n2): c1 after round 2
+  uint32_t k0, k1;   // the key after two rounds
+};
+Q_HD DrawPrep draws_prepare(uint64_t seed, uint64_t env_id, uint32_t stream) {
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  const uint64_t p0 = (uint64_t)0xD2511F53u * (uint32_t)env_id;
+  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ stream ^ k1;          // round 1's c2
+  const uint64_t p1 = (uint64_t)0xCD9E8D57u * n2;
+  return DrawPrep{(uint32_t)(env_id >> 32) ^ k0, (uint32_t)(p1 >> 32) ^ (k0 + kPhiloxW0),
+                  (uint32_t)p0 ^ (k1 + kPhiloxW1), (uint32_t)p1, k0 + 2u * kPhiloxW0, k1 + 2u * kPhiloxW1};
+}
+Q_HD Draws draws_at(const DrawPrep& p, uint32_t ctr) {
+  const uint64_t q1 = (uint64_t)0xCD9E8D57u * ctr;                  // round 1, the counter's product
+  const uint64_t q0 = (uint64_t)0xD2511F53u * ((uint32_t)(q1 >> 32) ^ p.a);   // round 2
+  uint32_t c0 = p.b ^ (uint32_t)q1, c1 = p.d, c2 = (uint32_t)(q0 >> 32) ^ p.c, c3 = (uint32_t)q0;
+  uint32_t k0 = p.k0, k1 = p.k1;
+#pragma unroll
+  for (int r = 2; r < Q2048_PHILOX_ROUNDS; ++r) {
+    philox_round(c0, c1, c2, c3, k0, k1);
+    k0 += kPhiloxW0;
+    k1 += kPhiloxW1;
+  }
+  return Draws{c0, c1, c2, c3};
 }
 
 // draw -> decision (DESIGN.md "draw contract"; the reference call each replaces is cited there)
@@ -240,6 +282,31 @@ Q_HD double lut_pow12(uint32_t L) { constexpr double t[32] = Q2048_POW12; return
 Q_HD double lut_log2p1(uint32_t L) { constexpr double t[32] = Q2048_LOG2P1; return t[L & 31u]; }
 Q_HD double lut_stall(uint32_t k) { constexpr double t[32] = Q2048_STALL; return t[k < 31u ? k : 31u]; }
 
+
+// WHERE the five tables are read from.  Indexed per lane, a constexpr array becomes a vector load from constant
+// memory in the middle of the step -- on the device that is the address path of the table requests, and the wait
+// for its answer also waits for every table request still in flight.  The fused rollout therefore stages one
+// LutImage per workgroup in LDS and steps through ImageLuts; ConstLuts (the arrays above) is the definition and
+// the default of every function below.  Both are initialised from the same generated lists: equal bit for bit.
+struct LutImage { double pow12[32], log2p1[32], stall[32], log2_inv[64], log2_lg[64]; };
+#define Q2048_LUT_IMAGE { Q2048_POW12, Q2048_LOG2P1, Q2048_STALL, Q2048_LOG2_INV, Q2048_LOG2_LG }
+constexpr int kLutImageDoubles = (int)(sizeof(LutImage) / sizeof(double));   // 224: 1792 bytes
+struct ConstLuts {
+  Q_HD double pow12(uint32_t L) const { return lut_pow12(L); }
+  Q_HD double log2p1(uint32_t L) const { return lut_log2p1(L); }
+  Q_HD double stall(uint32_t k) const { return lut_stall(k); }
+  Q_HD double log2_inv(uint32_t j) const { constexpr double t[64] = Q2048_LOG2_INV; return t[j & 63u]; }
+  Q_HD double log2_lg(uint32_t j) const { constexpr double t[64] = Q2048_LOG2_LG; return t[j & 63u]; }
+};
+struct ImageLuts {
+  const LutImage* im;
+  Q_HD double pow12(uint32_t L) const { return im->pow12[L & 31u]; }
+  Q_HD double log2p1(uint32_t L) const { return im->log2p1[L & 31u]; }
+  Q_HD double stall(uint32_t k) const { return im->stall[k < 31u ? k : 31u]; }
+  Q_HD double log2_inv(uint32_t j) const { return im->log2_inv[j & 63u]; }
+  Q_HD double log2_lg(uint32_t j) const { return im->log2_lg[j & 63u]; }
+};
+
 Q_HD uint64_t f64_bits(double d) { union { double d; uint64_t u; } c; c.d = d; return c.u; }
 Q_HD double bits_f64(uint64_t u) { union { double d; uint64_t u; } c; c.u = u; return c.d; }
 
@@ -248,44 +315,46 @@ Q_HD double bits_f64(uint64_t u) { union { double d; uint64_t u; } c; c.u = u; r
 // stored as float32, so this is >20 bits more than the rounding it feeds.
 //   x = m * 2^e, m in [1, 2);  j = top 6 mantissa bits;  r = m * inv[j] - 1, |r| <= 2^-7;
 //   log2(x) = e + lg[j] + r * (a1 + r * (a2 + ... + r * a6)),  lg[j] = -log2(inv[j]) exactly.
-Q_HD double log2_ge1(double x) {
-  constexpr double inv[64] = Q2048_LOG2_INV;
-  constexpr double lg[64] = Q2048_LOG2_LG;
+template <class LutT = ConstLuts>
+Q_HD double log2_ge1(double x, const LutT& lut = LutT()) {
   constexpr double a[6] = Q2048_LOG2_COEF;
   const uint64_t u = f64_bits(x);
   const int e = (int)(u >> 52) - 1023;
   const uint32_t j = (uint32_t)(u >> 46) & 63u;
   const double m = bits_f64((u & 0x000FFFFFFFFFFFFFull) | 0x3FF0000000000000ull);
-  const double r = fma(m, inv[j], -1.0);
+  const double r = fma(m, lut.log2_inv(j), -1.0);
   double p = fma(r, a[5], a[4]);
   p = fma(r, p, a[3]);
   p = fma(r, p, a[2]);
   p = fma(r, p, a[1]);
   p = fma(r, p, a[0]);
-  return fma(r, p, (double)e + lg[j]);
+  return fma(r, p, (double)e + lut.log2_lg(j));
 }
 
 // update_and_normalize (:197-205); both log2 arguments are >= 1
 // One logarithm serves both signs: |r - 1| for r < 0 is |r| + 1, the same double (rounding is
 // symmetric), and r + 1 is |r| + 1 for r >= 0 (-0.0 included).
-Q_HD double normalize_reward(double r) {
-  const double v = fmin(log2_ge1(fabs(r) + 1.0), 10.0);
+template <class LutT = ConstLuts>
+Q_HD double normalize_reward(double r, const LutT& lut = LutT()) {
+  const double v = fmin(log2_ge1(fabs(r) + 1.0, lut), 10.0);
   return r >= 0 ? v : -v;
 }
 
 // calculate_reward (:136-184); L = log2(max tile), prev = log2(previous_max), both integers
-Q_HD double calculate_reward(uint32_t score, bool valid, bool over, uint32_t L, uint8_t& prev) {
+template <class LutT = ConstLuts>
+Q_HD double calculate_reward(uint32_t score, bool valid, bool over, uint32_t L, uint8_t& prev,
+                             const LutT& lut = LutT()) {
   L = L < 1u ? 1u : L;                                   // :141
   const double cl = (double)L;                           // :144
   double bonus = 0.0, r;
   if (L > prev) {                                        // :148
-    bonus = (cl - (double)prev) * lut_pow12(L);          // :149
+    bonus = (cl - (double)prev) * lut.pow12(L);          // :149
     prev = (uint8_t)L;                                   // :150
   }
   if (!valid) {
     if (over) {
-      if (L >= 9u && L <= 11u) r = bonus + lut_pow12(L); // :156-158
-      else r = 0.0 - lut_log2p1(L);                      // :160
+      if (L >= 9u && L <= 11u) r = bonus + lut.pow12(L); // :156-158
+      else r = 0.0 - lut.log2p1(L);                      // :160
     } else {
       r = 0.0 - 0.1 * cl;                                // :164
     }
@@ -293,9 +362,9 @@ Q_HD double calculate_reward(uint32_t score, bool valid, bool over, uint32_t L, 
     r = (double)score;                                   // :168
     if (bonus > 0) r += bonus;                           // :171-172
     else r += cl * 0.05;                                 // :173-174
-    if (L >= 9u) r += lut_pow12(L) * 2;                  // :176-177
+    if (L >= 9u) r += lut.pow12(L) * 2;                  // :176-177
   }
-  return normalize_reward(r);                            // :181
+  return normalize_reward(r, lut);                          // :181
 }
 
 struct StepOut {
@@ -315,15 +384,15 @@ Q_HD bool spawn_then_over(BoardT& b, bool valid, uint32_t x_pos, uint32_t x_val)
 
 // Game2048_env.step (:97-129) for one lane.  x_pos/x_val are the spawn draws.  BoardT is the
 // 4x4 Board above or the 5x5 Board5 of q2048_core5.hpp (same functions, overloaded).
-template <class BoardT>
-Q_HD StepOut env_step(BoardT& b, Aux& a, int action, uint32_t x_pos, uint32_t x_val) {
+template <class BoardT, class LutT = ConstLuts>
+Q_HD StepOut env_step(BoardT& b, Aux& a, int action, uint32_t x_pos, uint32_t x_val, const LutT& lut = LutT()) {
   StepOut o;
   uint32_t score;
   const bool valid = move(b, action, score);                            // :98
   const bool over = spawn_then_over(b, valid, x_pos, x_val);            // :61-62, :99
   const uint32_t mx = max_log2(b);                                      // :100
   a.score += (int32_t)score;                                            // :104
-  double r = calculate_reward(score, valid, over, mx, a.prev_max);      // :107
+  double r = calculate_reward(score, valid, over, mx, a.prev_max, lut); // :107
   uint32_t cnt = a.cons_count;
   if ((uint8_t)action == a.cons_action) {                               // :110
     cnt = cnt + 1u < kConsCountSat ? cnt + 1u : kConsCountSat;          // :111
@@ -335,7 +404,7 @@ Q_HD StepOut env_step(BoardT& b, Aux& a, int action, uint32_t x_pos, uint32_t x_
   bool done = !valid && over;                                           // :117-118
   if (cnt > 10u) {                                                      // :121
     if (cnt > 100u) done = true;                                        // :122-123
-    r += lut_stall(cnt - 10u);                                          // :124-127
+    r += lut.stall(cnt - 10u);                                          // :124-127
   }
   o.reward64 = r;
   o.reward = (float)r;
@@ -399,11 +468,11 @@ Q_HD StepOut env_step_dqn(BoardT& b, Aux& a, int action, uint32_t x_pos, uint32_
 }
 
 // the step of profile ENV; (y_pos, y_val) are only used by kEnvDqn
-template <int ENV, class BoardT>
+template <int ENV, class BoardT, class LutT = ConstLuts>
 Q_HD StepOut env_step_profile(BoardT& b, Aux& a, int action, uint32_t x_pos, uint32_t x_val,
-                              uint32_t y_pos, uint32_t y_val) {
+                              uint32_t y_pos, uint32_t y_val, const LutT& lut = LutT()) {
   if constexpr ((ENV & kEnvDqn) != 0) return env_step_dqn(b, a, action, x_pos, x_val, y_pos, y_val);
-  else return env_step(b, a, action, x_pos, x_val);
+  else return env_step(b, a, action, x_pos, x_val, lut);
 }
 
 // Game2048.__init__ (:11-14) / Game2048_env.reset (:187-191): empty board, two spawns,
@@ -532,6 +601,24 @@ Q_HD float max4(float q0, float q1, float q2, float q3) { return fmaxf(fmaxf(q0,
 Q_HD int eps_greedy(double eps, uint32_t x_eps, uint32_t x_act, float q0, float q1, float q2,
                     float q3, bool& explored) {
   explored = draw_uniform(x_eps) < eps;                       // :35
+  return explored ? draw_action(x_act) : argmax4(q0, q1, q2, q3);  // :36 / :38
+}
+
+// The same test on integers.  draw_uniform(x) = x * 2^-32 is exact in a double, and so is eps * 2^32 (a change
+// of exponent), hence x * 2^-32 < eps <=> x < eps * 2^32 <=> x < ceil(eps * 2^32) for the integer x.
+// eps_threshold is that bound, clamped to [0, 2^32] (eps <= 0 or NaN: never; eps >= 1: always) -- computed
+// once per launch, the step compares one integer instead of cvt + mul + cmp in f64.
+Q_HD uint64_t eps_threshold(double eps) {
+  if (!(eps > 0.0)) return 0ull;
+  if (eps >= 1.0) return 1ull << 32;
+  return (uint64_t)ceil(eps * 4294967296.0);
+}
+Q_HD bool draw_below(uint32_t x, uint64_t threshold) {
+  return (threshold >> 32) != 0ull || x < (uint32_t)threshold;
+}
+Q_HD int eps_greedy_at(uint64_t threshold, uint32_t x_eps, uint32_t x_act, float q0, float q1, float q2,
+                       float q3, bool& explored) {
+  explored = draw_below(x_eps, threshold);                    // :35
   return explored ? draw_action(x_act) : argmax4(q0, q1, q2, q3);  // :36 / :38
 }
 

@@ -343,6 +343,14 @@ inline StepOut env_step_any(int env, BoardT& b, Aux& a, int act, uint32_t x_pos,
   return (env & kEnvDqn) ? env_step_profile<kEnvDqn>(b, a, act, x_pos, x_val, y_pos, y_val)
                          : env_step_profile<0>(b, a, act, x_pos, x_val, y_pos, y_val);
 }
+// the fused rollout's step: the reward tables read from one image (as the device's workgroups read theirs from LDS)
+const LutImage g_lut_image = Q2048_LUT_IMAGE;
+template <class BoardT>
+inline StepOut env_step_any(int env, BoardT& b, Aux& a, int act, uint32_t x_pos, uint32_t x_val, uint32_t y_pos, uint32_t y_val,
+                            const ImageLuts& lut) {
+  return (env & kEnvDqn) ? env_step_profile<kEnvDqn>(b, a, act, x_pos, x_val, y_pos, y_val, lut)
+                         : env_step_profile<0>(b, a, act, x_pos, x_val, y_pos, y_val, lut);
+}
 
 // ---- env ---------------------------------------------------------------------------------------------------------
 template <int N>
@@ -550,8 +558,10 @@ void fused_rollout_n(uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mas
   using Key = typename Geo<N>::Key;
   struct Lane {
     BoardT b; Aux a; Key key_s, key_n; Row q; int64_t slot_s; u64 salt; uint64_t id; double reward_sum;
-    StepOut o; int act; bool explored, same;
+    StepOut o; int act; bool explored, same; DrawPrep prep;
   };
+  const uint64_t eps_t = eps_threshold(eps);     // the step's epsilon test and draws as the device kernel does them
+  const ImageLuts lut{&g_lut_image};
   const int env = env_bits(flags);
   const bool play_only = (flags & Q2048_FLAG_PLAY_ONLY) != 0, no_learn = (flags & Q2048_FLAG_NO_LEARN) != 0;
   const bool learns = !play_only && !no_learn, frozen = (flags & Q2048_FLAG_NO_NEW_ROWS) != 0;
@@ -585,15 +595,16 @@ void fused_rollout_n(uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mas
         L.slot_s = play_only ? kNoSlot : find(L.key_s, L.q);
         if (frozen && learns && L.slot_s < 0) visit_get<N>(cache, i, table, mask, L.key_s, L.q);   // the visit row goes on
         L.reward_sum = 0.0;
+        L.prep = draws_prepare(seed, L.id, kStreamStep);
       }
       for (int t = 0; t < steps; ++t) {
         for (int l = 0; l < n; ++l) {                    // choose, step, ask for s'
           Lane& L = lane[l];
-          const Draws x = draws(seed, L.id, ctr0 + (uint32_t)t, kStreamStep);
+          const Draws x = draws_at(L.prep, ctr0 + (uint32_t)t);
           Draws y{0u, 0u, 0u, 0u};
           if (env & kEnvDqn) y = draws(seed, L.id, ctr0 + (uint32_t)t, kStreamOver);
-          L.act = eps_greedy(eps, x.x0, x.x1, L.q.q0, L.q.q1, L.q.q2, L.q.q3, L.explored);       // :92
-          L.o = env_step_any(env, L.b, L.a, L.act, x.x2, x.x3, y.x0, y.x1);                      // :93
+          L.act = eps_greedy_at(eps_t, x.x0, x.x1, L.q.q0, L.q.q1, L.q.q2, L.q.q3, L.explored);  // :92
+          L.o = env_step_any(env, L.b, L.a, L.act, x.x2, x.x3, y.x0, y.x1, lut);                 // :93
           L.key_n = state_key(L.b, L.salt, status);                                              // :94
           L.same = key_eq(L.key_n, L.key_s);
           if (!L.same && !play_only) __builtin_prefetch(&table[key_hash(L.key_n) & mask], 1, 1);

@@ -1194,6 +1194,11 @@ __device__ unsigned long long* g_timeline;
 #else
 #define Q2048_STAMP(k) do { } while (0)
 #endif
+// The reward tables of the step (q2048_core.hpp, LutImage): one copy in constant memory, staged per workgroup in
+// LDS by the fused rollout, whose step then reads them with ds_read -- no vector load, and no wait on the vector
+// memory counter (which the table's stores and claims of the step before are still counted in), inside the
+// step's arithmetic.
+__device__ const LutImage g_lut_image = Q2048_LUT_IMAGE;
 template <int N, int ENV, int MODE, int BLOCK>
 __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
     uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mask, int64_t B, int steps, double eps,
@@ -1203,8 +1208,13 @@ __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
   RowCache<N>* const cache = static_cast<RowCache<N>*>(row_cache);
   __shared__ BlockStats bs;
   __shared__ Stage<N, BLOCK / 64> st;
+  __shared__ LutImage lut_lds;
+  static_assert(BLOCK >= kLutImageDoubles, "one double of the image per thread");
   Q2048_STAMP(0);
-  stats_clear(bs);
+  if (threadIdx.x < kLutImageDoubles)
+    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
+  stats_clear(bs);                                        // (its barrier publishes the image too)
+  const ImageLuts lut{&lut_lds};
   const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   auto b = load_board(boards, i, B, st);
   if (i < B) {
@@ -1246,14 +1256,17 @@ __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
     uint32_t pend = 0;
     TdCounters tdc{0u, 0u};
     double reward_sum = 0.0;
+    // what the draws and the epsilon test do not need to redo every step (q2048_core.hpp)
+    const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
+    const uint64_t eps_t = eps_threshold(eps);
 
     for (int t = 0; t < steps; ++t) {
-      const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+      const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
       Draws y{0u, 0u, 0u, 0u};
       if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
       bool explored;
-      const int act = eps_greedy(eps, x.x0, x.x1, q.q0, q.q1, q.q2, q.q3, explored);  // main.py:92
-      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1);      // :93
+      const int act = eps_greedy_at(eps_t, x.x0, x.x1, q.q0, q.q1, q.q2, q.q3, explored);  // main.py:92
+      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);     // :93
       const auto key_n = state_key(b, salt, status);                                   // :94
       const bool same = key_eq(key_n, key_s);
       // the row of s: claimed one step ago (in flight since), or now if s opened the episode/launch
