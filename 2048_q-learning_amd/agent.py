@@ -455,6 +455,7 @@ class BatchedQLearningAgent:
         self._steps_at_read, self._steps_launched, self._row_rate = 0, 0, 1.0
         self._warned_full = False
         self.stats_i, self.stats_f = new_stats_vectors(self.device)
+        self._play_stats = None                   # the greedy player's own statistics (`play_rollout`), made when first used
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.q_table = _QTableView(self)
         self.row_cache_enabled = bool(row_cache)
@@ -623,6 +624,39 @@ class BatchedQLearningAgent:
             self._mirror_launches += 1
         env.ctr += int(steps)
         self.ctr += int(steps)
+
+    def play_rollout(self, env: BatchedGame2048Env, steps: int, epsilon: float = 0.0) -> None:
+        """The greedy player (q2048_play_rollout): `steps` steps of every env in ONE launch, each the first maximum
+        of the state's stored row over the moves that CHANGE the board (with probability `epsilon` a uniformly drawn
+        legal move instead), the env step, and on done the episode statistics and the reset -- what
+        `evaluate.py --policy legal` measures, without its four library calls and twenty torch kernels per step.
+        The table is only read: nothing is learnt, created or cached.  The player is a function of (table, env):
+        seed, env_id0 and the step counter are the ENV's (an evaluation batch need not be in step with the
+        agent), `env.ctr` advances, `agent.ctr`, the row cache and the growth / freeze bookkeeping are untouched.
+        Statistics go to a buffer of the player's own (`play_stats`), never into the training statistics."""
+        if env.device != self.device:
+            raise ValueError("env and agent live on different devices")
+        if env.board_size != self.board_size:
+            raise ValueError("env and agent have different board sizes")
+        if self._play_stats is None:
+            self._play_stats = new_stats_vectors(self.device)
+        si, sf = self._play_stats
+        N.check(self._L.q2048_play_rollout(
+            _ptr(env.boards), _ptr(env.aux), _ptr(self.table), self.capacity_log2, env.num_envs, self.board_size,
+            int(steps), float(epsilon), env.seed, env.env_id0, env.ctr & 0xFFFFFFFF,
+            (self.flags & N.FLAG_INDEPENDENT) | env.env_flags, _ptr(si), _ptr(sf), _ptr(self.status),
+            _stream(self.device)), "play_rollout")
+        env.ctr += int(steps)
+
+    def play_stats(self, reset: bool = False) -> dict:
+        """Synchronising host copy of the player's statistics (the dict of `stats()`; inserts and drops are 0)."""
+        if self._play_stats is None:
+            self._play_stats = new_stats_vectors(self.device)
+        out = stats_dict(*(v.cpu().numpy() for v in self._play_stats))   # (read before the reset: on "cpu" these are views)
+        if reset:
+            for v in self._play_stats:
+                v.zero_()
+        return out
 
     def mirrored_stats(self):
         """(stats_i, stats_f) as the last `fused_rollout` launch left them, read from the host-side

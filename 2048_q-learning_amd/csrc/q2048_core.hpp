@@ -622,6 +622,48 @@ Q_HD int eps_greedy_at(uint64_t threshold, uint32_t x_eps, uint32_t x_act, float
   return explored ? draw_action(x_act) : argmax4(q0, q1, q2, q3);  // :36 / :38
 }
 
+// ------------------------------------------------------------------------------------------
+// the greedy PLAYER's decision (q2048_play_rollout; kernel and CPU twin both decide through these two)
+// ------------------------------------------------------------------------------------------
+// legal-move mask: bit a is set iff action a would change the board -- the trial-move loop of
+// Deep_QLearning/main_dir/mainDQL_CNN_step2.py:168-174 (`env.game.move(action, trial=True)`), what
+// q2048_legal_moves writes.  Four trial moves on a copy; only the four answers are kept.
+template <class BoardT>
+Q_HD uint32_t legal_mask(const BoardT& b) {
+  uint32_t m = 0;
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    BoardT t = b;
+    uint32_t score;
+    m |= (uint32_t)move(t, a, score) << a;
+  }
+  return m;
+}
+// The move of a player that only makes moves that change the board.  Greedy: the first maximum of the row over
+// the legal moves, ascending action order, strict > (np.argmax of the masked row, Agent/main.py:34-38 restricted
+// to the mask; +0 and -0 compare equal).  Exploring (x_eps below the launch's eps_threshold): the k-th legal move
+// in ascending order, k = (x_act * n_legal) >> 32.  No legal move: action 0, never counted as explored.
+Q_HD int play_action(uint32_t legal, float q0, float q1, float q2, float q3, uint64_t threshold, uint32_t x_eps,
+                     uint32_t x_act, bool& explored) {
+  legal &= 15u;
+  const uint32_t n_legal = popc(legal);
+  explored = n_legal != 0u && draw_below(x_eps, threshold);
+  if (explored) {
+    uint32_t k = draw_index(x_act, n_legal), m = legal;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { const bool drop = k != 0u; m &= drop ? m - 1u : m; k -= drop ? 1u : 0u; }
+    return __builtin_ctz(m);
+  }
+  int best = 0;
+  float top = 0.f;
+  bool have = false;
+  if (legal & 1u) { top = q0; have = true; }
+  if ((legal & 2u) && (!have || q1 > top)) { top = q1; best = 1; have = true; }
+  if ((legal & 4u) && (!have || q2 > top)) { top = q2; best = 2; have = true; }
+  if ((legal & 8u) && (!have || q3 > top)) { top = q3; best = 3; }
+  return best;
+}
+
 // update_q_value (Agent/main.py:41-43) in the reference's own double arithmetic: no fused
 // multiply-add (CPython rounds the product and the sum separately, and so does the oracle), so the
 // device's doubles equal the oracle's bit for bit and only the final float32 store differs from the

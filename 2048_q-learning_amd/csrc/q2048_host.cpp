@@ -680,6 +680,56 @@ void fused_rollout_n(uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mas
   stats_merge(parts, used, stats_i, stats_f);
 }
 
+// ---- the greedy player (q2048_play_rollout): row, legal-move mask, play_action (q2048_core.hpp: the kernel's own
+// decision), env step, statistics and reset on done -- `steps` times per env, the table only read.  Envs are split
+// over the threads as the fused rollout splits them; an env's trajectory does not depend on the split.
+template <int N>
+void play_rollout_n(uint8_t* boards, q2048_aux* aux, const q2048_slot* table, u64 mask, int64_t B, int steps, double eps,
+                    uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i, double* stats_f,
+                    uint32_t* status) {
+  const uint64_t eps_t = eps_threshold(eps);
+  const ImageLuts lut{&g_lut_image};
+  const int env = env_bits(flags);
+  const int T = threads_for(B);
+  std::vector<Stats> parts((size_t)T);
+  Stats* sp = parts.data();
+  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+    Stats& st = sp[tid];
+    for (int64_t i = lo; i < hi; ++i) {
+      const uint64_t id = env_id0 + (uint64_t)i;
+      const u64 salt = (flags & Q2048_FLAG_INDEPENDENT) ? lane_salt(id) : 0ull;
+      typename Geo<N>::BoardT b;
+      load_board(boards, i, b);
+      Aux a = ld_aux(aux, i);
+      const DrawPrep prep = draws_prepare(seed, id, kStreamStep);
+      double reward_sum = 0.0;
+      for (int t = 0; t < steps; ++t) {
+        const Draws x = draws_at(prep, ctr0 + (uint32_t)t);
+        Draws y{0u, 0u, 0u, 0u};
+        if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+        Row q;
+        probe_find(table, mask, state_key(b, salt, status), q, kMaxProbe);
+        bool explored;
+        const int act = play_action(legal_mask(b), q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
+        const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+        st.i[Q2048_ST_VALID] += o.valid != 0;
+        st.i[Q2048_ST_EXPLORE] += explored;
+        reward_sum += (double)o.reward;
+        if (o.done) {
+          st.i[Q2048_ST_EPISODES] += 1;
+          st.episode(a, o.max_log2);
+          begin_episode(b, a, seed, id, (env & kEnvResetShaping) != 0);
+        }
+      }
+      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
+      st.f[Q2048_SF_REWARD] += reward_sum;
+      store_board(boards, i, b);
+      st_aux(aux, i, a);
+    }
+  });
+  stats_merge(parts, used, stats_i, stats_f);
+}
+
 // ---- the deterministic step: phase 1 over every env against the step-start table, then each (row, action) group
 // folds its updates in env order in double and rounds once (include/q2048.h "Deterministic mode") ----------------
 template <int N>
@@ -968,6 +1018,23 @@ int q2048_fused_rollout_opts(uint8_t* boards, q2048_aux* aux, q2048_slot* table,
     std::memcpy(m + Q2048_NSTAT_I, stats_f, sizeof(double) * Q2048_NSTAT_F);
     m[Q2048_MIRROR_SEQ] = ++o.mirror_ticket[1];
   }
+  return Q2048_OK;
+}
+int q2048_play_rollout(uint8_t* boards, q2048_aux* aux, const q2048_slot* table, int cap_log2, int64_t B, int n,
+                       int64_t steps, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
+                       int64_t* stats_i, double* stats_f, uint32_t* status, void*) {
+  if (int e = check_batch(B, n)) return e;
+  if (int e = check_flags(flags, kAbiFlags & ~(Q2048_FLAG_INDEPENDENT | Q2048_FLAG_ENV_DQN | Q2048_FLAG_RESET_SHAPING)))
+    return e;
+  if (int e = check_table(table, cap_log2)) return e;
+  if (!boards || !aux || !status) return Q2048_ERR_NULL;
+  if (!aligned16(boards) || !aligned16(aux)) return Q2048_ERR_ALIGN;
+  if (steps < 0 || steps > (1 << 30)) return Q2048_ERR_SIZE;
+  if (!(eps >= 0.0 && eps <= 1.0)) return Q2048_ERR_RANGE;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  const u64 mask = (1ull << cap_log2) - 1ull;
+  if (n == 4) play_rollout_n<4>(boards, aux, table, mask, B, (int)steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status);
+  else play_rollout_n<5>(boards, aux, table, mask, B, (int)steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status);
   return Q2048_OK;
 }
 int q2048_fused_rollout(uint8_t* boards, q2048_aux* aux, q2048_slot* table, int cap_log2, int64_t B, int n,

@@ -1376,6 +1376,71 @@ __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
 }
 
 // ---------------------------------------------------------------------------------------------
+// the greedy player (q2048_play_rollout): what a table is worth over the moves that change the board, `steps`
+// times per lane in one launch.  Per step: the row of the state (q2048_q_lookup's probe: bulk limit, absent = zeros),
+// the trial-move mask (k_legal_moves), the first maximum over the legal moves -- or, exploring, the k-th legal
+// move -- (play_action, q2048_core.hpp: shared with the CPU twin), the env step on the step's own draws, and on
+// done the episode statistics and the reset, as in the fused rollout.  A valid move always changes the state, so
+// there is no row to carry: one lookup per step, and nothing is written but boards, aux and the statistics.
+// Every loop is bounded by `steps` and the probe limit; no lane waits for another; the table sees loads only.
+// ---------------------------------------------------------------------------------------------
+template <int N, int ENV>
+__global__ __launch_bounds__(kBlock) void k_play_rollout(
+    uint8_t* boards, q2048_aux* aux, const q2048_slot* table, u64 mask, int64_t B, int steps, double eps,
+    uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i, double* stats_f,
+    uint32_t* status) {
+  __shared__ BlockStats bs;
+  __shared__ Stage<N> st;
+  __shared__ LutImage lut_lds;
+  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
+  if (threadIdx.x < kLutImageDoubles)
+    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
+  stats_clear(bs);                                        // (its barrier publishes the image too)
+  const ImageLuts lut{&lut_lds};
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  auto b = load_board(boards, i, B, st);
+  if (i < B) {
+    const uint64_t id = env_id0 + (uint64_t)i;
+    const u64 salt = (flags & Q2048_FLAG_INDEPENDENT) ? lane_salt(id) : 0ull;
+    Aux a = ld_aux(aux, i);
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
+    double reward_sum = 0.0;
+    const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
+    const uint64_t eps_t = eps_threshold(eps);
+    for (int t = 0; t < steps; ++t) {
+      const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
+      Draws y{0u, 0u, 0u, 0u};
+      if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+      Row q;
+      bool made;
+      probe_find(table, mask, state_key(b, salt, status), q, made, kMaxProbe);
+      bool explored;
+      const int act = play_action(legal_mask(b), q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
+      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+      if (o.done) {
+        episode_stats(bs, a, o.max_log2);
+        begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
+      }
+      n_valid += wave_count(o.valid != 0);
+      n_explore += wave_count(explored);
+      n_done += wave_count(o.done != 0);
+      reward_sum += (double)o.reward;
+    }
+    st_aux(aux, i, a);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+    const uint32_t n_active = wave_count(true);
+    if (wave_leader()) {
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  store_board(boards, i, B, b, st);
+  stats_flush(bs, stats_i, stats_f);
+}
+
+// ---------------------------------------------------------------------------------------------
 // deterministic mode.  One step = phase 1 (every env acts on the table as it is at the start of
 // the step and emits where its update goes and its TD target), a stable radix sort of the updates
 // by a 16-bit hash of (state, action) -- two 8-bit passes of the radix partition below -- and
@@ -2628,6 +2693,23 @@ int q2048_fused_rollout_opts(uint8_t* boards, q2048_aux* aux, q2048_slot* table,
                      (u64)((1ull << cap_log2) - 1ull), B, (int)steps, eps, lr, gamma, seed, env_id0, ctr0,
                      flags, stats_i, stats_f, status, o.log, o.log_capacity, reinterpret_cast<u64*>(o.log_count),
                      o.row_cache, reinterpret_cast<u64*>(o.stats_mirror), o.mirror_ticket, side);
+  return launch_status();
+}
+
+int q2048_play_rollout(uint8_t* boards, q2048_aux* aux, const q2048_slot* table, int cap_log2, int64_t B, int n,
+                       int64_t steps, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
+                       int64_t* stats_i, double* stats_f, uint32_t* status, void* stream) {
+  if (int e = check_batch(B, n)) return e;
+  if (int e = check_flags(flags, kAbiFlags & ~(Q2048_FLAG_INDEPENDENT | Q2048_FLAG_ENV_DQN | Q2048_FLAG_RESET_SHAPING)))
+    return e;
+  if (int e = check_table(table, cap_log2)) return e;
+  if (!boards || !aux || !status) return Q2048_ERR_NULL;
+  if (!aligned16(boards) || !aligned16(aux)) return Q2048_ERR_ALIGN;
+  if (steps < 0 || steps > (1 << 30)) return Q2048_ERR_SIZE;
+  if (!(eps >= 0.0 && eps <= 1.0)) return Q2048_ERR_RANGE;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  Q2048_LAUNCH_ENV(k_play_rollout, flags, n, B, stream, boards, aux, table, (u64)((1ull << cap_log2) - 1ull), B,
+                   (int)steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status);
   return launch_status();
 }
 

@@ -10,7 +10,9 @@ score / return, max-tile histogram.  Two policies:
   --policy legal (default)   argmax of the stored row over the moves that CHANGE the board (the trial-move
         mask of Deep_QLearning/main_dir/mainDQL_CNN_step2.py:168-174, `q2048_legal_moves`; first maximum wins
         as in np.argmax, a state without a row reads as zeros): what a trained table is worth as a player.
-        Batched calls: q_values, legal_moves, step, reset(done).
+        Batched calls: q_values, legal_moves, step, reset(done).  With --fused the whole step -- lookup, mask,
+        choice, env step, statistics, reset -- runs in the kernel, `--steps-per-launch` steps per launch
+        (q2048_play_rollout): the same games at --epsilon 0, at the batch sizes the project trains at.
   --policy reference         the agent of Agent/main.py:34-38 with its learning switched off, through the
         fused rollout with Q2048_FLAG_NO_LEARN: argmax over ALL four actions.  The reference's loop relies on
         the update that follows an invalid move (its negative reward sends argmax elsewhere, main.py:43,99);
@@ -48,7 +50,15 @@ def parse_args(argv=None):
     p.add_argument("--max-steps", type=int, default=100000, help="stop after this many steps per env at the latest")
     p.add_argument("--env-profile", choices=["shaped", "nopenalty"], default="shaped")
     p.add_argument("--reset-shaping-state", action="store_true")
-    return p.parse_args(argv)
+    p.add_argument("--fused", action="store_true",
+                   help="--policy legal in ONE launch per --steps-per-launch steps (q2048_play_rollout: lookup, legal-move "
+                        "mask, choice, env step, statistics and reset in the kernel) instead of four library calls and "
+                        "about twenty torch kernels per step.  Same games at --epsilon 0; with --epsilon > 0 the "
+                        "exploring moves come from the step draws (the player's draw contract), not from torch's generator")
+    args = p.parse_args(argv)
+    if args.fused and args.policy != "legal":
+        p.error("--fused applies to --policy legal")
+    return args
 
 
 def main(argv=None):
@@ -69,7 +79,9 @@ def main(argv=None):
                                  profile=args.env_profile, reset_shaping_state=args.reset_shaping_state)
     rows_before = agent.table_size()
     target, t0 = args.episodes * args.num_envs, time.time()
-    if args.policy == "legal":
+    if args.policy == "legal" and args.fused:
+        st = play_fused(agent, env, args, target)
+    elif args.policy == "legal":
         st = play_legal_moves(torch, agent, env, args, target)
     else:
         st = agent.stats()
@@ -78,14 +90,30 @@ def main(argv=None):
                 agent.fused_rollout(env, args.steps_per_launch, learn=False)
             st = agent.stats()
     assert agent.table_size() == rows_before and st["inserts"] == 0      # nothing was learnt
-    print(json.dumps({"model": args.model, "rows": rows_before, "board_size": n, "epsilon": args.epsilon,
-                      "policy": args.policy,
-                      "envs": args.num_envs, "games": st["episodes"], "env_steps": st["steps"],
-                      "mean_score": st["mean_score"], "mean_return": st["mean_return"],
-                      "valid_move_frac": st["valid_moves"] / max(st["steps"], 1),
-                      "max_tile_hist": {str(k): v for k, v in st["max_tile_hist"].items()},
-                      "best_tile": max(st["max_tile_hist"], default=0),
-                      "seconds": round(time.time() - t0, 3)}))
+    out = {"model": args.model, "rows": rows_before, "board_size": n, "epsilon": args.epsilon,
+           "policy": args.policy,
+           "envs": args.num_envs, "games": st["episodes"], "env_steps": st["steps"],
+           "mean_score": st["mean_score"], "mean_return": st["mean_return"],
+           "valid_move_frac": st["valid_moves"] / max(st["steps"], 1),
+           "max_tile_hist": {str(k): v for k, v in st["max_tile_hist"].items()},
+           "best_tile": max(st["max_tile_hist"], default=0),
+           "seconds": round(time.time() - t0, 3)}
+    if args.fused:
+        out["fused"] = True
+    print(json.dumps(out))
+    return st
+
+
+def play_fused(agent, env, args, target) -> dict:
+    """`play_legal_moves` in one launch per `--steps-per-launch` steps (`BatchedQLearningAgent.play_rollout`): the same
+    cadence -- the number of finished games is read once per launch -- and, at --epsilon 0, the same games."""
+    agent.play_stats(reset=True)
+    st = agent.play_stats()
+    while st["episodes"] < target and env.ctr < args.max_steps:
+        agent.play_rollout(env, args.steps_per_launch, args.epsilon)
+        st = agent.play_stats()
+    games = max(st["episodes"], 1)
+    st.update({"mean_score": st["score_sum"] / games, "mean_return": st["return_sum"] / games})
     return st
 
 

@@ -63,7 +63,8 @@ extern "C" {
                                the table); q2048_fused_rollout_opts accepts both the 56-byte layout shipped before and
                                the 64-byte one, so a caller built against the earlier header runs unchanged;
                                q2048_table_merge (combine two tables on the device) arrived without a bump as well: a
-                               caller detects it by its symbol */
+                               caller detects it by its symbol; so did q2048_play_rollout (the greedy player over the
+                               legal moves, one launch) */
 
 /* return codes */
 #define Q2048_OK 0
@@ -437,6 +438,37 @@ int q2048_fused_rollout_opts(uint8_t *boards, q2048_aux *aux, q2048_slot *table,
                              uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
                              int64_t *stats_i, double *stats_f, uint32_t *status,
                              const q2048_rollout_opts *opts, void *stream);
+
+/* The GREEDY PLAYER: what a trained table is worth when only moves that change the board are made -- `steps` steps
+ * for B envs in ONE launch, the table only read.  It replaces the loop q_lookup / legal_moves / env_step /
+ * env_reset(done) (evaluate.py --policy legal): the legal-move mask is the trial-move loop of
+ * Deep_QLearning/main_dir/mainDQL_CNN_step2.py:168-174, the choice the argmax of Agent/main.py:34-38 restricted to it.
+ * One step of one env (lane i = global env env_id0 + i, counter ctr0 + t):
+ *   row     the state's row exactly as q2048_q_lookup reads it (same probe and probe limit: rows beyond the learning
+ *           paths' limit are found; Q2048_FLAG_INDEPENDENT salts the key with the env's id; an absent state reads as
+ *           zeros; `reserved` is never interpreted, so a 4x4 table that carries line summaries plays the same);
+ *   mask    bit a set iff action a would change the board (q2048_legal_moves);
+ *   action  the first maximum of the row over the legal moves: ascending action order, strict > (np.argmax of the
+ *           masked row; +0 and -0 compare equal).  No legal move: action 0;
+ *   explore DRAW CONTRACT of the player: the step's one Philox call (stream 0 of (seed, env id, ctr0 + t), the call
+ *           q2048_env_step makes) gives x0..x3.  The env explores iff x0 < ceil(eps * 2^32) (eps >= 1: always, eps = 0:
+ *           never -- the integer form of x0 / 2^32 < eps) AND it has a legal move; its move is then the k-th legal one
+ *           in ascending order, k = (x1 * n_legal) >> 32.  With no legal move the action stays 0 and the step is not
+ *           counted as explored.  (q2048_q_choose draws its random action from all four: x1 >> 30.)
+ *   step    q2048_env_step's step with x2, x3 of the same call (Q2048_FLAG_ENV_DQN: the DQN path's env, its
+ *           is_game_over spawn from words 0, 1 of stream 2) -- the draws q2048_env_step uses at counter ctr0 + t; on
+ *           done the episode statistics and the reset of q2048_fused_rollout.
+ * Written: boards, aux, the statistics -- steps, valid, explore, episodes, the score / return sums, the max-tile
+ * histogram and the reward sum, ADDED to stats_i / stats_f (either may be NULL; inserts and drops stay 0) -- and
+ * Q2048_STATUS_TILE_OVERFLOW.  Never the table, no row cache, no other status bit: the result is a function of
+ * (table, boards, aux, seed, env ids, counter) at any B.
+ * flags: Q2048_FLAG_INDEPENDENT, _ENV_DQN, _RESET_SHAPING; any other Q2048_FLAG_* bit, and any bit outside the ABI, is
+ * Q2048_ERR_FLAGS.  eps outside [0, 1] is Q2048_ERR_RANGE.  B == 0 or steps == 0: nothing happens, Q2048_OK.  Argument
+ * errors in the order of q2048_fused_rollout: n, B, flags, table (NULL, cap_log2, alignment), boards / aux / status
+ * NULL, their alignment, steps, eps. */
+int q2048_play_rollout(uint8_t *boards, q2048_aux *aux, const q2048_slot *table, int cap_log2, int64_t B, int n,
+                       int64_t steps, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
+                       int64_t *stats_i, double *stats_f, uint32_t *status, void *stream);
 
 /* Deterministic mode: reproducible shared-table training at any B (the default rollout is
  * lock-free and depends on scheduling wherever lanes share a state).  Per step:

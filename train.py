@@ -106,6 +106,19 @@ def parse_args(argv=None):
                    "--episodes schedule are done; 0 = run to the end")
     p.add_argument("--summary", default="", help="after the run, write the per-episode log's summary row "
                    "(layout of the reference's plots/summary_statistics_cleaned.csv) to this CSV")
+    p.add_argument("--eval-every", type=int, default=0,
+                   help="batched mode, hash-table agent: every N epochs measure the table as a PLAYER -- greedy over the "
+                        "moves that change the board (evaluate.py --policy legal --fused, q2048_play_rollout) on a "
+                        "separate env batch with its own seed, between two training launches on the training stream. "
+                        "The table is only read and training's draws, counters and statistics are untouched: the run "
+                        "trains what it trains without the flag.  0 (default) = off")
+    p.add_argument("--eval-envs", type=int, default=4096, help="envs of the evaluation batch (--eval-every)")
+    p.add_argument("--eval-episodes", type=int, default=1, help="games per evaluation env and evaluation (on average)")
+    p.add_argument("--eval-log", default="eval_log.jsonl",
+                   help="one JSON line per evaluation: epoch, env_steps trained, games, mean_score, mean_return, "
+                        "max_tile_hist, valid_move_frac (PATH.rankR in a multi-rank job: every rank plays its replica)")
+    p.add_argument("--eval-max-steps", type=int, default=100000, help="an evaluation stops after this many steps per env "
+                   "at the latest")
     return p.parse_args(argv)
 
 
@@ -244,6 +257,11 @@ def train_batched(args, pkg):
     stop_epoch = min(args.episodes, args.stop_epoch) if args.stop_epoch else args.episodes
     target = stop_epoch * shard.total_envs
     best_tile, grown, reports, said_frozen = 0, 0, 0, False
+    evaluator = None
+    if args.eval_every > 0:
+        if args.agent != "hash":
+            raise SystemExit("--eval-every applies to the hash-table agent")
+        evaluator = _Evaluator(args, pkg, agent, dev, rank, world, epoch)
     agent.train_progress = {"epoch": epoch}
     agent.train_env = env
     while total_eps < target:
@@ -268,6 +286,8 @@ def train_batched(args, pkg):
             agent.decay_exploration(epoch)                # Agent/main.py:109, once per epoch
             epoch += 1
         agent.train_progress = {"epoch": epoch}
+        if evaluator is not None:
+            evaluator.maybe(epoch, st["steps"])
         best_tile = max(st["max_tile_hist"], default=0)
         reports += 1
         if args.agent == "hash":
@@ -304,6 +324,46 @@ def train_batched(args, pkg):
         pkg.dist.barrier()
         torch.distributed.destroy_process_group()
     return agent
+
+
+class _Evaluator:
+    """--eval-every: the table as a greedy player over the legal moves (`BatchedQLearningAgent.play_rollout`) on an
+    env batch of its own -- its own seed, derived from --seed; its own step counter -- queued on the training stream
+    between two training launches.  The player reads the table and writes its env batch and its own statistics:
+    the training env, the agent's counters, row cache, statistics and growth bookkeeping never see it."""
+
+    def __init__(self, args, pkg, agent, dev, rank, world, epoch):
+        import json
+
+        self._json, self.args, self.agent = json, args, agent
+        seed = (args.seed * 6364136223846793005 + 1442695040888963407) & ((1 << 63) - 1)
+        self.env = pkg.BatchedGame2048Env(args.eval_envs, args.board_size, dev, seed, rank * args.eval_envs,
+                                          profile=args.env_profile, reset_shaping_state=args.reset_shaping_state)
+        self.path = args.eval_log if world == 1 else f"{args.eval_log}.rank{rank}"
+        self.next_epoch = (epoch // args.eval_every + 1) * args.eval_every
+        open(self.path, "w").close()
+
+    def maybe(self, epoch, env_steps):
+        """One evaluation, and one line of the log, per multiple of --eval-every that `epoch` has reached."""
+        while self.next_epoch <= epoch:
+            self.run(self.next_epoch, env_steps)
+            self.next_epoch += self.args.eval_every
+
+    def run(self, epoch, env_steps):
+        args, agent, env = self.args, self.agent, self.env
+        target, last = args.eval_episodes * env.num_envs, env.ctr + args.eval_max_steps
+        agent.play_stats(reset=True)
+        st = agent.play_stats()
+        while st["episodes"] < target and env.ctr < last:
+            agent.play_rollout(env, args.steps_per_launch)
+            st = agent.play_stats()
+        games = max(st["episodes"], 1)
+        with open(self.path, "a") as fh:
+            fh.write(self._json.dumps({
+                "epoch": epoch, "env_steps": env_steps, "games": st["episodes"], "mean_score": st["score_sum"] / games,
+                "mean_return": st["return_sum"] / games,
+                "max_tile_hist": {str(k): v for k, v in st["max_tile_hist"].items()},
+                "valid_move_frac": st["valid_moves"] / max(st["steps"], 1)}) + "\n")
 
 
 def _report_growths(agent, grown, rank) -> int:
