@@ -32,6 +32,7 @@ STATUS_BAD_ACTION, STATUS_TILE_OVERFLOW, STATUS_TABLE_FULL, STATUS_DEEP_ROW = 1,
 FLAG_INDEPENDENT, FLAG_SINGLE_ENV, FLAG_TD_CAS = 1, 2, 4
 FLAG_ENV_DQN, FLAG_RESET_SHAPING, FLAG_PLAY_ONLY, FLAG_NO_LEARN, FLAG_NO_NEW_ROWS = 8, 16, 32, 64, 128
 FLAG_LINE_SUMMARY = 1 << 24
+FLAG_SYMMETRIC = 1 << 26
 MERGE_ADD, MERGE_BLEND, MERGE_MAXABS = 0, 1, 2
 ABI_VERSION = 7
 ST_STEPS, ST_EPISODES, ST_VALID, ST_SCORE, ST_INSERTS, ST_DROPS, ST_EXPLORE, ST_CAS_RETRY = range(8)
@@ -213,6 +214,7 @@ _SIGNATURES = {
     "q2048_rowcache_rebind": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                         C.c_void_p]),
     "q2048_legal_moves": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "q2048_canonicalize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "q2048_encode_onehot": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "q2048_rt_choose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_uint64, C.c_uint64,
                                   C.c_uint32, C.c_void_p, C.c_void_p]),

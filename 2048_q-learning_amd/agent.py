@@ -358,6 +358,15 @@ class BatchedQLearningAgent:
     strict_td       update Q[s][a] with a compare-and-swap loop (concurrent updates of one entry
                     serialise) instead of one store (last writer wins).  Same result whenever
                     no two lanes share (s, a); several times slower when many lanes do.
+    symmetric       SYMMETRY FOLDING (Q2048_FLAG_SYMMETRIC, 4x4 only): the table holds one row for the eight mirror
+                    images of a board -- four quarter turns, each with or without a mirror -- keyed by the image
+                    with the smallest key, and every row learns from all eight images: up to 8x fewer rows for the
+                    same experience, so `freeze_load` binds that much later.  `fused_rollout`, `play_rollout`,
+                    `q_values`, statistics, growth, freezing, checkpoints and `merge_from` work as without it;
+                    everything the caller sees (actions, `q_values`, the episode log) is in the env's own frame.
+                    `export_rows` / `export_dict` return the CANONICAL states only (one per orbit).  The 4-call API
+                    (`choose_action`, `update_q_value`) and `deterministic_rollout` raise ValueError; a folded
+                    checkpoint loads only into a folded agent (and a plain one only into a plain agent).
     row_cache       `choose_action` / `update_q_value` hand the row an env read as next_state on to
                     its next call through a device buffer of 32 B per env (q2048_*_cached: what the
                     fused rollout carries in registers), so an update reads one scattered row instead
@@ -369,9 +378,12 @@ class BatchedQLearningAgent:
                  strict_td: bool = False, board_size: int = 4, placement="auto", row_cache: bool = True,
                  initial_capacity_log2="auto", max_capacity_log2: int | None = None, load_limit: float = 0.35,
                  growth_step_log2: int = 2, prefetch_growth: bool = True, async_growth: bool = True,
-                 verify_growth: bool = False, freeze_load: "float | None" = 0.5):
+                 verify_growth: bool = False, freeze_load: "float | None" = 0.5, symmetric: bool = False):
         self.device = _require_gpu(device)
         self._L = N.lib_for(self.device)
+        self.symmetric = bool(symmetric)
+        if self.symmetric and board_size != 4:
+            raise ValueError("symmetric=True (Q2048_FLAG_SYMMETRIC) folds 4x4 boards only")
         self.on_gpu = self.device.type == "cuda"
         if action_space != 4:
             raise ValueError("the 2048 action space has 4 actions")
@@ -429,6 +441,8 @@ class BatchedQLearningAgent:
         self.capacity_log2 = int(capacity_log2)
         self.seed, self.env_id0 = int(seed), int(env_id0)
         self.flags = (N.FLAG_INDEPENDENT if independent else 0) | (N.FLAG_TD_CAS if strict_td else 0)
+        # (Q2048_FLAG_SYMMETRIC is not in `flags`: only the entry points that take it get it, `_sym`)
+        self._sym = N.FLAG_SYMMETRIC if self.symmetric else 0
         self.experiment_bits = 0  # unstable tuning bits OR-ed into fused_rollout's flags
         self.ctr = 0  # choose_action calls so far = counter word of the step draws
         try:
@@ -531,6 +545,7 @@ class BatchedQLearningAgent:
 
     def choose_action(self, boards: torch.Tensor) -> torch.Tensor:
         """choose_action (:34-38) for B states -> uint8 actions [B]."""
+        self._refuse_symmetric("choose_action")
         boards = self._boards(boards)
         B = boards.shape[0]
         actions = torch.empty(B, dtype=torch.uint8, device=self.device)
@@ -545,6 +560,7 @@ class BatchedQLearningAgent:
 
     def update_q_value(self, boards, actions, reward, next_boards, done) -> None:
         """update_q_value (:40-43) for B transitions."""
+        self._refuse_symmetric("update_q_value")
         boards, next_boards = self._boards(boards), self._boards(next_boards)
         B = boards.shape[0]
         actions = self._vec(actions, torch.uint8, B, "actions")
@@ -563,19 +579,38 @@ class BatchedQLearningAgent:
                  return_found: bool = False):
         """q_table[state] for B states -> float32 [B, 4] (zeros where absent).  In independent
         mode board i is looked up in the rows of env `env_id0 + i`, or, when `env_id` is given,
-        every board in the rows of that one env."""
+        every board in the rows of that one env.  A symmetric agent looks up the row of the board's canonical
+        image and returns it in the board's own frame (q[a] is the value of action a ON THIS BOARD)."""
         boards = self._boards(boards)
         B = boards.shape[0]
         q = torch.empty((B, 4), dtype=torch.float32, device=self.device)
         found = torch.empty(B, dtype=torch.uint8, device=self.device) if return_found else None
         if B == 0:                               # (an empty batch has no data pointers to hand over)
             return (q, found.bool()) if return_found else q
-        flags = self.flags | (N.FLAG_SINGLE_ENV if env_id is not None else 0)
+        flags = self.flags | self._sym | (N.FLAG_SINGLE_ENV if env_id is not None else 0)
         N.check(self._L.q2048_q_lookup(
             _ptr(self.table), self.capacity_log2, _ptr(boards), B, self.board_size,
             self.env_id0 if env_id is None else int(env_id), flags, _ptr(q), _ptr(found),
             _ptr(self.status), _stream(self.device)), "q_lookup")
         return (q, found.bool()) if return_found else q
+
+    def canonicalize(self, boards: torch.Tensor):
+        """q2048_canonicalize for B 4x4 boards -> (canonical images uint8 [B, 16], g uint8 [B]): the image a
+        symmetric table is keyed by, and which of the eight it is (include/q2048.h, Q2048_FLAG_SYMMETRIC)."""
+        if self.board_size != 4:
+            raise ValueError("canonical images are defined for 4x4 boards")
+        boards = self._boards(boards)
+        B = boards.shape[0]
+        out, g = torch.empty_like(boards), torch.empty(B, dtype=torch.uint8, device=self.device)
+        if B:
+            N.check(self._L.q2048_canonicalize(_ptr(boards), B, 4, _ptr(out), _ptr(g), _stream(self.device)),
+                    "canonicalize")
+        return out, g
+
+    def _refuse_symmetric(self, what: str) -> None:
+        if self.symmetric:
+            raise ValueError(f"{what} does not take Q2048_FLAG_SYMMETRIC (symmetric=True): a folded table learns "
+                             "through fused_rollout and is read through q_values / play_rollout")
 
     # -- throughput entry point ----------------------------------------------------------
     def fused_rollout(self, env: BatchedGame2048Env, steps: int, episode_log: "EpisodeLog | None" = None,
@@ -616,7 +651,7 @@ class BatchedQLearningAgent:
             _ptr(env.boards), _ptr(env.aux), _ptr(self.table), self.capacity_log2, env.num_envs,
             self.board_size, int(steps), float(self.epsilon), float(self.lr), float(self.gamma), self.seed,
             self.env_id0, self.ctr & 0xFFFFFFFF,
-            flags | self.experiment_bits | env.env_flags |
+            flags | self._sym | self.experiment_bits | env.env_flags |
             (N.FLAG_PLAY_ONLY if play_only else 0) | (0 if learn else N.FLAG_NO_LEARN),
             _ptr(self.stats_i), _ptr(self.stats_f), _ptr(self.status), C.byref(opts), _stream(self.device)),
             "fused_rollout")
@@ -644,7 +679,7 @@ class BatchedQLearningAgent:
         N.check(self._L.q2048_play_rollout(
             _ptr(env.boards), _ptr(env.aux), _ptr(self.table), self.capacity_log2, env.num_envs, self.board_size,
             int(steps), float(epsilon), env.seed, env.env_id0, env.ctr & 0xFFFFFFFF,
-            (self.flags & N.FLAG_INDEPENDENT) | env.env_flags, _ptr(si), _ptr(sf), _ptr(self.status),
+            (self.flags & N.FLAG_INDEPENDENT) | self._sym | env.env_flags, _ptr(si), _ptr(sf), _ptr(self.status),
             _stream(self.device)), "play_rollout")
         env.ctr += int(steps)
 
@@ -676,6 +711,7 @@ class BatchedQLearningAgent:
         transitions in env order -- bit for bit, at any B (tested at 1 048 576 boards).  Six launches
         per step, 7.2e9 env-steps/s at 1 Mi boards: `fused_rollout` is the fast path, this one is
         the yard-stick."""
+        self._refuse_symmetric("deterministic_rollout")
         if env.device != self.device or env.board_size != self.board_size:
             raise ValueError("env and agent do not match")
         if (env.seed, env.env_id0, env.ctr) != (self.seed, self.env_id0, self.ctr):
@@ -1034,7 +1070,8 @@ class BatchedQLearningAgent:
 
     def export_dict(self) -> dict:
         """The table in the reference's form: {tuple of 4 tuples of raw tile values ->
-        np.float64[4]} (Agent/main.py:16,82).  Shared-table mode only."""
+        np.float64[4]} (Agent/main.py:16,82).  Shared-table mode only.  A symmetric agent's table holds the
+        CANONICAL states only -- one board per orbit of the eight symmetries, its row in that board's frame."""
         if self.flags & N.FLAG_INDEPENDENT:
             raise ValueError("salted keys of independent mode do not decode to boards")
         keys, q = self.export_rows()
@@ -1066,6 +1103,8 @@ class BatchedQLearningAgent:
               "flags": self.flags, "ctr": self.ctr, "seed": self.seed, "env_id0": self.env_id0,
               "lr": self.lr, "gamma": self.gamma, "schedule": dict(vars(self.schedule)),
               "stats_i": self.stats_i.to("cpu", copy=True), "stats_f": self.stats_f.to("cpu", copy=True)}
+        if self.symmetric:
+            sd["symmetric"] = True                # (a checkpoint without the field is a plain table)
         if compact:
             sd["keys"], sd["q"] = self.export_rows()
         else:
@@ -1080,6 +1119,10 @@ class BatchedQLearningAgent:
     def load_state_dict(self, sd: dict) -> None:
         if sd["board_size"] != self.board_size:
             raise ValueError("checkpoint was taken with another board size")
+        if bool(sd.get("symmetric", False)) != self.symmetric:
+            raise ValueError("a symmetry-folded table (symmetric=True) and a plain one do not load into each other: "
+                             f"the checkpoint is {'folded' if sd.get('symmetric') else 'plain'}, this agent is "
+                             f"{'folded' if self.symmetric else 'plain'}")
         self.ctr, self.seed, self.env_id0 = int(sd["ctr"]), int(sd["seed"]), int(sd["env_id0"])
         self.lr, self.gamma, self.flags = sd["lr"], sd["gamma"], int(sd["flags"])
         vars(self.schedule).update(sd["schedule"])
@@ -1173,6 +1216,8 @@ class BatchedQLearningAgent:
             raise ValueError("the two agents live on different devices")
         if other.board_size != self.board_size:
             raise ValueError("the two agents have different board sizes")
+        if other.symmetric != self.symmetric:
+            raise ValueError("a symmetry-folded table (symmetric=True) and a plain one cannot be merged")
         if mode not in self._MERGE_MODES:
             raise ValueError(f"mode must be one of {sorted(self._MERGE_MODES)}")
         weight = float(weight)

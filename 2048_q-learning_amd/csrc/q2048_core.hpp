@@ -544,6 +544,55 @@ Q_HD Board unpack_key(uint64_t key) {
                unpack_row((uint32_t)(key >> 32)), unpack_row((uint32_t)(key >> 48))};
 }
 
+// ------------------------------------------------------------------------------------------
+// SYMMETRY FOLDING (include/q2048.h, Q2048_FLAG_SYMMETRIC): one table row for the eight mirror images of a
+// board.  The images of b, in numpy terms:  g = 0..3: np.rot90(b, g);  g = 4..7: np.rot90(np.fliplr(b), g - 4).
+// With T = transpose, H = np.fliplr, V = np.flipud these are
+//   g:  0 b    1 V(T b)    2 V(H b)    3 H(T b)    4 H b    5 T b    6 V b    7 V(H(T b))
+// All of it works on the packed key (cell 4r + c in nibble 4r + c: a row is 16 bits): shifts and masks, no
+// memory access.  The canonical image is the one with the smallest key; on a tie the smallest g.
+// ------------------------------------------------------------------------------------------
+Q_HD uint64_t key_flip_h(uint64_t k) {          // np.fliplr: the four nibbles of every row reversed
+  k = ((k & 0x0f0f0f0f0f0f0f0full) << 4) | ((k >> 4) & 0x0f0f0f0f0f0f0f0full);
+  return ((k & 0x00ff00ff00ff00ffull) << 8) | ((k >> 8) & 0x00ff00ff00ff00ffull);
+}
+Q_HD uint64_t key_flip_v(uint64_t k) {          // np.flipud: the four rows reversed
+  k = ((k & 0x0000ffff0000ffffull) << 16) | ((k >> 16) & 0x0000ffff0000ffffull);
+  return (k << 32) | (k >> 32);
+}
+Q_HD uint64_t key_transpose(uint64_t k) {       // nibble (r, c) <-> (c, r): 2x2 blocks of nibbles, then of bytes
+  const uint64_t a = (k & 0xf0f00f0ff0f00f0full) | ((k & 0x0000f0f00000f0f0ull) << 12) | ((k & 0x0f0f00000f0f0000ull) >> 12);
+  return (a & 0xff00ff0000ff00ffull) | ((a & 0x00ff00ff00000000ull) >> 24) | ((a & 0x00000000ff00ff00ull) << 24);
+}
+struct Canon { uint64_t key; uint32_t g; };     // the canonical image's key and which image it is
+Q_HD Canon canonical_key(uint64_t k) {
+  const uint64_t t = key_transpose(k), hk = key_flip_h(k), ht = key_flip_h(t);
+  const uint64_t cand[8] = {k, key_flip_v(t), key_flip_v(hk), ht, hk, t, key_flip_v(k), key_flip_v(ht)};
+  Canon c{k, 0u};
+#pragma unroll
+  for (uint32_t g = 1; g < 8u; ++g) {           // ascending g, strict <: the smallest g wins a tie
+    const bool lt = cand[g] < c.key;
+    c.key = lt ? cand[g] : c.key;
+    c.g = lt ? g : c.g;
+  }
+  return c;
+}
+// image g of a board in bytes (what q2048_canonicalize writes: tiles above 2^15 keep their value)
+Q_HD Board board_image(const Board& b, uint32_t g) {
+  const Board t = transpose(b);
+  Board o = (g & 1u) ? t : b;                                        // g odd: the images of T b
+  if ((0x9cu >> g) & 1u)                                             // H for g in {2, 3, 4, 7}
+    o = Board{__builtin_bswap32(o.r0), __builtin_bswap32(o.r1), __builtin_bswap32(o.r2), __builtin_bswap32(o.r3)};
+  if ((0xc6u >> g) & 1u) o = Board{o.r3, o.r2, o.r1, o.r0};          // V for g in {1, 2, 6, 7}
+  return o;
+}
+// pi_g: move(image_g(b), pi_g(a)) == image_g(move(b, a)) with a = 0 left, 1 up, 2 right, 3 down -- a quarter
+// turn counter-clockwise takes "up" to "left", the mirror swaps left and right.  A row stored in the canonical
+// frame is read in the env's frame as Q_env[a] = Q_canon[pi_g(a)].
+Q_HD int sym_action(uint32_t g, int a) {
+  return (int)((g < 4u ? (uint32_t)a - g : 2u - (uint32_t)a - g) & 3u);
+}
+
 Q_HD uint64_t mix64(uint64_t h) {
   h *= 0x9E3779B97F4A7C15ull;
   h ^= h >> 29;

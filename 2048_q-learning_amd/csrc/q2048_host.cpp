@@ -76,6 +76,26 @@ inline Geo<5>::Key state_key(const Board5& b, u64 salt, uint32_t*) {
   const Key5 k = pack_key(b);
   return Geo<5>::Key{k.k0 ^ (salt & 0x7fffffffffffffffull), k.k1 ^ (mix64(salt) & 0x3fffffffffffffffull)};
 }
+// Q2048_FLAG_SYMMETRIC (4x4): the key of the board's canonical image, salted AFTER canonicalisation; g = which image
+template <bool SYM, class BoardT>
+inline auto state_key_as(const BoardT& b, u64 salt, uint32_t* status, uint32_t& g) {
+  if constexpr (SYM) {
+    bool ov;
+    const Canon c = canonical_key(pack_key(b, ov));
+    if (ov) status_or(status, Q2048_STATUS_TILE_OVERFLOW);
+    g = c.g;
+    const u64 k = c.key ^ salt;
+    return Geo<4>::Key{k == 0ull ? 1ull : k};
+  } else {
+    g = 0u;
+    return state_key(b, salt, status);
+  }
+}
+template <int N>
+inline typename Geo<N>::Key state_key_sym(bool sym, const typename Geo<N>::BoardT& b, u64 salt, uint32_t* status, uint32_t& g) {
+  if constexpr (N == 4) { if (sym) return state_key_as<true>(b, salt, status, g); }
+  return state_key_as<false>(b, salt, status, g);
+}
 inline bool key_eq(const Geo<4>::Key& a, const Geo<4>::Key& b) { return a.k0 == b.k0; }
 inline bool key_eq(const Geo<5>::Key& a, const Geo<5>::Key& b) { return a.k0 == b.k0 && a.k1 == b.k1; }
 inline u64 key_hash(const Geo<4>::Key& k) { return mix64(k.k0); }
@@ -95,6 +115,10 @@ inline uint32_t probe_limit(u64 mask, uint32_t maxp) { return mask >= (u64)maxp 
 struct Row { float q0, q1, q2, q3; };
 inline float row_get(const Row& r, int a) { return a == 0 ? r.q0 : a == 1 ? r.q1 : a == 2 ? r.q2 : r.q3; }
 inline void row_set(Row& r, int a, float v) { (a == 0 ? r.q0 : a == 1 ? r.q1 : a == 2 ? r.q2 : r.q3) = v; }
+// a row stored in the canonical frame, read in the frame of the env whose board is image g's pre-image
+inline Row row_env(const Row& r, uint32_t g) {
+  return Row{row_get(r, sym_action(g, 0)), row_get(r, sym_action(g, 1)), row_get(r, sym_action(g, 2)), row_get(r, sym_action(g, 3))};
+}
 
 inline u64 ld_u64(const uint64_t* p) { return __atomic_load_n(p, __ATOMIC_ACQUIRE); }
 inline float ld_f32(const float* p) {
@@ -332,8 +356,9 @@ constexpr uint32_t kAbiFlags = Q2048_FLAG_INDEPENDENT | Q2048_FLAG_SINGLE_ENV | 
                                Q2048_FLAG_NO_NEW_ROWS | Q2048_FLAG_LINE_SUMMARY;   // (the last one: 4x4 accepted, not used --
                                                                                    // slot by slot, same results; 5x5 with a side
                                                                                    // array: used, fused_rollout_n)
-inline int check_flags(uint32_t flags, uint32_t refused = 0u) {
-  return ((flags & ~kAbiFlags) || (flags & refused)) ? Q2048_ERR_FLAGS : Q2048_OK;
+// (`also`: Q2048_FLAG_SYMMETRIC, for the entry points that take it -- the fused rollouts, the player, q_lookup)
+inline int check_flags(uint32_t flags, uint32_t refused = 0u, uint32_t also = 0u) {
+  return ((flags & ~(kAbiFlags | also)) || (flags & refused)) ? Q2048_ERR_FLAGS : Q2048_OK;
 }
 inline int env_bits(uint32_t flags) {
   return ((flags & Q2048_FLAG_ENV_DQN) ? kEnvDqn : 0) | ((flags & Q2048_FLAG_RESET_SHAPING) ? kEnvResetShaping : 0);
@@ -527,6 +552,7 @@ void q_update_impl_n(q2048_slot* table, u64 mask, const uint8_t* s, const uint8_
 template <int N>
 void q_lookup_impl_n(const q2048_slot* table, u64 mask, const uint8_t* boards, int64_t B, uint64_t env_id0,
                      uint32_t flags, float* q_out, uint8_t* found, uint32_t* status) {
+  const bool sym = (flags & Q2048_FLAG_SYMMETRIC) != 0;
   parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
     for (int64_t i = lo; i < hi; ++i) {
       typename Geo<N>::BoardT b;
@@ -534,7 +560,9 @@ void q_lookup_impl_n(const q2048_slot* table, u64 mask, const uint8_t* boards, i
       const uint64_t id = (flags & Q2048_FLAG_SINGLE_ENV) ? env_id0 : env_id0 + (uint64_t)i;
       const u64 salt = (flags & Q2048_FLAG_INDEPENDENT) ? lane_salt(id) : 0ull;
       Row r;
-      const int64_t slot = probe_find(table, mask, state_key(b, salt, status), r, kMaxProbe);
+      uint32_t g;
+      const int64_t slot = probe_find(table, mask, state_key_sym<N>(sym, b, salt, status, g), r, kMaxProbe);
+      if (sym) r = row_env(r, g);                      // q_out is in the env's frame
       q_out[4 * i] = r.q0; q_out[4 * i + 1] = r.q1; q_out[4 * i + 2] = r.q2; q_out[4 * i + 3] = r.q3;
       if (found != nullptr) found[i] = slot >= 0;
     }
@@ -559,6 +587,7 @@ void fused_rollout_n(uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mas
   struct Lane {
     BoardT b; Aux a; Key key_s, key_n; Row q; int64_t slot_s; u64 salt; uint64_t id; double reward_sum;
     StepOut o; int act; bool explored, same; DrawPrep prep;
+    uint32_t g_s, g_n;      // Q2048_FLAG_SYMMETRIC: which image of the board the canonical one is (else 0)
   };
   const uint64_t eps_t = eps_threshold(eps);     // the step's epsilon test and draws as the device kernel does them
   const ImageLuts lut{&g_lut_image};
@@ -566,6 +595,9 @@ void fused_rollout_n(uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mas
   const bool play_only = (flags & Q2048_FLAG_PLAY_ONLY) != 0, no_learn = (flags & Q2048_FLAG_NO_LEARN) != 0;
   const bool learns = !play_only && !no_learn, frozen = (flags & Q2048_FLAG_NO_NEW_ROWS) != 0;
   const bool creates = learns && !frozen, cas = (flags & Q2048_FLAG_TD_CAS) != 0;
+  // Q2048_FLAG_SYMMETRIC: keys, the carried row, the visit row and every table index are in the canonical frame;
+  // only the four values handed to the epsilon-greedy choice and the action's index into the row are permuted
+  const bool sym = N == 4 && !play_only && (flags & Q2048_FLAG_SYMMETRIC) != 0;
   // 5x5, key set closed, Q2048_FLAG_LINE_SUMMARY and a side array: the lookups are decided from it, as on the device
   const bool summary = N == 5 && learns && frozen && (flags & Q2048_FLAG_LINE_SUMMARY) != 0 && side != nullptr;
   const int T = threads_for(B);
@@ -588,7 +620,7 @@ void fused_rollout_n(uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mas
         L.salt = (flags & Q2048_FLAG_INDEPENDENT) ? lane_salt(L.id) : 0ull;
         load_board(boards, i, L.b);
         L.a = ld_aux(aux, i);
-        L.key_s = state_key(L.b, L.salt, status);
+        L.key_s = state_key_sym<N>(sym, L.b, L.salt, status, L.g_s);
         // the row of the current state: read when the state is reached and carried (as the kernel carries it in
         // registers); created at its first update (the defaultdict creates q_table[state] at :43)
         L.q = Row{0.f, 0.f, 0.f, 0.f};
@@ -603,16 +635,19 @@ void fused_rollout_n(uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mas
           const Draws x = draws_at(L.prep, ctr0 + (uint32_t)t);
           Draws y{0u, 0u, 0u, 0u};
           if (env & kEnvDqn) y = draws(seed, L.id, ctr0 + (uint32_t)t, kStreamOver);
-          L.act = eps_greedy_at(eps_t, x.x0, x.x1, L.q.q0, L.q.q1, L.q.q2, L.q.q3, L.explored);  // :92
+          const Row qe = sym ? row_env(L.q, L.g_s) : L.q;
+          L.act = eps_greedy_at(eps_t, x.x0, x.x1, qe.q0, qe.q1, qe.q2, qe.q3, L.explored);      // :92
           L.o = env_step_any(env, L.b, L.a, L.act, x.x2, x.x3, y.x0, y.x1, lut);                 // :93
-          L.key_n = state_key(L.b, L.salt, status);                                              // :94
+          L.key_n = state_key_sym<N>(sym, L.b, L.salt, status, L.g_n);                           // :94
+          // (symmetric: still "the move was invalid" -- a valid move adds a spawned tile, so the tile sum grows and
+          // s' can never lie in the orbit of s)
           L.same = key_eq(L.key_n, L.key_s);
           if (!L.same && !play_only) __builtin_prefetch(&table[key_hash(L.key_n) & mask], 1, 1);
         }
         for (int l = 0; l < n; ++l) {                    // the table: q_table[next_state], the TD write, the reset
           Lane& L = lane[l];
           const StepOut& o = L.o;
-          const int act = L.act;
+          const int act = sym ? sym_action(L.g_s, L.act) : L.act;   // the action's index into the (canonical) row
           bool ins_s = false, ins_n = false;
           if (L.slot_s < 0 && L.slot_s != kNoSlot && creates) L.slot_s = probe_insert(table, mask, L.key_s, (u64)~L.slot_s, ins_s);
           Row qn = L.q;                                                                          // q_table[next_state] (:41)
@@ -645,7 +680,8 @@ void fused_rollout_n(uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mas
                 Row ql = L.q;
                 if ((updated || (frozen && learns)) && !no_learn) row_set(ql, act, nq);
                 q2048_episode rec;
-                rec.env_id = L.id; rec.episode = L.a.episode; rec.action = (uint8_t)act;
+                if (sym) ql = row_env(ql, L.g_s);             // the log is the env's view
+                rec.env_id = L.id; rec.episode = L.a.episode; rec.action = (uint8_t)L.act;
                 rec.max_log2 = o.max_log2; rec.steps_lo = (uint16_t)(ctr0 + (uint32_t)t);
                 rec.reward = o.reward; rec.total_return = L.a.ep_return; rec.score = L.a.score;
                 rec.q[0] = ql.q0; rec.q[1] = ql.q1; rec.q[2] = ql.q2; rec.q[3] = ql.q3;
@@ -654,14 +690,14 @@ void fused_rollout_n(uint8_t* boards, q2048_aux* aux, q2048_slot* table, u64 mas
               }
             }
             begin_episode(L.b, L.a, seed, L.id, (env & kEnvResetShaping) != 0);                  // :81
-            L.key_s = state_key(L.b, L.salt, status);
+            L.key_s = state_key_sym<N>(sym, L.b, L.salt, status, L.g_s);
             L.q = Row{0.f, 0.f, 0.f, 0.f};
             L.slot_s = play_only ? kNoSlot : find(L.key_s, L.q);
           } else if (L.same) {           // invalid move: same state, its row just changed (:100)
             if ((updated || (frozen && learns)) && !no_learn) row_set(L.q, act, nq);
             else if (!updated) L.slot_s = kNoSlot;
           } else {
-            L.key_s = L.key_n; L.slot_s = slot_n; L.q = qn;                                      // :100
+            L.key_s = L.key_n; L.slot_s = slot_n; L.q = qn; L.g_s = L.g_n;                       // :100
           }
         }
       }
@@ -690,6 +726,7 @@ void play_rollout_n(uint8_t* boards, q2048_aux* aux, const q2048_slot* table, u6
   const uint64_t eps_t = eps_threshold(eps);
   const ImageLuts lut{&g_lut_image};
   const int env = env_bits(flags);
+  const bool sym = (flags & Q2048_FLAG_SYMMETRIC) != 0;
   const int T = threads_for(B);
   std::vector<Stats> parts((size_t)T);
   Stats* sp = parts.data();
@@ -708,7 +745,9 @@ void play_rollout_n(uint8_t* boards, q2048_aux* aux, const q2048_slot* table, u6
         Draws y{0u, 0u, 0u, 0u};
         if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
         Row q;
-        probe_find(table, mask, state_key(b, salt, status), q, kMaxProbe);
+        uint32_t g;
+        probe_find(table, mask, state_key_sym<N>(sym, b, salt, status, g), q, kMaxProbe);
+        if (sym) q = row_env(q, g);                    // the legal mask and the tie order are the env's
         bool explored;
         const int act = play_action(legal_mask(b), q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
         const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
@@ -971,7 +1010,8 @@ int q2048_q_update(q2048_slot* table, int cap_log2, const uint8_t* boards_s, con
 int q2048_q_lookup(const q2048_slot* table, int cap_log2, const uint8_t* boards, int64_t B, int n, uint64_t env_id0,
                    uint32_t flags, float* q_out, uint8_t* found, uint32_t* status, void*) {
   if (int e = check_batch(B, n)) return e;
-  if (int e = check_flags(flags)) return e;
+  if (int e = check_flags(flags, 0u, Q2048_FLAG_SYMMETRIC)) return e;
+  if (n == 5 && (flags & Q2048_FLAG_SYMMETRIC)) return Q2048_ERR_UNSUPPORTED;
   if (int e = check_table(table, cap_log2)) return e;
   if (!boards || !q_out || !status) return Q2048_ERR_NULL;
   if (!aligned16(boards) || !aligned16(q_out)) return Q2048_ERR_ALIGN;
@@ -993,7 +1033,8 @@ int q2048_fused_rollout_opts(uint8_t* boards, q2048_aux* aux, q2048_slot* table,
     std::memcpy(&o, opts, opts->size);
   }
   if (int e = check_batch(B, n)) return e;
-  if (int e = check_flags(flags)) return e;
+  if (int e = check_flags(flags, 0u, Q2048_FLAG_SYMMETRIC)) return e;
+  if (n == 5 && (flags & Q2048_FLAG_SYMMETRIC)) return Q2048_ERR_UNSUPPORTED;
   if (o.log != nullptr && (o.log_count == nullptr || o.log_capacity < 0)) return Q2048_ERR_NULL;
   if (o.log != nullptr && !aligned16(o.log)) return Q2048_ERR_ALIGN;
   if (o.row_cache != nullptr && !aligned16(o.row_cache)) return Q2048_ERR_ALIGN;
@@ -1024,8 +1065,10 @@ int q2048_play_rollout(uint8_t* boards, q2048_aux* aux, const q2048_slot* table,
                        int64_t steps, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
                        int64_t* stats_i, double* stats_f, uint32_t* status, void*) {
   if (int e = check_batch(B, n)) return e;
-  if (int e = check_flags(flags, kAbiFlags & ~(Q2048_FLAG_INDEPENDENT | Q2048_FLAG_ENV_DQN | Q2048_FLAG_RESET_SHAPING)))
+  if (int e = check_flags(flags, kAbiFlags & ~(Q2048_FLAG_INDEPENDENT | Q2048_FLAG_ENV_DQN | Q2048_FLAG_RESET_SHAPING),
+                          Q2048_FLAG_SYMMETRIC))
     return e;
+  if (n == 5 && (flags & Q2048_FLAG_SYMMETRIC)) return Q2048_ERR_UNSUPPORTED;
   if (int e = check_table(table, cap_log2)) return e;
   if (!boards || !aux || !status) return Q2048_ERR_NULL;
   if (!aligned16(boards) || !aligned16(aux)) return Q2048_ERR_ALIGN;
@@ -1263,6 +1306,25 @@ int q2048_table_merge(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, 
     bits |= p.bits;
   }
   if (bits && status != nullptr) status_or(status, bits);
+  return Q2048_OK;
+}
+
+int q2048_canonicalize(const uint8_t* boards, int64_t B, int n, uint8_t* boards_out, uint8_t* sym_out, void*) {
+  if (int e = check_batch(B, n)) return e;
+  if (n != 4) return Q2048_ERR_UNSUPPORTED;
+  if (boards == nullptr) return Q2048_ERR_NULL;
+  if (!aligned16(boards) || !aligned16(boards_out)) return Q2048_ERR_ALIGN;
+  if (B == 0) return Q2048_OK;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Board b;
+      load_board(boards, i, b);
+      bool ov;
+      const uint32_t g = canonical_key(pack_key(b, ov)).g;
+      if (boards_out != nullptr) store_board(boards_out, i, board_image(b, g));
+      if (sym_out != nullptr) sym_out[i] = (uint8_t)g;
+    }
+  });
   return Q2048_OK;
 }
 

@@ -188,6 +188,23 @@ __device__ __forceinline__ Geo<5>::Key state_key(const Board5& b, u64 salt, uint
   return Geo<5>::Key{k.k0 ^ (salt & 0x7fffffffffffffffull),
                      k.k1 ^ (mix64(salt) & 0x3fffffffffffffffull)};
 }
+// Q2048_FLAG_SYMMETRIC (SYM, 4x4 only): the key of the board's canonical image -- the smallest of the eight mirror
+// images' keys, q2048_core.hpp -- salted AFTER canonicalisation; g = which image it is (0 without SYM).  Registers
+// only: no LDS, no load, no atomic.
+template <bool SYM, class BoardT>
+__device__ __forceinline__ auto state_key_as(const BoardT& b, u64 salt, uint32_t* status, uint32_t& g) {
+  if constexpr (SYM) {
+    bool ov;
+    const Canon c = canonical_key(pack_key(b, ov));
+    if (ov) atomicOr(status, Q2048_STATUS_TILE_OVERFLOW);
+    g = c.g;
+    const u64 k = c.key ^ salt;
+    return Geo<4>::Key{k == 0ull ? 1ull : k};
+  } else {
+    g = 0u;
+    return state_key(b, salt, status);
+  }
+}
 __device__ __forceinline__ bool key_eq(const Geo<4>::Key& a, const Geo<4>::Key& b) { return a.k0 == b.k0; }
 __device__ __forceinline__ bool key_eq(const Geo<5>::Key& a, const Geo<5>::Key& b) {
   return a.k0 == b.k0 && a.k1 == b.k1;
@@ -242,6 +259,12 @@ __device__ __forceinline__ float row_get(const Row& r, int a) {
 __device__ __forceinline__ void row_set(Row& r, int a, float v) {
   r.q0 = a == 0 ? v : r.q0; r.q1 = a == 1 ? v : r.q1;
   r.q2 = a == 2 ? v : r.q2; r.q3 = a == 3 ? v : r.q3;
+}
+// a row stored in the canonical frame, read in the frame of the env whose board has the canonical image g:
+// Q_env[a] = Q_canon[pi_g(a)] (Q2048_FLAG_SYMMETRIC)
+__device__ __forceinline__ Row row_env(const Row& r, uint32_t g) {
+  return Row{row_get(r, sym_action(g, 0)), row_get(r, sym_action(g, 1)), row_get(r, sym_action(g, 2)),
+             row_get(r, sym_action(g, 3))};
 }
 
 // `confirm`: the slot's first key word equals key.k0 (this lane just set it, or found it so).
@@ -892,6 +915,23 @@ __global__ __launch_bounds__(kBlock) void k_legal_moves(const uint8_t* boards, i
 
 // one-hot encoder (Dqn8TestNOPERCNN.py:271-277): thread = (board, channel, row) -> 4 outputs;
 // the 1 KiB (f32) / 512 B (bf16) image of a board is written by 64 consecutive threads
+// q2048_canonicalize: the canonical image of every board and which of the eight images it is (q2048_core.hpp).
+// One board per lane, one 16-byte load and at most one 16-byte store: in place is safe.
+__global__ __launch_bounds__(kBlock) void k_canonicalize(const uint8_t* boards, int64_t B, uint8_t* boards_out,
+                                                         uint8_t* sym_out) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  const uint4 v = reinterpret_cast<const uint4*>(boards)[i];
+  const Board b{v.x, v.y, v.z, v.w};
+  bool ov;
+  const uint32_t g = canonical_key(pack_key(b, ov)).g;
+  if (boards_out != nullptr) {
+    const Board c = board_image(b, g);
+    reinterpret_cast<uint4*>(boards_out)[i] = make_uint4(c.r0, c.r1, c.r2, c.r3);
+  }
+  if (sym_out != nullptr) sym_out[i] = (uint8_t)g;
+}
+
 template <bool BF16>
 __global__ __launch_bounds__(kBlock) void k_encode_onehot(const uint8_t* boards, int64_t B, void* out) {
   const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -1040,7 +1080,7 @@ __global__ __launch_bounds__(kBlock) void k_q_choose(const q2048_slot* table, u6
   actions[i] = (uint8_t)act;
 }
 
-template <int N>
+template <int N, bool SYM = false>
 __global__ __launch_bounds__(kBlock) void k_q_lookup(const q2048_slot* table, u64 mask,
                                                      const uint8_t* boards, int64_t B, uint64_t env_id0,
                                                      uint32_t flags, float* q_out, uint8_t* found,
@@ -1053,7 +1093,9 @@ __global__ __launch_bounds__(kBlock) void k_q_lookup(const q2048_slot* table, u6
   const u64 salt = (flags & Q2048_FLAG_INDEPENDENT) ? lane_salt(id) : 0ull;
   Row r;
   bool made;
-  const int64_t slot = probe_find(table, mask, state_key(b, salt, status), r, made, kMaxProbe);
+  uint32_t g;
+  const int64_t slot = probe_find(table, mask, state_key_as<SYM>(b, salt, status, g), r, made, kMaxProbe);
+  if constexpr (SYM) r = row_env(r, g);                   // q_out is in the env's frame
   reinterpret_cast<float4*>(q_out)[i] = make_float4(r.q0, r.q1, r.q2, r.q3);
   if (found != nullptr) found[i] = slot >= 0;
 }
@@ -1171,6 +1213,12 @@ __global__ __launch_bounds__(kUpdateBlock) void k_q_update(q2048_slot* table, u6
 // state without a row reads as zeros and its update is dropped and counted.
 constexpr int kModeLearn = 0, kModeCas = 1, kModeEval = 2, kModeFrozen = 4, kModeSummary = 8;   // (kModeSummary: with kModeFrozen;
                                                         // 4x4: summaries in the slots, 5x5: in the side array `side`)
+// kModeSym (a bit, with any of the above; N = 4 only): Q2048_FLAG_SYMMETRIC -- the table is addressed by the canonical
+// image of the board.  Keys, the carried row `q`, the deferred-write mask `pend`, the visit row and the row cache stay
+// in the canonical frame (they only ever see a key, so the claim pipeline, the cache, the closed key set and the line
+// summaries work unchanged); only the four values handed to the epsilon-greedy choice and the action's index into the
+// row are permuted.  Without the bit every line it adds compiles away.
+constexpr int kModeSym = 16;
 // Lanes per workgroup of the fused rollout: 512 for batches that fill the chip more than twice over at that
 // size (>= 786 432 boards), 256 below.  Nine alternating pairs of the driver's command at 1 Mi boards: 47.2 us
 // per step against 48.3 (8 of 9 pairs; 5x5: 64.4 against 66.4; profiles/r04_block512_*.txt) -- half as many
@@ -1226,7 +1274,9 @@ __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
     // Q2048_FLAG_NO_LEARN (MODE kModeEval): evaluation of a trained table -- rows are read
     // (epsilon-greedy over the stored values), nothing is created or written
     constexpr bool play_only = (ENV & kEnvPlayOnly) != 0;
-    constexpr bool no_learn = MODE == kModeEval;
+    constexpr bool no_learn = (MODE & ~kModeSym) == kModeEval;
+    constexpr bool sym = (MODE & kModeSym) != 0;
+    static_assert(!sym || (N == 4 && !play_only), "symmetry folding: 4x4 learners, evaluators and frozen tables");
     constexpr bool frozen = (MODE & kModeFrozen) != 0;
     constexpr bool summary = (MODE & kModeSummary) != 0;   // line summaries: Q2048_FLAG_LINE_SUMMARY
 #ifdef Q2048_EXPERIMENTS   // bits 8..11 write mode, 12 no row creation, 13 no next-state probe, 14 no deferral, 16..23 CAS attempts
@@ -1241,7 +1291,8 @@ __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
     constexpr int max_cas = kMaxCas;
 #endif
     Aux a = ld_aux(aux, i);
-    auto key_s = state_key(b, salt, status);
+    uint32_t g_s;           // which image of the board the canonical one is (0 unless `sym`)
+    auto key_s = state_key_as<sym>(b, salt, status, g_s);
     Row q{0.f, 0.f, 0.f, 0.f};
     bool made0 = false;
     // The row the launch starts in: what this env's last launch (or update_q_value) left in the row
@@ -1265,9 +1316,15 @@ __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
       Draws y{0u, 0u, 0u, 0u};
       if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
       bool explored;
-      const int act = eps_greedy_at(eps_t, x.x0, x.x1, q.q0, q.q1, q.q2, q.q3, explored);  // main.py:92
-      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);     // :93
-      const auto key_n = state_key(b, salt, status);                                   // :94
+      Row qe = q;                                       // the row as the env sees it: first maximum in ascending ENV action
+      if constexpr (sym) qe = row_env(q, g_s);
+      const int act_env = eps_greedy_at(eps_t, x.x0, x.x1, qe.q0, qe.q1, qe.q2, qe.q3, explored);  // main.py:92
+      const StepOut o = env_step_profile<ENV>(b, a, act_env, x.x2, x.x3, y.x0, y.x1, lut);         // :93
+      const int act = sym ? sym_action(g_s, act_env) : act_env;   // the action's index into the (canonical) row
+      uint32_t g_n;
+      const auto key_n = state_key_as<sym>(b, salt, status, g_n);                      // :94
+      // `same` still means "the move was invalid" under symmetry folding: a valid move adds a spawned tile, so the
+      // tile sum grows and s' can never lie in the orbit of s.
       const bool same = key_eq(key_n, key_s);
       // the row of s: claimed one step ago (in flight since), or now if s opened the episode/launch
       bool ins_s = false, ins_n = false;
@@ -1307,8 +1364,9 @@ __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
           if ((int64_t)at < log_cap) {
             Row ql = q;
             if ((updated || frozen) && !no_learn) row_set(ql, act, nq);   // the logged row is the live one (:96), post-update
+            if constexpr (sym) ql = row_env(ql, g_s);                     // (the log is the env's view)
             q2048_episode rec;
-            rec.env_id = id; rec.episode = a.episode; rec.action = (uint8_t)act;
+            rec.env_id = id; rec.episode = a.episode; rec.action = (uint8_t)act_env;
             rec.max_log2 = o.max_log2; rec.steps_lo = (uint16_t)(ctr0 + (uint32_t)t);
             rec.reward = o.reward; rec.total_return = a.ep_return; rec.score = a.score;
             rec.q[0] = ql.q0; rec.q[1] = ql.q1; rec.q[2] = ql.q2; rec.q[3] = ql.q3;
@@ -1317,7 +1375,7 @@ __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
           }
         }
         begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);                  // :81
-        key_s = state_key(b, salt, status);
+        key_s = state_key_as<sym>(b, salt, status, g_s);
         bool made = false;
         q = Row{0.f, 0.f, 0.f, 0.f};
         slot_s = play_only ? kNoSlot : probe_find_as<summary>(table, side, mask, key_s, q, made);
@@ -1326,7 +1384,7 @@ __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
         if ((updated || frozen) && !no_learn) row_set(q, act, nq);   // (evaluation: the stored row stays as it is)
         else if (!updated) slot_s = kNoSlot;             // dropped: do not retry the claim with a stale hint
       } else {
-        key_s = key_n; slot_s = slot_n; q = qn;                                        // :100
+        key_s = key_n; slot_s = slot_n; q = qn; g_s = g_n;                             // :100
         if (!x_noclaim) {
           bool made = false;
           slot_s = claim_issue(table, mask, slot_s, key_s, claim, made);
@@ -1384,7 +1442,7 @@ __global__ __launch_bounds__(BLOCK, Q2048_FUSED_WAVES(N)) void k_fused_rollout(
 // there is no row to carry: one lookup per step, and nothing is written but boards, aux and the statistics.
 // Every loop is bounded by `steps` and the probe limit; no lane waits for another; the table sees loads only.
 // ---------------------------------------------------------------------------------------------
-template <int N, int ENV>
+template <int N, int ENV, bool SYM = false>
 __global__ __launch_bounds__(kBlock) void k_play_rollout(
     uint8_t* boards, q2048_aux* aux, const q2048_slot* table, u64 mask, int64_t B, int steps, double eps,
     uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i, double* stats_f,
@@ -1413,7 +1471,9 @@ __global__ __launch_bounds__(kBlock) void k_play_rollout(
       if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
       Row q;
       bool made;
-      probe_find(table, mask, state_key(b, salt, status), q, made, kMaxProbe);
+      uint32_t g;
+      probe_find(table, mask, state_key_as<SYM>(b, salt, status, g), q, made, kMaxProbe);
+      if constexpr (SYM) q = row_env(q, g);             // the legal mask and the tie order are the env's
       bool explored;
       const int act = play_action(legal_mask(b), q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
       const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
@@ -2332,7 +2392,7 @@ inline int check_table(const void* table, int cap_log2) {
   hipLaunchKernelGGL((k_fused_rollout<NN, E, M, BLK>), dim3((unsigned)(((B) + (BLK) - 1) / (BLK))), dim3(BLK), 0, \
                      (hipStream_t)(stream), __VA_ARGS__)
 #define Q2048_LAUNCH_FUSED_CASE(E, M, n, B, stream, ...)                                          \
-  case (E) * 16 + (M):                                                                            \
+  case (E) * 32 + (M):                                                                            \
     if ((n) == 4) {                                                                               \
       if ((B) >= kFusedBigBatch) Q2048_LAUNCH_FUSED_ONE(4, E, M, kFusedBlockBig, B, stream, __VA_ARGS__);     \
       else Q2048_LAUNCH_FUSED_ONE(4, E, M, kFusedBlockSmall, B, stream, __VA_ARGS__);             \
@@ -2341,7 +2401,20 @@ inline int check_table(const void* table, int cap_log2) {
       else Q2048_LAUNCH_FUSED_ONE(5, E, M, kFusedBlockSmall, B, stream, __VA_ARGS__);             \
     }                                                                                             \
     break;
+// (symmetry folding is instantiated for N = 4 only: the entry point refuses n = 5 with the flag)
+#define Q2048_LAUNCH_FUSED_CASE4(E, M, n, B, stream, ...)                                         \
+  case (E) * 32 + (M):                                                                            \
+    if ((B) >= kFusedBigBatch) Q2048_LAUNCH_FUSED_ONE(4, E, M, kFusedBlockBig, B, stream, __VA_ARGS__);       \
+    else Q2048_LAUNCH_FUSED_ONE(4, E, M, kFusedBlockSmall, B, stream, __VA_ARGS__);               \
+    break;
 #define Q2048_LAUNCH_FUSED_ENV(E, n, B, stream, ...)                                              \
+  Q2048_LAUNCH_FUSED_CASE4(E, kModeSym + kModeLearn, n, B, stream, __VA_ARGS__)                   \
+  Q2048_LAUNCH_FUSED_CASE4(E, kModeSym + kModeCas, n, B, stream, __VA_ARGS__)                     \
+  Q2048_LAUNCH_FUSED_CASE4(E, kModeSym + kModeEval, n, B, stream, __VA_ARGS__)                    \
+  Q2048_LAUNCH_FUSED_CASE4(E, kModeSym + kModeFrozen, n, B, stream, __VA_ARGS__)                  \
+  Q2048_LAUNCH_FUSED_CASE4(E, kModeSym + kModeFrozen + kModeCas, n, B, stream, __VA_ARGS__)       \
+  Q2048_LAUNCH_FUSED_CASE4(E, kModeSym + kModeFrozen + kModeSummary, n, B, stream, __VA_ARGS__)   \
+  Q2048_LAUNCH_FUSED_CASE4(E, kModeSym + kModeFrozen + kModeSummary + kModeCas, n, B, stream, __VA_ARGS__) \
   Q2048_LAUNCH_FUSED_CASE(E, kModeLearn, n, B, stream, __VA_ARGS__)                               \
   Q2048_LAUNCH_FUSED_CASE(E, kModeCas, n, B, stream, __VA_ARGS__)                                 \
   Q2048_LAUNCH_FUSED_CASE(E, kModeEval, n, B, stream, __VA_ARGS__)                                \
@@ -2350,7 +2423,7 @@ inline int check_table(const void* table, int cap_log2) {
   Q2048_LAUNCH_FUSED_CASE(E, kModeFrozen + kModeSummary, n, B, stream, __VA_ARGS__)               \
   Q2048_LAUNCH_FUSED_CASE(E, kModeFrozen + kModeSummary + kModeCas, n, B, stream, __VA_ARGS__)
 #define Q2048_LAUNCH_FUSED(flags, n, side, B, stream, ...)                                        \
-  switch (env_bits(flags) * 16 + fused_mode(flags, n, side)) {                                        \
+  switch (env_bits(flags) * 32 + fused_mode(flags, n, side)) {                                        \
     Q2048_LAUNCH_FUSED_ENV(0, n, B, stream, __VA_ARGS__)                                          \
     Q2048_LAUNCH_FUSED_ENV(1, n, B, stream, __VA_ARGS__)                                          \
     Q2048_LAUNCH_FUSED_ENV(2, n, B, stream, __VA_ARGS__)                                          \
@@ -2365,10 +2438,11 @@ inline int env_bits(uint32_t flags) {
          ((flags & Q2048_FLAG_PLAY_ONLY) ? kEnvPlayOnly : 0);
 }
 inline int fused_mode(uint32_t flags, int n, const void* side) {   // play-only launches touch no table: one instantiation
-  if (flags & Q2048_FLAG_PLAY_ONLY) return kModeLearn;
-  if (flags & Q2048_FLAG_NO_LEARN) return kModeEval;   // (evaluation creates nothing anyway)
+  if (flags & Q2048_FLAG_PLAY_ONLY) return kModeLearn;   // (Q2048_FLAG_SYMMETRIC is inert here: no table, no key)
+  const int sym = (flags & Q2048_FLAG_SYMMETRIC) ? kModeSym : 0;
+  if (flags & Q2048_FLAG_NO_LEARN) return kModeEval | sym;   // (evaluation creates nothing anyway)
   const bool frozen = (flags & Q2048_FLAG_NO_NEW_ROWS) != 0u;
-  return ((flags & Q2048_FLAG_TD_CAS) ? kModeCas : kModeLearn) | (frozen ? kModeFrozen : 0) |
+  return sym | ((flags & Q2048_FLAG_TD_CAS) ? kModeCas : kModeLearn) | (frozen ? kModeFrozen : 0) |
          ((frozen && (n == 4 || side != nullptr) && (flags & Q2048_FLAG_LINE_SUMMARY)) ? kModeSummary : 0);   // (5x5: only with a side array)
 }
 // flag bits outside the ABI are an argument error (experiment builds also take bits 8..23)
@@ -2377,8 +2451,9 @@ constexpr uint32_t kAbiFlags = Q2048_FLAG_INDEPENDENT | Q2048_FLAG_SINGLE_ENV | 
                                Q2048_FLAG_NO_LEARN | Q2048_FLAG_NO_NEW_ROWS | Q2048_FLAG_LINE_SUMMARY;
 constexpr size_t kOptsSizeNoSide = offsetof(q2048_rollout_opts, line_summary);   // the layout before `line_summary`
 static_assert(kOptsSizeNoSide == 56 && sizeof(q2048_rollout_opts) == 64, "ABI layout");
-inline int check_flags(uint32_t flags, uint32_t refused = 0u) {
-  uint32_t allowed = kAbiFlags;
+// (`also`: Q2048_FLAG_SYMMETRIC, for the entry points that take it -- the fused rollouts, the player, q_lookup)
+inline int check_flags(uint32_t flags, uint32_t refused = 0u, uint32_t also = 0u) {
+  uint32_t allowed = kAbiFlags | also;
 #ifdef Q2048_EXPERIMENTS
   allowed |= 0x00ffff00u;
 #endif
@@ -2631,11 +2706,17 @@ int q2048_q_lookup(const q2048_slot* table, int cap_log2, const uint8_t* boards,
                    uint64_t env_id0, uint32_t flags, float* q_out, uint8_t* found, uint32_t* status,
                    void* stream) {
   if (int e = check_batch(B, n)) return e;
-  if (int e = check_flags(flags)) return e;
+  if (int e = check_flags(flags, 0u, Q2048_FLAG_SYMMETRIC)) return e;
+  if (n == 5 && (flags & Q2048_FLAG_SYMMETRIC)) return Q2048_ERR_UNSUPPORTED;
   if (int e = check_table(table, cap_log2)) return e;
   if (!boards || !q_out || !status) return Q2048_ERR_NULL;
   if (!aligned16(boards) || !aligned16(q_out)) return Q2048_ERR_ALIGN;
   if (B == 0) return Q2048_OK;
+  if (flags & Q2048_FLAG_SYMMETRIC) {
+    hipLaunchKernelGGL((k_q_lookup<4, true>), dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, table,
+                       (u64)((1ull << cap_log2) - 1ull), boards, B, env_id0, flags, q_out, found, status);
+    return launch_status();
+  }
   Q2048_LAUNCH(k_q_lookup, n, B, stream, table, (u64)((1ull << cap_log2) - 1ull), boards, B, env_id0,
                flags, q_out, found, status);
   return launch_status();
@@ -2673,7 +2754,8 @@ int q2048_fused_rollout_opts(uint8_t* boards, q2048_aux* aux, q2048_slot* table,
     memcpy(&o, opts, opts->size);
   }
   if (int e = check_batch(B, n)) return e;
-  if (int e = check_flags(flags)) return e;
+  if (int e = check_flags(flags, 0u, Q2048_FLAG_SYMMETRIC)) return e;
+  if (n == 5 && (flags & Q2048_FLAG_SYMMETRIC)) return Q2048_ERR_UNSUPPORTED;   // (a 125-bit compare: not built)
   if (o.log != nullptr && (o.log_count == nullptr || o.log_capacity < 0)) return Q2048_ERR_NULL;
   if (o.log != nullptr && !aligned16(o.log)) return Q2048_ERR_ALIGN;
   if (o.row_cache != nullptr && !aligned16(o.row_cache)) return Q2048_ERR_ALIGN;
@@ -2700,14 +2782,27 @@ int q2048_play_rollout(uint8_t* boards, q2048_aux* aux, const q2048_slot* table,
                        int64_t steps, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
                        int64_t* stats_i, double* stats_f, uint32_t* status, void* stream) {
   if (int e = check_batch(B, n)) return e;
-  if (int e = check_flags(flags, kAbiFlags & ~(Q2048_FLAG_INDEPENDENT | Q2048_FLAG_ENV_DQN | Q2048_FLAG_RESET_SHAPING)))
+  if (int e = check_flags(flags, kAbiFlags & ~(Q2048_FLAG_INDEPENDENT | Q2048_FLAG_ENV_DQN | Q2048_FLAG_RESET_SHAPING),
+                          Q2048_FLAG_SYMMETRIC))
     return e;
+  if (n == 5 && (flags & Q2048_FLAG_SYMMETRIC)) return Q2048_ERR_UNSUPPORTED;
   if (int e = check_table(table, cap_log2)) return e;
   if (!boards || !aux || !status) return Q2048_ERR_NULL;
   if (!aligned16(boards) || !aligned16(aux)) return Q2048_ERR_ALIGN;
   if (steps < 0 || steps > (1 << 30)) return Q2048_ERR_SIZE;
   if (!(eps >= 0.0 && eps <= 1.0)) return Q2048_ERR_RANGE;
   if (B == 0 || steps == 0) return Q2048_OK;
+  if (flags & Q2048_FLAG_SYMMETRIC) {
+#define Q2048_LAUNCH_PLAY_SYM(E)                                                                                      \
+  case E:                                                                                                             \
+    hipLaunchKernelGGL((k_play_rollout<4, E, true>), dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, boards, \
+                       aux, table, (u64)((1ull << cap_log2) - 1ull), B, (int)steps, eps, seed, env_id0, ctr0, flags,   \
+                       stats_i, stats_f, status);                                                                     \
+    break;
+    switch (env_bits(flags) & 3) { Q2048_LAUNCH_PLAY_SYM(0) Q2048_LAUNCH_PLAY_SYM(1) Q2048_LAUNCH_PLAY_SYM(2) Q2048_LAUNCH_PLAY_SYM(3) }
+#undef Q2048_LAUNCH_PLAY_SYM
+    return launch_status();
+  }
   Q2048_LAUNCH_ENV(k_play_rollout, flags, n, B, stream, boards, aux, table, (u64)((1ull << cap_log2) - 1ull), B,
                    (int)steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status);
   return launch_status();
@@ -2824,6 +2919,17 @@ int q2048_det_rollout_cached(uint8_t* boards, q2048_aux* aux, q2048_slot* table,
   }
   if (stripes != nullptr)
     hipLaunchKernelGGL(k_stats_fold, dim3(1), dim3(64), 0, s, stripes, stats_i, stats_f);
+  return launch_status();
+}
+
+int q2048_canonicalize(const uint8_t* boards, int64_t B, int n, uint8_t* boards_out, uint8_t* sym_out, void* stream) {
+  if (int e = check_batch(B, n)) return e;
+  if (n != 4) return Q2048_ERR_UNSUPPORTED;
+  if (boards == nullptr) return Q2048_ERR_NULL;
+  if (!aligned16(boards) || !aligned16(boards_out)) return Q2048_ERR_ALIGN;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_canonicalize, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, boards, B, boards_out,
+                     sym_out);
   return launch_status();
 }
 

@@ -71,7 +71,8 @@ def main(argv=None):
     cap = max(int(sd["capacity_log2"]), 4) if "table" in sd else max(16, (2 * max(rows, 1) - 1).bit_length())
     agent = pkg.BatchedQLearningAgent(1, learning_rate=sd["lr"], discount_factor=sd["gamma"],
                                       exploration_rate=args.epsilon, capacity_log2=cap, seed=args.seed,
-                                      device=args.device, board_size=n, placement="plain")
+                                      device=args.device, board_size=n, placement="plain",
+                                      symmetric=bool(sd.get("symmetric", False)))   # (a folded table is read folded)
     agent.load_state_dict(sd)
     agent.seed, agent.ctr, agent.epsilon = args.seed, 0, args.epsilon     # evaluation has its own draws
     agent.stats(reset=True)
@@ -91,7 +92,7 @@ def main(argv=None):
             st = agent.stats()
     assert agent.table_size() == rows_before and st["inserts"] == 0      # nothing was learnt
     out = {"model": args.model, "rows": rows_before, "board_size": n, "epsilon": args.epsilon,
-           "policy": args.policy,
+           "policy": args.policy, **({"symmetric": True} if agent.symmetric else {}),
            "envs": args.num_envs, "games": st["episodes"], "env_steps": st["steps"],
            "mean_score": st["mean_score"], "mean_return": st["mean_return"],
            "valid_move_frac": st["valid_moves"] / max(st["steps"], 1),

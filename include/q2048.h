@@ -64,7 +64,8 @@ extern "C" {
                                the 64-byte one, so a caller built against the earlier header runs unchanged;
                                q2048_table_merge (combine two tables on the device) arrived without a bump as well: a
                                caller detects it by its symbol; so did q2048_play_rollout (the greedy player over the
-                               legal moves, one launch) */
+                               legal moves, one launch) and Q2048_FLAG_SYMMETRIC (one row for a board's eight mirror
+                               images), detected by the symbol q2048_canonicalize */
 
 /* return codes */
 #define Q2048_OK 0
@@ -183,6 +184,46 @@ extern "C" {
                                      slot with the key's fingerprint costs its head and, on a first-word match, its second
                                      half.  Without the pointer the flag is ignored on 5x5; on 4x4 the pointer is ignored.
                                      (bits 8..23 belong to the measurement build's experiment switches) */
+
+#define Q2048_FLAG_SYMMETRIC (1u << 26) /* SYMMETRY FOLDING, 4x4 only: the table holds ONE row for the eight mirror images of
+                                     a board.  2048 has an eight-element symmetry group (four quarter turns, each with or
+                                     without a mirror), and what the reference's reward is made of -- score, validity,
+                                     max tile, game over (Game2048_env.py:136-184) -- and its spawn (uniform over the
+                                     empty cells, :16-20) are invariant under it, so the true Q satisfies
+                                     Q(s, a) = Q(g s, pi_g(a)): a table keyed by a canonical image needs up to 8x fewer
+                                     rows for the same experience, and every row learns from all eight images.  (The only
+                                     action-dependent shaping, the consecutive-action penalty, lives in `aux` and is not
+                                     in the key without the flag either.)
+                                       IMAGES of a board b (the [4][4] array of log2 cells), in numpy terms:
+                                         g = 0..3: np.rot90(b, g), g counter-clockwise quarter turns;
+                                         g = 4..7: np.rot90(np.fliplr(b), g - 4).
+                                       CANONICAL IMAGE: the one whose packed 64-bit key (cell 4r + c in nibble 4r + c, as
+                                         q2048_slot.key) is smallest as an unsigned integer; on a tie -- boards with a
+                                         non-trivial stabiliser -- the smallest g.
+                                       ACTIONS: pi_g is defined by move(image_g(b), pi_g(a)) == image_g(move(b, a)) for
+                                         all b and a (a = 0 left, 1 up, 2 right, 3 down):
+                                           g < 4:  pi_g(a) = (a - g) & 3        g >= 4:  pi_g(a) = (2 - a - (g - 4)) & 3
+                                              a:   0 1 2 3                         a:   0 1 2 3
+                                           g = 0:  0 1 2 3                      g = 4:  2 1 0 3
+                                           g = 1:  3 0 1 2                      g = 5:  1 0 3 2
+                                           g = 2:  2 3 0 1                      g = 6:  0 3 2 1
+                                           g = 3:  1 2 3 0                      g = 7:  3 2 1 0
+                                     With the flag the table is addressed by the canonical image's key (the salt of
+                                     Q2048_FLAG_INDEPENDENT is applied AFTER canonicalisation) and a stored row is in the
+                                     canonical frame.  Everything the caller or the policy sees is in the ENV frame,
+                                     Q_env[a] = Q_canon[pi_g(a)]: the epsilon-greedy choice and its first-maximum tie order
+                                     (ascending env action), the random action x1 >> 30, the player's legal mask, q_out of
+                                     q2048_q_lookup, q2048_episode.q and .action.  The TD write goes to Q_canon[pi_g(a)].
+                                     Where g = 0 for every board met the behaviour is that without the flag, draw for
+                                     draw.  The row cache, visit rows, Q2048_FLAG_NO_NEW_ROWS and the 4x4 line summaries
+                                     work unchanged (they only ever see a key); export / import / merge / growth are
+                                     table-level and move canonical keys like any others.  A table is EITHER folded or
+                                     plain for its whole life: the flag is a property of the table, not of a call.
+                                     Taken by q2048_fused_rollout / _log / _opts, q2048_play_rollout and q2048_q_lookup
+                                     (with Q2048_FLAG_PLAY_ONLY: accepted and inert); n = 5 with the flag is
+                                     Q2048_ERR_UNSUPPORTED (a 125-bit compare: not built); every other entry point with
+                                     a flags argument refuses it (Q2048_ERR_FLAGS).  A library that has the flag exports
+                                     q2048_canonicalize (below): that symbol is how a caller detects it. */
 
 /* per-env state, Game2048_env.__init__ (Game2048_env.py:81-95) + episode bookkeeping */
 typedef struct q2048_aux {
@@ -667,6 +708,15 @@ int q2048_table_export(const q2048_slot *table, int cap_log2, uint64_t *keys_out
  * loop of Deep_QLearning/main_dir/mainDQL_CNN_step2.py:168-174 (`env.game.move(action,
  * trial=True)`), the reference's way of listing legal moves.  No board is modified. */
 int q2048_legal_moves(const uint8_t *boards, int64_t B, int n, uint8_t *mask_out, void *stream);
+
+/* The canonical image of B 4x4 boards under the eight symmetries (Q2048_FLAG_SYMMETRIC above: images, tie rule, action
+ * table): boards_out[i] = the image of boards[i] whose packed key is smallest (bytes are moved, so a tile above 2^15
+ * keeps its value; the comparison sees its low nibble, as the state key does), sym_out[i] = g, which image that is.
+ * boards_out may be `boards` itself (in place) or NULL, sym_out may be NULL.  What a host that canonicalises for
+ * itself needs, and the symbol by which a caller detects that the library folds symmetries.
+ * Errors: n = 5 -> Q2048_ERR_UNSUPPORTED (other n too); boards NULL -> Q2048_ERR_NULL; boards or boards_out not 16-byte
+ * aligned -> Q2048_ERR_ALIGN; B < 0 -> Q2048_ERR_SIZE.  B == 0: nothing happens, Q2048_OK. */
+int q2048_canonicalize(const uint8_t *boards, int64_t B, int n, uint8_t *boards_out, uint8_t *sym_out, void *stream);
 
 /* One-hot state encoder of the reference's DQN front-end (Deep_QLearning/main_dir/
  * Dqn8TestNOPERCNN.py:271-277: one_hot(log2(tile), depth 16) transposed to [16, 4, 4]):

@@ -66,6 +66,9 @@ def main(argv=None):
             first = {k: v for k, v in sd.items() if k not in ("keys", "q", "table", "env", "visit_rows")}
         if int(sd["board_size"]) != int(first["board_size"]):
             raise SystemExit(f"{path}: board size {sd['board_size']}, {args.inputs[0]} has {first['board_size']}")
+        if bool(sd.get("symmetric", False)) != bool(first.get("symmetric", False)):
+            raise SystemExit(f"{path} and {args.inputs[0]}: a symmetry-folded table (train.py --symmetric) and a plain "
+                             "one cannot be merged")
         if int(sd["flags"]) & FLAG_INDEPENDENT:
             raise SystemExit(f"{path} was trained with private rows per env (Q2048_FLAG_INDEPENDENT): its keys are "
                              "salted by env id and mean nothing in another learner's table")
@@ -79,7 +82,8 @@ def main(argv=None):
     def agent_of(capacity_log2):
         return pkg.BatchedQLearningAgent(1, learning_rate=first["lr"], discount_factor=first["gamma"],
                                          capacity_log2=capacity_log2, device=args.device, board_size=n,
-                                         placement="plain", freeze_load=None, row_cache=False)
+                                         placement="plain", freeze_load=None, row_cache=False,
+                                         symmetric=bool(first.get("symmetric", False)))
 
     dst = agent_of(_capacity_for(sum(rows_in)))
     mode, weight = {"mean": ("add", 1.0 / K), "sum": ("add", 1.0), "maxabs": ("maxabs", 1.0),

@@ -77,6 +77,12 @@ def parse_args(argv=None):
                    "races an update is stored plainly and counted in the statistics)")
     p.add_argument("--deterministic", action="store_true",
                    help="batched mode: reproducible two-phase steps (slower; see deterministic_rollout)")
+    p.add_argument("--symmetric", action="store_true",
+                   help="batched mode, 4x4, hash-table agent, fused path: SYMMETRY FOLDING (Q2048_FLAG_SYMMETRIC) -- one "
+                        "table row for the eight mirror images of a board, keyed by the image with the smallest key; up "
+                        "to 8x fewer rows for the same experience, so the table freezes that much later.  Learns a "
+                        "different table than without the flag (every row is shared by its images); --save records it "
+                        "and evaluate.py / --resume / merge_tables.py follow the file")
     p.add_argument("--agent", choices=["hash", "row-tuple"], default="hash",
                    help="hash = the reference's whole-board Q-table; row-tuple = BASELINE configs[1]")
     p.add_argument("--log", default="debug_log.csv", help="CSV log path (Agent/main.py:71)")
@@ -212,7 +218,8 @@ def train_batched(args, pkg):
                                           args.epsilon_min, cap, dev, args.seed, shard.env_id0,
                                           strict_td=args.strict_td, board_size=args.board_size,
                                           initial_capacity_log2=args.initial_capacity_log2 or "auto",
-                                          async_growth=args.growth == "async", freeze_load=args.freeze_load or None)
+                                          async_growth=args.growth == "async", freeze_load=args.freeze_load or None,
+                                          symmetric=args.symmetric)
     if args.deterministic and args.agent != "hash":
         raise SystemExit("--deterministic applies to the hash-table agent")
     if (args.save or args.resume) and args.agent != "hash":
@@ -417,6 +424,14 @@ def _save(agent, path, world, rank):
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.symmetric:
+        if args.board_size != 4:
+            raise SystemExit("--symmetric folds 4x4 boards only (--board-size 5 is not built)")
+        if args.agent != "hash" or args.deterministic:
+            raise SystemExit("--symmetric applies to the fused hash-table path (not --agent row-tuple, not --deterministic)")
+        if args.num_envs == 1 and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+            raise SystemExit("--symmetric needs the batched mode (--num-envs > 1): the one-state loop learns through "
+                             "choose_action / update_q_value, which do not take the flag")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # the parent of the job has made no GPU call: one fresh process per rank (launch.py)
         spec = importlib.util.spec_from_file_location(
