@@ -34,6 +34,7 @@ FLAG_ENV_DQN, FLAG_RESET_SHAPING, FLAG_PLAY_ONLY, FLAG_NO_LEARN, FLAG_NO_NEW_ROW
 FLAG_LINE_SUMMARY = 1 << 24
 FLAG_SYMMETRIC = 1 << 26
 MERGE_ADD, MERGE_BLEND, MERGE_MAXABS = 0, 1, 2
+FOLD_MEAN, FOLD_MEAN_TRAINED, FOLD_SUM, FOLD_MAXABS = 0, 1, 2, 3
 ABI_VERSION = 7
 ST_STEPS, ST_EPISODES, ST_VALID, ST_SCORE, ST_INSERTS, ST_DROPS, ST_EXPLORE, ST_CAS_RETRY = range(8)
 ST_HIST0, NSTAT_I = 8, 32
@@ -231,6 +232,8 @@ _SIGNATURES = {
                                      C.c_int, C.c_void_p, C.c_void_p]),
     "q2048_table_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "q2048_table_fold": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -1151,10 +1151,10 @@ class BatchedQLearningAgent:
 
     def import_rows(self, keys: np.ndarray, q: np.ndarray) -> None:
         """Inserts (key, q[4]) rows exported by `export_rows` (any capacity that holds them)."""
-        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(len(q), -1)
         rows = len(q)
-        if rows == 0:
+        if rows == 0:                                   # (an empty table's checkpoint: nothing to reshape or insert)
             return
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(rows, -1)
         self.invalidate_row_cache()
         while self.growable and rows * 2 > (1 << self.capacity_log2) and self.capacity_log2 < self.max_capacity_log2:
             self.grow_table(min(self.max_capacity_log2,
@@ -1251,6 +1251,75 @@ class BatchedQLearningAgent:
             warnings.warn("table_merge placed rows deeper than the learning paths probe (2^10 slots): q_values finds "
                           "them, choose / update / rollouts read them as absent -- merge into a larger table")
         return {"read": read, "created": created, "combined": combined, "dropped": dropped}
+
+    _FOLD_KINDS = {"mean": N.FOLD_MEAN, "mean_trained": N.FOLD_MEAN_TRAINED, "sum": N.FOLD_SUM, "maxabs": N.FOLD_MAXABS}
+
+    def fold_from(self, other: "BatchedQLearningAgent", fold: str = "mean_trained", mode: str = "add",
+                  weight: float = 1.0) -> dict:
+        """Folds `other`'s PLAIN table into this symmetry-folded one on the device (q2048_table_fold): the rows `other`
+        holds for a board's up to eight mirror images become one row in the canonical frame, and that row finds or
+        creates its row here, combined with it by `mode` / `weight` as `merge_from` combines a row.  The way into a
+        folded table for a learner that was trained plain.  `other` is only read.
+          fold  "mean"          per action the mean over the images that have a row
+                "mean_trained"  per action the mean over the images whose entry is not exactly 0: an image the run
+                                never updated for that action does not dilute the ones it did (0 when there is none)
+                "sum"           per action the sum over the images that have a row
+                "maxabs"        per action the entry of largest magnitude
+        float32, every product and sum rounded on its own, a fixed order of the images: a float32 numpy model gives the
+        same bits, whatever the slots the rows lie in.  Sizing, the frozen rule and the row bookkeeping are
+        `merge_from`'s (rows + other's rows is still an upper bound).  Keys salted per env (independent=True) cannot
+        be told from boards and are refused.
+        Returns the call's counters: {"read", "orbits", "created", "combined", "dropped"}; read == other's rows,
+        orbits == created + combined + dropped."""
+        if not isinstance(other, BatchedQLearningAgent) or other is self:
+            raise ValueError("fold_from takes another BatchedQLearningAgent")
+        if other.device != self.device:
+            raise ValueError("the two agents live on different devices")
+        if self.board_size != 4 or other.board_size != 4:
+            raise ValueError("symmetry folding is built for board size 4 only")
+        if not self.symmetric:
+            raise ValueError("fold_from needs a symmetry-folded destination (symmetric=True); merge_from combines two "
+                             "tables of one kind")
+        if other.symmetric:
+            raise ValueError("the source is already symmetry-folded: merge_from combines two folded tables")
+        if (self.flags | other.flags) & N.FLAG_INDEPENDENT:
+            raise ValueError("keys salted per env (independent=True, Q2048_FLAG_INDEPENDENT) do not decode to boards "
+                             "and cannot be folded")
+        if fold not in self._FOLD_KINDS:
+            raise ValueError(f"fold must be one of {sorted(self._FOLD_KINDS)}")
+        if mode not in self._MERGE_MODES:
+            raise ValueError(f"mode must be one of {sorted(self._MERGE_MODES)}")
+        weight = float(weight)
+        if not np.isfinite(weight) or (mode == "blend" and not 0.0 <= weight <= 1.0):
+            raise ValueError("weight must be finite, and in [0, 1] for mode 'blend'")
+        if self.frozen:
+            raise ValueError("this agent's key set is closed (frozen): a fold would create rows its visit rows and "
+                             "line summaries do not know")
+        self.finish_growth()
+        other.finish_growth()
+        rows, rows_other = self._rows_exact(), other._rows_exact()
+        total = rows + rows_other                         # (an upper bound: an orbit has at least one row in `other`)
+        while self.growable and total * 2 > (1 << self.capacity_log2) and self.capacity_log2 < self.max_capacity_log2:
+            self.grow_table(min(self.max_capacity_log2, max(self.capacity_log2 + 1, int(np.ceil(np.log2(2.0 * total))))),
+                            _rows=rows)
+        if total > 0.9 * (1 << self.capacity_log2):
+            raise ValueError("table too small for the fold (load factor could exceed 0.9)")
+        self.invalidate_row_cache()
+        self._summarised, self._side = False, None        # (rows arrive: line summaries stop describing the table)
+        counters = torch.zeros(5, dtype=torch.int64, device=self.device)
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)    # this call's own word (the agent's is sticky)
+        N.check(self._L.q2048_table_fold(_ptr(self.table), self.capacity_log2, _ptr(other.table), other.capacity_log2, 1,
+                                         self._FOLD_KINDS[fold], self._MERGE_MODES[mode], weight, _ptr(counters),
+                                         _ptr(status), _stream(self.device)), "table_fold")
+        read, orbits, created, combined, dropped = (int(v) for v in counters.tolist())
+        code = int(status.item())
+        self._rebase_rows(rows + created)
+        if code & N.STATUS_TABLE_FULL:
+            raise RuntimeError(f"table_fold dropped {dropped} orbits (probe limit)")
+        if code & N.STATUS_DEEP_ROW:
+            warnings.warn("table_fold placed rows deeper than the learning paths probe (2^10 slots): q_values finds "
+                          "them, choose / update / rollouts read them as absent -- fold into a larger table")
+        return {"read": read, "orbits": orbits, "created": created, "combined": combined, "dropped": dropped}
 
     def recount_rows(self) -> int:
         """Counts the occupied slots (one streaming pass, synchronising) and makes that the base of the row

@@ -739,6 +739,88 @@ Q_HD float td_value(float q_sa, float reward, float max_q_next, bool done, doubl
 }
 
 // ------------------------------------------------------------------------------------------
+// FOLDING A PLAIN TABLE INTO A SYMMETRY-FOLDED ONE (include/q2048.h, q2048_table_fold; kernel and CPU twin both
+// walk an orbit through fold_orbit).  The rows of the up to eight mirror images of a board become the one row of
+// their canonical image.  The MEMBERS of the orbit of the canonical key c are image_h(c), h = 0..7 in ascending
+// h, an h whose key equals that of a smaller h left out (boards with a stabiliser); the PRESENT members are the
+// ones with a row in the source.  A member's row enters the canonical frame by its own g (the smallest g with
+// image_g(member) = c, what the fused rollout uses when it meets that board): Qc[pi_g(a)] = Q_member[a].  The
+// present members' rows are combined per action in member order, float32, every sum and product rounded on its
+// own, the division a multiplication by float32(1.0 / k).
+// ------------------------------------------------------------------------------------------
+constexpr int kFoldMean = 0, kFoldMeanTrained = 1, kFoldSum = 2, kFoldMaxAbs = 3;   // Q2048_FOLD_*
+// image_h(k), h = 0..7 (the candidates of canonical_key, in its order)
+Q_HD void key_images(uint64_t k, uint64_t img[8]) {
+  const uint64_t t = key_transpose(k), hk = key_flip_h(k), ht = key_flip_h(t);
+  img[0] = k; img[1] = key_flip_v(t); img[2] = key_flip_v(hk); img[3] = ht;
+  img[4] = hk; img[5] = t; img[6] = key_flip_v(k); img[7] = key_flip_v(ht);
+}
+Q_HD float fold_inv(uint32_t k) {               // float32(1.0 / k), k = 1..8: the mean is a product, never a `/`
+  return k == 1u ? 1.0f : k == 2u ? 0.5f : k == 3u ? (float)(1.0 / 3.0) : k == 4u ? 0.25f : k == 5u ? (float)(1.0 / 5.0)
+       : k == 6u ? (float)(1.0 / 6.0) : k == 7u ? (float)(1.0 / 7.0) : 0.125f;
+}
+// the entry x of the next member joins its action's running value (`n` entries have joined before; the first one
+// is taken as it is -- no 0 + x, so a lone -0.0 stays -0.0)
+template <int FOLD>
+Q_HD void fold_step(float& acc, uint32_t& n, float x) {
+  Q2048_NO_CONTRACT
+  if (FOLD == kFoldMeanTrained && x == 0.0f) return;      // an untrained entry (+0 or -0) does not dilute a trained one
+  if (n == 0u) acc = x;
+  else if (FOLD == kFoldMaxAbs) acc = fabsf(x) > fabsf(acc) ? x : acc;   // equal magnitude: the earlier member's
+  else acc = acc + x;
+  n += 1u;
+}
+template <int FOLD>
+Q_HD float fold_finish(float acc, uint32_t n) {
+  Q2048_NO_CONTRACT
+  if (FOLD == kFoldMean || FOLD == kFoldMeanTrained) {
+    const float inv = fold_inv(n);
+    return n == 0u ? 0.0f : acc * inv;                    // (MEAN_TRAINED with no trained entry: +0.0)
+  }
+  return acc;
+}
+// The orbit of the source row (m, q[4]), seen from that row.  `find(key, out[4])` says whether `key` has a row in
+// the source and reads it.  Returns false when a present member precedes m: m is not its orbit's LEADER and
+// another row's call returns true for this orbit.  For the leader: true, `canon` = the canonical key, r[4] = the
+// orbit's row.  Exactly one present member of every orbit is its leader, so a caller that writes only for leaders
+// writes every destination row once.
+template <int FOLD, class Find>
+Q_HD bool fold_orbit(uint64_t m, const float q[4], const Find& find, uint64_t& canon, float r[4]) {
+  canon = canonical_key(m).key;
+  uint64_t img[8];
+  key_images(canon, img);
+  float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  uint32_t n[4] = {0u, 0u, 0u, 0u};
+  bool leader = false;
+#pragma unroll
+  for (int h = 0; h < 8; ++h) {
+    bool repeat = false;
+#pragma unroll
+    for (int j = 0; j < h; ++j) repeat |= img[j] == img[h];
+    if (repeat) continue;
+    float v[4];
+    if (img[h] == m) {
+      leader = true;
+      v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+    } else {
+      if (!find(img[h], v)) continue;
+      if (!leader) return false;
+    }
+    const uint32_t g = canonical_key(img[h]).g;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int at = sym_action(g, a);
+#pragma unroll
+      for (int b = 0; b < 4; ++b)               // (selects, not an index: the accumulators stay in registers)
+        if (at == b) fold_step<FOLD>(acc[b], n[b], v[a]);
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < 4; ++b) r[b] = fold_finish<FOLD>(acc[b], n[b]);
+  return true;
+}
+
+// ------------------------------------------------------------------------------------------
 // row-tuple linear Q (BASELINE configs[1]: "flat-array Q over row-tuple features").  NOT the
 // reference's learner (its Q is keyed by the whole board, Agent/main.py:82): Q(s,a) is the sum
 // over the four rows r of W[r][idx_r(s)][a] with idx_r = pack_row(row r); same epsilon-greedy

@@ -1309,6 +1309,81 @@ int q2048_table_merge(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, 
   return Q2048_OK;
 }
 
+// the device's fold (k_table_fold), value for value: the same walk of the orbit (fold_orbit, q2048_core.hpp), the
+// leader's one find-or-create in `dst`, the merge's arithmetic; slots of `src` split over the threads
+namespace {
+static_assert(Q2048_FOLD_MEAN == kFoldMean && Q2048_FOLD_MEAN_TRAINED == kFoldMeanTrained && Q2048_FOLD_SUM == kFoldSum &&
+              Q2048_FOLD_MAXABS == kFoldMaxAbs, "q2048.h / q2048_core.hpp");
+}  // namespace
+int q2048_table_fold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, int src_cap_log2, int key_words, int fold,
+                     int mode, float w, uint64_t* counters, uint32_t* status, void*) {
+  if (!dst || !src || !counters) return Q2048_ERR_NULL;
+  if (key_words == 2) return Q2048_ERR_UNSUPPORTED;
+  if (key_words != 1) return Q2048_ERR_SIZE;
+  if (dst_cap_log2 < 4 || dst_cap_log2 > 40 || src_cap_log2 < 4 || src_cap_log2 > 40) return Q2048_ERR_SIZE;
+  if (!aligned16(dst) || !aligned16(src)) return Q2048_ERR_ALIGN;
+  if (fold != Q2048_FOLD_MEAN && fold != Q2048_FOLD_MEAN_TRAINED && fold != Q2048_FOLD_SUM && fold != Q2048_FOLD_MAXABS)
+    return Q2048_ERR_FLAGS;
+  if (mode != Q2048_MERGE_ADD && mode != Q2048_MERGE_BLEND && mode != Q2048_MERGE_MAXABS) return Q2048_ERR_FLAGS;
+  if (!std::isfinite(w) || (mode == Q2048_MERGE_BLEND && !(w >= 0.0f && w <= 1.0f))) return Q2048_ERR_RANGE;
+  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), s0 = reinterpret_cast<uintptr_t>(src);
+  const uintptr_t d1 = d0 + (sizeof(q2048_slot) << dst_cap_log2), s1 = s0 + (sizeof(q2048_slot) << src_cap_log2);
+  if (s0 < d1 && d0 < s1) return Q2048_ERR_RANGE;
+  const int64_t cap = (int64_t)1 << src_cap_log2;
+  const u64 mask = (1ull << dst_cap_log2) - 1ull, src_mask = (1ull << src_cap_log2) - 1ull;
+  const float one_minus_w = 1.0f - w;
+  struct Part { uint64_t read = 0, created = 0, combined = 0, dropped = 0; uint32_t bits = 0; };
+  std::vector<Part> parts((size_t)threads_for(cap));
+  Part* part = parts.data();
+  const int used = parallel_ranges(cap, [=](int64_t lo, int64_t hi, int t) {
+    Part p;
+    const auto find = [src, src_mask](uint64_t k, float out[4]) {
+      Row row;
+      const bool present = probe_find(src, src_mask, Geo<4>::Key{(u64)k}, row, kMaxProbe) >= 0;
+      out[0] = row.q0; out[1] = row.q1; out[2] = row.q2; out[3] = row.q3;
+      return present;
+    };
+    for (int64_t i = lo; i < hi; ++i) {
+      const q2048_slot& s = src[i];
+      if (s.key == 0ull) continue;
+      ++p.read;
+      uint64_t canon;
+      float r[4];
+      const bool leads = fold == Q2048_FOLD_MEAN           ? fold_orbit<kFoldMean>(s.key, s.q, find, canon, r)
+                         : fold == Q2048_FOLD_MEAN_TRAINED ? fold_orbit<kFoldMeanTrained>(s.key, s.q, find, canon, r)
+                         : fold == Q2048_FOLD_SUM          ? fold_orbit<kFoldSum>(s.key, s.q, find, canon, r)
+                                                           : fold_orbit<kFoldMaxAbs>(s.key, s.q, find, canon, r);
+      if (!leads) continue;                                  // another row leads this orbit
+      const Geo<4>::Key key{(u64)canon};
+      const u64 hash = key_hash(key);
+      bool inserted;
+      const int64_t slot = probe_insert(dst, mask, key, hash & mask, inserted, kMaxProbe);
+      if (slot < 0) { ++p.dropped; p.bits |= Q2048_STATUS_TABLE_FULL; continue; }
+      if (inserted) {
+        ++p.created;
+        if (seq_pos(seq_of(hash, mask), (u64)slot) >= probe_limit(mask, kRolloutProbe)) p.bits |= Q2048_STATUS_DEEP_ROW;
+        for (int a = 0; a < 4; ++a) st_f32(&dst[slot].q[a], mode == Q2048_MERGE_ADD ? mul_rn(w, r[a]) : r[a]);
+      } else {
+        ++p.combined;
+        for (int a = 0; a < 4; ++a) st_f32(&dst[slot].q[a], merge_value(mode, ld_f32(&dst[slot].q[a]), r[a], w, one_minus_w));
+      }
+    }
+    part[t] = p;
+  });
+  uint32_t bits = 0u;
+  for (int t = 0; t < used; ++t) {
+    const Part& p = parts[(size_t)t];
+    counters[0] += p.read;
+    counters[1] += p.created + p.combined + p.dropped;
+    counters[2] += p.created;
+    counters[3] += p.combined;
+    counters[4] += p.dropped;
+    bits |= p.bits;
+  }
+  if (bits && status != nullptr) status_or(status, bits);
+  return Q2048_OK;
+}
+
 int q2048_canonicalize(const uint8_t* boards, int64_t B, int n, uint8_t* boards_out, uint8_t* sym_out, void*) {
   if (int e = check_batch(B, n)) return e;
   if (n != 4) return Q2048_ERR_UNSUPPORTED;

@@ -2325,6 +2325,103 @@ __global__ __launch_bounds__(kBlock) void k_table_merge(const q2048_slot* src, u
   }
 }
 
+// Fold (q2048_table_fold): the merge's sibling for a PLAIN `src` and a symmetry-folded `dst`.  Up to eight rows of
+// `src` -- the mirror images of one board -- land on ONE row of `dst`, so "no two lanes ever meet on a dst row" has to
+// be made true: a lane streams `src` as the merge does, and for an occupied slot walks its orbit's members in order
+// (fold_orbit, q2048_core.hpp), looking the others up in `src` itself (probe_find under the bulk limit; `src` is only
+// read).  A lane that finds a present member ahead of its own is not the orbit's leader and stops there; the leader
+// collects the remaining members, forms the orbit's row in the canonical frame and performs the orbit's one
+// find-or-create in `dst`, combined by MODE exactly as the merge combines a source row.  One writer per dst row, no
+// float atomics: the result depends on the two tables' rows only.  counters[0..4] += rows read / orbits / created /
+// combined / dropped, one atomic per counter and block.
+static_assert(Q2048_FOLD_MEAN == kFoldMean && Q2048_FOLD_MEAN_TRAINED == kFoldMeanTrained && Q2048_FOLD_SUM == kFoldSum &&
+              Q2048_FOLD_MAXABS == kFoldMaxAbs, "q2048.h / q2048_core.hpp");
+template <int FOLD, int MODE>
+__global__ __launch_bounds__(kBlock) void k_table_fold(const q2048_slot* src, u64 src_cap, q2048_slot* dst, u64 dst_mask,
+                                                       float w, float one_minus_w, u64* counters, uint32_t* status) {
+  const u32x4* t16 = reinterpret_cast<const u32x4*>(src);
+  const u64 src_mask = src_cap - 1ull;
+  u64 read = 0ull, created = 0ull, combined = 0ull, dropped = 0ull;
+  uint32_t bits = 0u;
+  const auto find = [src, src_mask](uint64_t k, float out[4]) {
+    Row row;
+    bool made;
+    const bool present = probe_find(src, src_mask, Geo<4>::Key{(u64)k}, row, made, kMaxProbe) >= 0;
+    out[0] = row.q0; out[1] = row.q1; out[2] = row.q2; out[3] = row.q3;
+    return present;
+  };
+  for (u64 i = (u64)blockIdx.x * kBlock + threadIdx.x; i < src_cap; i += (u64)gridDim.x * kBlock) {
+    const u32x4 a = __builtin_nontemporal_load(&t16[2ull * i]);          // {key, q0, q1}
+    const u64 k = (u64)a.x | ((u64)a.y << 32);
+    if (k == 0ull) continue;
+    ++read;
+    const u32x4 b = __builtin_nontemporal_load(&t16[2ull * i + 1ull]);   // {q2, q3, summary word: not looked at}
+    const float own[4] = {bits_f32(a.z), bits_f32(a.w), bits_f32(b.x), bits_f32(b.y)};
+    uint64_t canon;
+    float s[4];
+    if (!fold_orbit<FOLD>(k, own, find, canon, s)) continue;             // another lane leads this orbit
+    const Geo<4>::Key key{(u64)canon};
+    bool inserted;
+    const int64_t slot = probe_insert(dst, dst_mask, key, key_home(key, dst_mask), inserted, kMaxProbe);
+    if (slot < 0) { ++dropped; bits |= Q2048_STATUS_TABLE_FULL; continue; }
+    float r0, r1, r2, r3;
+    if (inserted) {
+      ++created;
+      if (seq_pos(seq_of(key_hash(key), dst_mask), (u64)slot) >= probe_limit(dst_mask, kRolloutProbe)) bits |= Q2048_STATUS_DEEP_ROW;
+      if constexpr (MODE == Q2048_MERGE_ADD) { r0 = __fmul_rn(w, s[0]); r1 = __fmul_rn(w, s[1]); r2 = __fmul_rn(w, s[2]); r3 = __fmul_rn(w, s[3]); }
+      else { r0 = s[0]; r1 = s[1]; r2 = s[2]; r3 = s[3]; }
+    } else {
+      ++combined;
+      const u64 lo = ld_u64(&dst[slot].q[0]), hi = ld_u64(&dst[slot].q[2]);
+      r0 = merge_value<MODE>(bits_f32((uint32_t)lo), s[0], w, one_minus_w);
+      r1 = merge_value<MODE>(bits_f32((uint32_t)(lo >> 32)), s[1], w, one_minus_w);
+      r2 = merge_value<MODE>(bits_f32((uint32_t)hi), s[2], w, one_minus_w);
+      r3 = merge_value<MODE>(bits_f32((uint32_t)(hi >> 32)), s[3], w, one_minus_w);
+    }
+    uint2* q = reinterpret_cast<uint2*>(dst[slot].q);                    // 8-byte aligned (offset 8 of a 32-B slot)
+    q[0] = make_uint2(f32_bits(r0), f32_bits(r1));
+    q[1] = make_uint2(f32_bits(r2), f32_bits(r3));
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    read += __shfl_xor(read, d); created += __shfl_xor(created, d); combined += __shfl_xor(combined, d);
+    dropped += __shfl_xor(dropped, d); bits |= __shfl_xor(bits, d);
+  }
+  __shared__ u64 wc[4][kBlock / 64];
+  __shared__ uint32_t wb[kBlock / 64];
+  if ((threadIdx.x & 63u) == 0u) {
+    const uint32_t wv = threadIdx.x >> 6;
+    wc[0][wv] = read; wc[1][wv] = created; wc[2][wv] = combined; wc[3][wv] = dropped; wb[wv] = bits;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 n = 0ull, c = 0ull, m = 0ull, f = 0ull;
+    uint32_t sb = 0u;
+#pragma unroll
+    for (int v = 0; v < kBlock / 64; ++v) { n += wc[0][v]; c += wc[1][v]; m += wc[2][v]; f += wc[3][v]; sb |= wb[v]; }
+    if (n) atomicAdd(&counters[0], n);
+    if (c + m + f) atomicAdd(&counters[1], c + m + f);
+    if (c) atomicAdd(&counters[2], c);
+    if (m) atomicAdd(&counters[3], m);
+    if (f) atomicAdd(&counters[4], f);
+    if (sb && status != nullptr) atomicOr(status, sb);
+  }
+}
+
+template <int FOLD>
+void launch_fold(int mode, dim3 grid, hipStream_t stream, const q2048_slot* src, u64 cap, q2048_slot* dst, u64 mask, float w,
+                 float one_minus_w, u64* counters, uint32_t* status) {
+  if (mode == Q2048_MERGE_ADD)
+    hipLaunchKernelGGL((k_table_fold<FOLD, Q2048_MERGE_ADD>), grid, dim3(kBlock), 0, stream, src, cap, dst, mask, w,
+                       one_minus_w, counters, status);
+  else if (mode == Q2048_MERGE_BLEND)
+    hipLaunchKernelGGL((k_table_fold<FOLD, Q2048_MERGE_BLEND>), grid, dim3(kBlock), 0, stream, src, cap, dst, mask, w,
+                       one_minus_w, counters, status);
+  else
+    hipLaunchKernelGGL((k_table_fold<FOLD, Q2048_MERGE_MAXABS>), grid, dim3(kBlock), 0, stream, src, cap, dst, mask, w,
+                       one_minus_w, counters, status);
+}
+
 // Placement probe: `steps` scattered device-scope atomic ORs of 0 per lane into key words chosen
 // like the rollout chooses rows -- the table's write-side request pattern with no effect on its
 // contents (x | 0 == x).  The host times it: where in device memory a table lies moves the
@@ -3054,6 +3151,33 @@ int q2048_table_merge(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, 
   const float one_minus_w = 1.0f - w;
   if (key_words == 1) Q2048_LAUNCH_MERGE(1);
   else Q2048_LAUNCH_MERGE(2);
+  return launch_status();
+}
+
+int q2048_table_fold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, int src_cap_log2, int key_words, int fold,
+                     int mode, float w, uint64_t* counters, uint32_t* status, void* stream) {
+  if (!dst || !src || !counters) return Q2048_ERR_NULL;
+  if (key_words == 2) return Q2048_ERR_UNSUPPORTED;                    // (5x5 has no folded table)
+  if (key_words != 1) return Q2048_ERR_SIZE;
+  if (dst_cap_log2 < 4 || dst_cap_log2 > 40 || src_cap_log2 < 4 || src_cap_log2 > 40) return Q2048_ERR_SIZE;
+  if (!aligned16(dst) || !aligned16(src)) return Q2048_ERR_ALIGN;
+  if (fold != Q2048_FOLD_MEAN && fold != Q2048_FOLD_MEAN_TRAINED && fold != Q2048_FOLD_SUM && fold != Q2048_FOLD_MAXABS)
+    return Q2048_ERR_FLAGS;
+  if (mode != Q2048_MERGE_ADD && mode != Q2048_MERGE_BLEND && mode != Q2048_MERGE_MAXABS) return Q2048_ERR_FLAGS;
+  if (!std::isfinite(w) || (mode == Q2048_MERGE_BLEND && !(w >= 0.0f && w <= 1.0f))) return Q2048_ERR_RANGE;
+  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), s0 = reinterpret_cast<uintptr_t>(src);
+  const uintptr_t d1 = d0 + (sizeof(q2048_slot) << dst_cap_log2), s1 = s0 + (sizeof(q2048_slot) << src_cap_log2);
+  if (s0 < d1 && d0 < s1) return Q2048_ERR_RANGE;                      // the two tables overlap (src == dst included)
+  const u64 cap = 1ull << src_cap_log2, mask = (1ull << dst_cap_log2) - 1ull;
+  const u64 want = (cap + kBlock - 1) / kBlock;
+  const dim3 grid((unsigned)(want < 2048 ? want : 2048));              // the merge's grid: a grid-stride pass over src
+  const float one_minus_w = 1.0f - w;
+  u64* ctr = reinterpret_cast<u64*>(counters);
+  const hipStream_t s = (hipStream_t)stream;
+  if (fold == Q2048_FOLD_MEAN) launch_fold<Q2048_FOLD_MEAN>(mode, grid, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
+  else if (fold == Q2048_FOLD_MEAN_TRAINED) launch_fold<Q2048_FOLD_MEAN_TRAINED>(mode, grid, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
+  else if (fold == Q2048_FOLD_SUM) launch_fold<Q2048_FOLD_SUM>(mode, grid, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
+  else launch_fold<Q2048_FOLD_MAXABS>(mode, grid, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
   return launch_status();
 }
 

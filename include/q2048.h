@@ -793,6 +793,52 @@ int q2048_table_import(q2048_slot *table, int cap_log2, const uint64_t *keys, co
 int q2048_table_merge(q2048_slot *dst, int dst_cap_log2, const q2048_slot *src, int src_cap_log2,
                       int key_words, int mode, float w, uint64_t *counters, uint32_t *status, void *stream);
 
+/* Folds a PLAIN table into a SYMMETRY-FOLDED one on the device (Q2048_FLAG_SYMMETRIC above: images, canonical image,
+ * pi_g): the way into a folded table for a learner that was trained plain.  `src` is a plain 4x4 table, `dst` a folded
+ * one that may already hold rows.  The rows of a board's up to eight mirror images become ONE row, combined by `fold`,
+ * and that row finds or creates the row of the canonical key in `dst`, combined with it by `mode` and `w` exactly as
+ * q2048_table_merge combines a source row (its arithmetic, its created-row rule, its status bits).  The merge's
+ * sibling; arrived without an ABI bump, detected by its symbol.  The result depends on the two tables' ROWS only --
+ * not on slot positions, not on scheduling -- and a float32 model on the host gives the same bits.
+ *   ORBIT     For a source key m, c = the canonical key of m.  The MEMBERS of c's orbit are image_h(c), h = 0..7, in
+ *             ascending h; an h whose key equals that of a smaller h is skipped (boards with a stabiliser have 4, 2 or
+ *             1 distinct images).  The PRESENT members are the ones that have a row in `src`.
+ *   FRAME     A member's row enters the canonical frame by the member's own g -- the smallest g with
+ *             image_g(member) = c, the convention of the fused rollout when it meets that board:
+ *             Qc[pi_g(a)] = Q_member[a].
+ *   fold      The present members' canonical-frame rows are combined per action, in member order.  float32, every sum
+ *             and every product rounded on its own; the first entry that joins is taken as it is (no 0 + x); the mean's
+ *             division is a multiplication by the constant float32(1.0 / k), k = 1..8.
+ *             Q2048_FOLD_MEAN          the sum over the k present members, times float32(1.0 / k).
+ *             Q2048_FOLD_MEAN_TRAINED  per action the same over the members whose entry is not exactly 0 (+0 or -0),
+ *                                      k counting those; +0 when none is -- an untrained entry does not dilute a
+ *                                      trained one.
+ *             Q2048_FOLD_SUM           the sum over the present members.
+ *             Q2048_FOLD_MAXABS        per action the entry of larger magnitude; on equal magnitude the earlier
+ *                                      member's.
+ *   mode, w   as q2048_table_merge, with the orbit's row in the place of the source row.
+ *   counters  device uint64[5], ADDED to: [0] occupied src rows read, [1] orbits (each has exactly one leading row),
+ *             [2] rows created in dst, [3] rows combined with an existing dst row, [4] orbits dropped (no slot within
+ *             the probe limit); [1] = [2] + [3] + [4].
+ *   status    may be NULL; Q2048_STATUS_TABLE_FULL / Q2048_STATUS_DEEP_ROW as q2048_table_merge.
+ * One streaming pass over `src`, and for every occupied slot lookups of the orbit's other members in `src` (up to the
+ * bulk probe limit of 2^14 positions): a row that finds a present member ahead of itself stops, the orbit's first
+ * present member collects the rest and performs the orbit's one write, so exactly one lane writes each dst row and no
+ * float atomic is needed.  Stream-ordered.  Nothing else may write `src` or touch `dst` while the call is in flight.
+ * `src` is never written and its `reserved` words are never read (line summaries in it are harmless); the `reserved`
+ * words of `dst` are untouched, and its line summaries are stale afterwards, as after a merge.  Keys salted by
+ * Q2048_FLAG_INDEPENDENT cannot be told from board keys: they fold to nonsense, and the caller must not pass them.
+ * Errors, in this order: dst, src or counters NULL -> Q2048_ERR_NULL; key_words == 2 -> Q2048_ERR_UNSUPPORTED (5x5 has
+ * no folded table); key_words not 1 or 2, or a cap_log2 outside 4..40 -> Q2048_ERR_SIZE; a table not 16-byte aligned
+ * -> Q2048_ERR_ALIGN; an unknown fold or mode -> Q2048_ERR_FLAGS; w not finite, or outside [0, 1] with
+ * Q2048_MERGE_BLEND -> Q2048_ERR_RANGE; the two tables' byte ranges overlap -> Q2048_ERR_RANGE. */
+#define Q2048_FOLD_MEAN 0
+#define Q2048_FOLD_MEAN_TRAINED 1
+#define Q2048_FOLD_SUM 2
+#define Q2048_FOLD_MAXABS 3
+int q2048_table_fold(q2048_slot *dst, int dst_cap_log2, const q2048_slot *src, int src_cap_log2, int key_words,
+                     int fold, int mode, float w, uint64_t *counters, uint32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

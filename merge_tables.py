@@ -14,9 +14,20 @@ travels through a Python dict.
          maxabs           per action the value of largest magnitude (an untrained entry is exactly 0)
          first / last     where inputs share a state, the first / the last input's row wins; other rows are copied
 
+  --fold mean | mean_trained | sum | maxabs
+                          the output is a SYMMETRY-FOLDED table (train.py --symmetric): every plain input is folded
+                          on its way in -- the rows of a board's eight mirror images become the one row of their
+                          canonical image, combined per action by the mean over the images that have a row / over the
+                          images whose entry was ever trained / the sum / the entry of largest magnitude
+                          (q2048_table_fold, `BatchedQLearningAgent.fold_from`) -- and --mode acts between inputs as
+                          before.  Inputs that are folded already merge as they are, so plain and folded files may
+                          be mixed.  One plain input with --fold is the converter of a plain file.  Without --fold a
+                          mix is refused and nothing is folded.
+
     python train.py --gpus 8 --num-envs 8388608 --episodes 40 --save models/q.pt
     python merge_tables.py --out models/q_merged.pt models/q.pt.rank*
     python evaluate.py --model models/q_merged.pt
+    python merge_tables.py --fold mean_trained --out models/q_folded.pt models/q_plain.pt
 
 Hyper-parameters, epsilon schedule, seed and training progress come from the first input; the statistics vectors are
 summed and the draw counter is the largest of the inputs'.  Prints one JSON line.
@@ -42,6 +53,8 @@ def parse_args(argv=None):
     p.add_argument("inputs", nargs="+", help="files written by train.py --save (q.pt.rank0 q.pt.rank1 ...)")
     p.add_argument("--out", required=True, help="the merged learner (loads like any file of train.py --save)")
     p.add_argument("--mode", choices=["mean", "sum", "maxabs", "first", "last"], default="mean")
+    p.add_argument("--fold", choices=["mean", "mean_trained", "sum", "maxabs"], default=None,
+                   help="write a symmetry-folded table: plain inputs are folded on their way in (see above)")
     p.add_argument("--device", default="cuda", help='"cuda[:i]", or "cpu" for the host twin of the kernels')
     return p.parse_args(argv)
 
@@ -59,16 +72,17 @@ def main(argv=None):
     t0 = time.time()
     K = len(args.inputs)
     # pass 1, headers only: one board size, shared tables, and an upper bound of the rows the result can hold
-    first, rows_in, stats_i, stats_f, ctr = None, [], None, None, 0
+    first, rows_in, folded_in, stats_i, stats_f, ctr = None, [], [], None, None, 0
     for path in args.inputs:
         sd = torch.load(path, map_location="cpu", weights_only=False)
         if first is None:
             first = {k: v for k, v in sd.items() if k not in ("keys", "q", "table", "env", "visit_rows")}
         if int(sd["board_size"]) != int(first["board_size"]):
             raise SystemExit(f"{path}: board size {sd['board_size']}, {args.inputs[0]} has {first['board_size']}")
-        if bool(sd.get("symmetric", False)) != bool(first.get("symmetric", False)):
+        folded_in.append(bool(sd.get("symmetric", False)))
+        if args.fold is None and folded_in[-1] != folded_in[0]:
             raise SystemExit(f"{path} and {args.inputs[0]}: a symmetry-folded table (train.py --symmetric) and a plain "
-                             "one cannot be merged")
+                             "one cannot be merged (--fold folds the plain ones)")
         if int(sd["flags"]) & FLAG_INDEPENDENT:
             raise SystemExit(f"{path} was trained with private rows per env (Q2048_FLAG_INDEPENDENT): its keys are "
                              "salted by env id and mean nothing in another learner's table")
@@ -79,23 +93,28 @@ def main(argv=None):
         del sd
     n = int(first["board_size"])
 
-    def agent_of(capacity_log2):
+    def agent_of(capacity_log2, symmetric):
         return pkg.BatchedQLearningAgent(1, learning_rate=first["lr"], discount_factor=first["gamma"],
                                          capacity_log2=capacity_log2, device=args.device, board_size=n,
                                          placement="plain", freeze_load=None, row_cache=False,
-                                         symmetric=bool(first.get("symmetric", False)))
+                                         symmetric=symmetric)
 
-    dst = agent_of(_capacity_for(sum(rows_in)))
+    if args.fold is not None and n != 4:
+        raise SystemExit(f"--fold: symmetry folding is built for board size 4 only, {args.inputs[0]} has {n}")
+    dst = agent_of(_capacity_for(sum(rows_in)), args.fold is not None or folded_in[0])
     mode, weight = {"mean": ("add", 1.0 / K), "sum": ("add", 1.0), "maxabs": ("maxabs", 1.0),
                     "first": ("blend", 0.0), "last": ("blend", 1.0)}[args.mode]
     merges = []
-    for path, rows in zip(args.inputs, rows_in):
+    for path, rows, folded in zip(args.inputs, rows_in, folded_in):
         sd = torch.load(path, map_location="cpu", weights_only=False)
         sd.pop("visit_rows", None)                    # (the envs' visit rows belong to the run, not to the table)
-        scratch = agent_of(int(sd["capacity_log2"]) if "table" in sd else _capacity_for(rows))
+        scratch = agent_of(int(sd["capacity_log2"]) if "table" in sd else _capacity_for(rows), folded)
         scratch.load_state_dict(sd)
         del sd
-        merges.append(dst.merge_from(scratch, mode=mode, weight=weight))
+        if dst.symmetric and not folded:              # (--fold: a plain input enters through its orbits)
+            merges.append(dst.fold_from(scratch, fold=args.fold, mode=mode, weight=weight))
+        else:
+            merges.append(dst.merge_from(scratch, mode=mode, weight=weight))
         if dst.on_gpu:
             torch.cuda.synchronize(dst.device)
         del scratch                                   # at most two tables at a time
@@ -104,11 +123,18 @@ def main(argv=None):
     out.update(first)                                 # hyper-parameters, schedule, seed, progress: the first input's
     out.update({"capacity_log2": dst.capacity_log2, "stats_i": stats_i, "stats_f": stats_f, "ctr": ctr,
                 "merged": {"inputs": [os.path.basename(p) for p in args.inputs], "mode": args.mode}})
+    if args.fold is not None:
+        out["symmetric"] = True
+        out["merged"].update({"fold": args.fold, "folded_inputs": [os.path.basename(p) for p, f in
+                                                                  zip(args.inputs, folded_in) if not f]})
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     torch.save(out, args.out, pickle_protocol=4)      # (protocol 4: rows of a long run pass 4 GiB, as train.py --save)
-    print(json.dumps({"out": args.out, "mode": args.mode, "device": args.device, "board_size": n, "inputs": args.inputs,
-                      "rows_in": rows_in, "merges": merges, "rows_out": check["rows"],
-                      "capacity_log2": dst.capacity_log2, "seconds": round(time.time() - t0, 3)}))
+    report = {"out": args.out, "mode": args.mode, "device": args.device, "board_size": n, "inputs": args.inputs,
+              "rows_in": rows_in, "merges": merges, "rows_out": check["rows"],
+              "capacity_log2": dst.capacity_log2, "seconds": round(time.time() - t0, 3)}
+    if args.fold is not None:
+        report["fold"] = args.fold
+    print(json.dumps(report))
     return out
 
 

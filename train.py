@@ -106,6 +106,12 @@ def parse_args(argv=None):
                    "the table, the statistics, the epoch counter, epsilon where the saved run left it (the "
                    "schedule's phase limits are rebuilt from this run's --episodes) and, when the batch has "
                    "the saved shape, the boards -- save at epoch k + resume to N trains what N epochs train")
+    p.add_argument("--fold", choices=["mean", "mean_trained", "sum", "maxabs"], default="",
+                   help="with --resume PLAIN --symmetric: the file holds a PLAIN table; fold it into this run's "
+                        "symmetry-folded one (q2048_table_fold: the rows of a board's eight mirror images become one, per "
+                        "action the mean over the images with a row / over the images whose entry was ever trained / "
+                        "the sum / the entry of largest magnitude).  Schedule, statistics and draw counter resume as "
+                        "without it; the saved visit rows are dropped.  Without --fold a plain file is refused")
     p.add_argument("--launch-timeout", type=float, default=86400.0,
                    help="self-launched ranks (--gpus N > 1 outside torchrun) are stopped after this many seconds")
     p.add_argument("--stop-epoch", type=int, default=0, help="stop (and --save) once this many epochs of the "
@@ -227,7 +233,10 @@ def train_batched(args, pkg):
     epoch0 = 0
     if args.resume:
         sd = _load(args.resume, rank)
-        agent.load_state_dict(sd)
+        if args.fold:
+            _fold_into(pkg, agent, sd, args, dev)
+        else:
+            agent.load_state_dict(sd)
         epoch0 = _resume_schedule(agent, sd, args, shard.total_envs)
         env_sd = sd.get("env")
         if env_sd is not None and tuple(env_sd["boards"].shape) == tuple(env.boards.shape) and \
@@ -399,6 +408,31 @@ def _resume_schedule(agent, sd, args, total_envs) -> int:
     return min(args.episodes, done // max(total_envs, 1))
 
 
+def _fold_into(pkg, agent, sd, args, dev):
+    """--resume PLAIN --symmetric --fold: everything but the table loads as always (an empty folded table), then the
+    file's plain table is loaded into a scratch agent and folded into the run's (BatchedQLearningAgent.fold_from)."""
+    import numpy as np
+
+    if sd.get("symmetric", False):
+        raise SystemExit(f"--fold: {args.resume} already holds a symmetry-folded table; resume it without --fold")
+    if int(sd["flags"]) & 1:
+        raise SystemExit(f"--fold: {args.resume} was trained with private rows per env (Q2048_FLAG_INDEPENDENT): its "
+                         "keys are salted by env id and do not decode to boards")
+    if int(sd["board_size"]) != 4:
+        raise SystemExit(f"--fold: {args.resume} has board size {sd['board_size']}; symmetry folding is built for 4 only")
+    table = {k: sd[k] for k in ("keys", "q", "table") if k in sd}
+    head = {k: v for k, v in sd.items() if k not in ("keys", "q", "table", "visit_rows")}
+    head.update({"symmetric": True, "keys": np.zeros((0,), np.uint64), "q": np.zeros((0, 4), np.float32)})
+    agent.load_state_dict(head)                   # schedule, statistics, counters; the table starts empty
+    rows = len(table["q"]) if "q" in table else 0
+    cap = int(sd["capacity_log2"]) if "table" in table else max(16, (2 * max(rows, 1) - 1).bit_length())
+    scratch = pkg.BatchedQLearningAgent(1, learning_rate=sd["lr"], discount_factor=sd["gamma"], capacity_log2=cap,
+                                        device=dev, board_size=4, placement="plain", freeze_load=None, row_cache=False)
+    scratch.load_state_dict({**head, **table, "symmetric": False})
+    out = agent.fold_from(scratch, fold=args.fold, mode="add", weight=1.0)
+    print(f"folded {args.resume}: {out['read']} plain rows -> {out['created']} rows ({args.fold})", flush=True)
+
+
 def _load(path, rank):
     import torch
 
@@ -432,6 +466,11 @@ def main(argv=None):
         if args.num_envs == 1 and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
             raise SystemExit("--symmetric needs the batched mode (--num-envs > 1): the one-state loop learns through "
                              "choose_action / update_q_value, which do not take the flag")
+    if args.fold:
+        if not args.symmetric:
+            raise SystemExit("--fold folds a plain file into a symmetry-folded table: it needs --symmetric")
+        if not args.resume:
+            raise SystemExit("--fold says how the plain file of --resume is folded: it needs --resume")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # the parent of the job has made no GPU call: one fresh process per rank (launch.py)
         spec = importlib.util.spec_from_file_location(
