@@ -110,8 +110,9 @@ def legal(pkg, dev, boards):
     return m.cpu().numpy()
 
 
-def make(pkg, dev, B, symmetric, independent=False, cap=16, seed=11, id0=500, eps=0.3, **kw):
-    env = pkg.BatchedGame2048Env(B, 4, dev, seed, id0)
+def make(pkg, dev, B, symmetric, independent=False, cap=16, seed=11, id0=500, eps=0.3, profile="shaped",
+         reset_shaping_state=False, **kw):
+    env = pkg.BatchedGame2048Env(B, 4, dev, seed, id0, profile=profile, reset_shaping_state=reset_shaping_state)
     agent = pkg.BatchedQLearningAgent(100, learning_rate=0.1, discount_factor=0.95, exploration_rate=eps,
                                       capacity_log2=cap, seed=seed, env_id0=id0, device=dev, independent=independent,
                                       placement="plain", symmetric=symmetric, **kw)
@@ -119,7 +120,8 @@ def make(pkg, dev, B, symmetric, independent=False, cap=16, seed=11, id0=500, ep
 
 
 def twin_of(pkg, env):
-    other = pkg.BatchedGame2048Env(env.num_envs, 4, env.device, env.seed, env.env_id0)
+    other = pkg.BatchedGame2048Env(env.num_envs, 4, env.device, env.seed, env.env_id0, profile=env.profile,
+                                   reset_shaping_state=env.reset_shaping_state)
     other.load_state_dict(env.state_dict())
     return other
 
@@ -217,14 +219,21 @@ def test_action_permutation_is_the_envs_own(pkg, dev):
 # ---------------------------------------------------------------------------------------------
 # 2. the fused learner == a plain agent driven by the four calls on canonical boards
 # ---------------------------------------------------------------------------------------------
-def model_run(pkg, O, dev, env, model, steps, eps):
+def model_run(pkg, O, dev, env, model, steps, eps, records=None, states=None):
     """Per step: numpy canon of s, the plain agent's rows of canon(s) permuted to the env frame, the action from the
     draws (explore iff x0 < ceil(eps * 2^32), then x1 >> 30, else the first maximum), env.step, update_q_value on the
-    canonical boards with the permuted action, reset(done)."""
+    canonical boards with the permuted action, reset(done).  The env's profile and the agent's write mode are those
+    of `env` and `model`.
+    `records` (a list): for every env whose step ended an episode, the record the episode log gets -- (env id,
+    episode, the ENV's action, reward, max_log2, score, total return, q), q being the model's row of canon(s) read
+    AFTER update_q_value and permuted to the env's frame, as four float32 bit patterns -- and, ninth, g of s.
+    `states` (a list): the boards [B, 16] every step started from."""
     thr = math.ceil(eps * 4294967296.0)
     B, explored, episodes = env.num_envs, 0, 0
     for _ in range(steps):
         s = env.boards.cpu().numpy()
+        if states is not None:
+            states.append(s.copy())
         cs, g, _ = canon(s)
         q = env_rows(model.q_values(torch.from_numpy(cs).to(dev)).cpu().numpy(), g)
         acts = np.zeros(B, dtype=np.uint8)
@@ -240,6 +249,13 @@ def model_run(pkg, O, dev, env, model, steps, eps):
         model.update_q_value(torch.from_numpy(cs).to(dev), torch.from_numpy(pi(g, acts).astype(np.uint8)).to(dev),
                              reward, torch.from_numpy(cn).to(dev), done)
         episodes += int(done.sum().item())
+        if records is not None and bool(done.any()):
+            over = np.flatnonzero(done.cpu().numpy())
+            live = env_rows(model.q_values(torch.from_numpy(cs).to(dev)).cpu().numpy(), g).view(np.uint32)
+            aux, rew, mx = env.aux_fields(), reward.cpu().numpy(), env.max_log2.cpu().numpy()   # (before the reset)
+            for i in over.tolist():
+                records.append((env.env_id0 + i, int(aux["episode"][i]), int(acts[i]), float(rew[i]), int(mx[i]),
+                                int(aux["score"][i]), float(aux["ep_return"][i]), tuple(live[i].tolist()), int(g[i])))
         env.reset(done)
     return explored, episodes
 
@@ -305,10 +321,10 @@ def test_shared_table_key_set_is_the_folded_plain_one(pkg, dev):
 # ---------------------------------------------------------------------------------------------
 # 4. closed key set: line summaries, drops, checkpoint / resume with visit rows
 # ---------------------------------------------------------------------------------------------
-def frozen_learner(pkg, dev, line_summaries):
+def frozen_learner(pkg, dev, line_summaries, strict_td=False):
     """Private rows, epsilon 0.3, launches of 8 until the agent's own policy closes the key set (2^14 slots at
     freeze_load 0.5) -- private rows make the run a function of its inputs, so two calls give the same learner."""
-    env, agent = make(pkg, dev, 256, True, independent=True, cap=14, freeze_load=0.5)
+    env, agent = make(pkg, dev, 256, True, independent=True, cap=14, freeze_load=0.5, strict_td=strict_td)
     agent.line_summaries = line_summaries
     with _quiet():
         for _ in range(40):
@@ -372,8 +388,8 @@ def dead_board():
     return torch.tensor([1 + ((r + c) & 1) for r in range(4) for c in range(4)], dtype=torch.uint8)
 
 
-def trained(pkg, dev, B=256):
-    env, agent = make(pkg, dev, B, True)
+def trained(pkg, dev, B=256, **kw):
+    env, agent = make(pkg, dev, B, True, **kw)
     agent.fused_rollout(env, 200)
     env.boards[:3] = dead_board().to(dev)[None, :]
     return env, agent
