@@ -22,9 +22,9 @@ LIB_PATH = os.environ.get("Q2048_LIB_PATH") or os.path.join(CSRC, "libq2048_hip.
 # tools/ and two parity tests load it explicitly, the package never does
 EXPERIMENTS_LIB_PATH = os.path.abspath(os.path.join(_PKG, "..", "tools", "variants", "libq2048_hip_exp.so"))
 HOST_LIB_PATH = os.path.join(CSRC, "libq2048_host.so")
-HOST_DEPS = ["q2048_host.cpp", "q2048_core.hpp", "q2048_core5.hpp", "q2048_luts.inc"]
+HOST_DEPS = ["q2048_host.cpp", "q2048_core.hpp", "q2048_core5.hpp", "q2048_luts.inc", "q2048_abi.hpp"]
 SOURCES = ["q2048_kernels.hip"]
-DEPS = ["q2048_kernels.hip", "q2048_core.hpp", "q2048_core5.hpp", "q2048_luts.inc"]
+DEPS = ["q2048_kernels.hip", "q2048_core.hpp", "q2048_core5.hpp", "q2048_luts.inc", "q2048_abi.hpp"]
 
 OK, PENDING, ERR_ALLOC, ERR_BUSY = 0, 1, -8, -10
 GROW_VERIFY_COUNT = 1

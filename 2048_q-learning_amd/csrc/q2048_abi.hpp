@@ -1,0 +1,77 @@
+// q2048_abi.hpp -- the argument checks of the C ABI (include/q2048.h) and the text of its error codes.
+//
+// Host code only, compiled into both libraries (libq2048_hip.so: q2048_kernels.hip; libq2048_host.so:
+// q2048_host.cpp), so that an argument one of them refuses the other refuses too, with the same code and in the
+// same order of precedence.  Everything has internal linkage: the libraries export the C ABI and nothing of this.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "q2048.h"
+
+namespace q2048 {
+
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline int check_batch(int64_t B, int n) {
+  if (n != 4 && n != 5) return Q2048_ERR_UNSUPPORTED;
+  // the device launches one block per 256 envs and HIP caps grid.x at 2^31 - 1 blocks
+  if (B < 0 || B > (int64_t)0x7fffffff * 256) return Q2048_ERR_SIZE;
+  return Q2048_OK;
+}
+static inline int check_table(const void* table, int cap_log2) {
+  if (table == nullptr) return Q2048_ERR_NULL;
+  if (cap_log2 < 4 || cap_log2 > 40) return Q2048_ERR_SIZE;
+  if (!aligned16(table)) return Q2048_ERR_ALIGN;
+  return Q2048_OK;
+}
+// flag bits outside the ABI are an argument error (experiment builds of the HIP library also take bits 8..23).
+// (Q2048_FLAG_LINE_SUMMARY on the host: 4x4 accepted and not used -- slot by slot, same results; 5x5 with a side
+// array: used.)
+constexpr uint32_t kAbiFlags = Q2048_FLAG_INDEPENDENT | Q2048_FLAG_SINGLE_ENV | Q2048_FLAG_TD_CAS |
+                               Q2048_FLAG_ENV_DQN | Q2048_FLAG_RESET_SHAPING | Q2048_FLAG_PLAY_ONLY |
+                               Q2048_FLAG_NO_LEARN | Q2048_FLAG_NO_NEW_ROWS | Q2048_FLAG_LINE_SUMMARY;
+// (`also`: Q2048_FLAG_SYMMETRIC, for the entry points that take it -- the fused rollouts, the player, q_lookup)
+static inline int check_flags(uint32_t flags, uint32_t refused = 0u, uint32_t also = 0u) {
+  uint32_t allowed = kAbiFlags | also;
+#ifdef Q2048_EXPERIMENTS
+  allowed |= 0x00ffff00u;
+#endif
+  return ((flags & ~allowed) || (flags & refused)) ? Q2048_ERR_FLAGS : Q2048_OK;
+}
+
+// What q2048_table_merge and q2048_table_fold check in common, in their order of precedence: NULL, SIZE, ALIGN,
+// FLAGS, RANGE.  `sizes_ok` / `rules_ok` are the caller's verdict on its own arguments of the same rank as the
+// capacities (key_words) / as the merge mode (the fold rule).
+static inline int check_merge(const void* dst, int dst_cap_log2, const void* src, int src_cap_log2, const void* counters,
+                              bool sizes_ok, bool rules_ok, int mode, float w) {
+  if (!dst || !src || !counters) return Q2048_ERR_NULL;
+  if (dst_cap_log2 < 4 || dst_cap_log2 > 40 || src_cap_log2 < 4 || src_cap_log2 > 40 || !sizes_ok) return Q2048_ERR_SIZE;
+  if (!aligned16(dst) || !aligned16(src)) return Q2048_ERR_ALIGN;
+  if (!rules_ok || (mode != Q2048_MERGE_ADD && mode != Q2048_MERGE_BLEND && mode != Q2048_MERGE_MAXABS)) return Q2048_ERR_FLAGS;
+  if (!std::isfinite(w) || (mode == Q2048_MERGE_BLEND && !(w >= 0.0f && w <= 1.0f))) return Q2048_ERR_RANGE;
+  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), s0 = reinterpret_cast<uintptr_t>(src);
+  const uintptr_t d1 = d0 + (sizeof(q2048_slot) << dst_cap_log2), s1 = s0 + (sizeof(q2048_slot) << src_cap_log2);
+  if (s0 < d1 && d0 < s1) return Q2048_ERR_RANGE;                      // the two tables overlap (src == dst included)
+  return Q2048_OK;
+}
+
+// q2048_strerror
+static inline const char* error_text(int code) {
+  switch (code) {
+    case Q2048_OK: return "ok";
+    case Q2048_ERR_NULL: return "a required pointer is NULL";
+    case Q2048_ERR_SIZE: return "size out of range (batch, steps, cap_log2 or key_words)";
+    case Q2048_ERR_ALIGN: return "boards/aux/table must be 16-byte aligned";
+    case Q2048_ERR_UNSUPPORTED: return "unsupported here (board side other than 4 or 5, or an entry point this library or geometry does not have)";
+    case Q2048_ERR_LAUNCH: return "HIP launch failed";
+    case Q2048_ERR_RANGE: return "scalar out of range (eps in [0,1], lr and gamma finite)";
+    case Q2048_ERR_FLAGS: return "flag bits this entry point does not take";
+    case Q2048_ERR_ALLOC: return "device memory could not be reserved, created or mapped";
+    case Q2048_ERR_VERIFY: return "a table failed its self-check (a fresh table not all zeros, or rows lost while growing)";
+    case Q2048_ERR_BUSY: return "the table already takes part in a growth (finish or abort that one first)";
+    case Q2048_PENDING: return "still working (not an error)";
+    default: return "unknown error";
+  }
+}
+
+}  // namespace q2048

@@ -6,7 +6,9 @@
 //   * by hipcc for gfx950 (the kernels in q2048_kernels.hip), and
 //   * by g++ for tests/hostcheck, which checks these exact functions against the CPU oracle
 //     exhaustively before anything runs on a GPU.
-// It is NOT a CPU fallback: nothing in the product calls the host instantiation.
+// It is NOT a CPU fallback: the host instantiation serves tests/hostcheck and the explicit device "cpu"
+// (q2048_host.cpp), which is built from these functions and nothing else.
+// It also holds the one definition of the Q-table's format ("THE TABLE'S FORMAT" below, keys in q2048_core5.hpp).
 //
 // What each function replaces in the reference (paths under QLearningBase/):
 //   move()            environment/Game2048_env.py:22-63  (rotate/move_left/rotate back)
@@ -602,6 +604,95 @@ Q_HD uint64_t mix64(uint64_t h) {
 }
 // independent-learners mode: every env owns private rows of the shared table
 Q_HD uint64_t lane_salt(uint64_t env_id) { return mix64(env_id + 0x2048ull) | 1ull; }
+
+// ------------------------------------------------------------------------------------------
+// THE TABLE'S FORMAT (q2048_slot of include/q2048.h): where a key's row lies, how far a probe
+// goes, what a row and a row-cache record are.  The HIP library and the CPU twin both compile THIS definition --
+// that is what makes a host table a device table byte for byte -- and tests/test_core_host.py holds it against
+// tests/table_model.py.  (The keys themselves, Geo<N>::Key, are in q2048_core5.hpp: the 5x5 one needs Board5.)
+// ------------------------------------------------------------------------------------------
+// Probe limits: beyond them a lookup reads "absent" and an update drops (counted; status TABLE_FULL).  They are
+// what makes a probe of a FULL table end, not a load policy: at load 0.93 the longest cluster of a 2^22-slot
+// table is already thousands of slots (ln n / (a - 1 - ln a)), and round 3's limit of 256 made "full" mean
+// "load ~0.85" (a racing import at load 0.93 dropped rows).  Bulk moves of rows (import, the rehash of a growth)
+// and q2048_q_lookup take kMaxProbe = 2^14 slots: they must place and find every row of a table the caller sized.
+// The learning paths (rollouts, choose, update) take kRolloutProbe = 2^10: a lane of a rollout probes twice per
+// step, and on a fixed table that has filled up 2^14 dependent 16-byte loads per probe made a launch orders of
+// magnitude slower before TABLE_FULL became visible; 2^10 bounds that at ~load 0.93, where an
+// absent key's expected probe is 100 slots already.  (Or the whole table if smaller.)
+constexpr uint32_t kMaxProbe = 1u << 14, kRolloutProbe = 1u << 10;
+constexpr int kMaxCas = 16;      // TD compare-and-swap attempts before the update is simply stored
+Q_HD uint32_t probe_limit(uint64_t mask, uint32_t maxp) {
+  return mask >= (uint64_t)maxp ? maxp : (uint32_t)mask + 1u;
+}
+// what a probe returns instead of a slot index (>= 0): ~h (< 0), h = the empty slot that ended it -- the place an
+// insert of the key would claim -- or kNoSlot when the probe limit was hit
+constexpr int64_t kNoSlot = INT64_MIN;
+
+// Probe sequence of a key: BUCKETISED.  A miss moves the whole 128-byte line (4 slots) the probed
+// slot lies in, and what a lookup costs is the number of lines it touches, so a
+// collision is resolved inside the line already fetched: the sequence starts at the home slot
+// (hash & mask), visits the other three slots of that line cyclically -- L2 hits -- and only then
+// moves on to the next line, same order.  Plain linear probing left the line at the first collision
+// of every key whose home is a line's last slot.  (Slots are 32 B; with a 128-byte aligned table
+// a group of four is exactly one line.  Any 16-byte aligned table works.)
+struct Seq { uint64_t line0, lmask; uint32_t off; };
+Q_HD Seq seq_of(uint64_t hash, uint64_t mask) {
+  return Seq{(hash & mask) >> 2, mask >> 2, (uint32_t)hash & 3u};
+}
+Q_HD uint64_t seq_slot(const Seq& s, uint32_t p) {   // p-th slot of the sequence
+  return (((s.line0 + (uint64_t)(p >> 2)) & s.lmask) << 2) | (uint64_t)((s.off + p) & 3u);
+}
+Q_HD uint32_t seq_pos(const Seq& s, uint64_t slot) { // inverse, for a slot on the sequence
+  return ((uint32_t)(((slot >> 2) - s.line0) & s.lmask) << 2) | (((uint32_t)slot - s.off) & 3u);
+}
+
+struct Row { float q0, q1, q2, q3; };
+Q_HD float row_get(const Row& r, int a) {
+  return a == 0 ? r.q0 : a == 1 ? r.q1 : a == 2 ? r.q2 : r.q3;
+}
+Q_HD void row_set(Row& r, int a, float v) {          // (selects, not an address: a carried row stays in registers)
+  r.q0 = a == 0 ? v : r.q0; r.q1 = a == 1 ? v : r.q1;
+  r.q2 = a == 2 ? v : r.q2; r.q3 = a == 3 ? v : r.q3;
+}
+// a row stored in the canonical frame, read in the frame of the env whose board has the canonical image g:
+// Q_env[a] = Q_canon[pi_g(a)] (Q2048_FLAG_SYMMETRIC).  (static: g++ keeps it out of line in places, and there it
+// stays a local symbol of the CPU twin, as it was)
+static Q_HD Row row_env(const Row& r, uint32_t g) {
+  return Row{row_get(r, sym_action(g, 0)), row_get(r, sym_action(g, 1)), row_get(r, sym_action(g, 2)),
+             row_get(r, sym_action(g, 3))};
+}
+
+// Row cache of the 4-call API (optional, caller-owned, one record per env): what the fused rollout
+// carries in registers from one step to the next -- the row this env read as s' in its last
+// update, with its slot -- handed from one q_update call to the next q_choose / q_update through
+// HBM as a coalesced stream.  s of step t + 1 is s' of step t unless an episode began, so the
+// update then needs ONE scattered row read (s') instead of two, and a greedy choose none.  A
+// record is used only when its key equals the key of the board actually passed in (0 = empty), so
+// any calling pattern is correct; like the register-carried row it does not see what OTHER envs
+// wrote to that row since.
+template <int N> struct RowCache;
+template <> struct RowCache<4> { uint64_t key; float q[4]; uint64_t slot; };                                // 32 B
+template <> struct RowCache<5> { uint64_t key; float q[4]; uint64_t key_hi; uint64_t slot; uint64_t pad; }; // 48 B
+static_assert(sizeof(RowCache<4>) == 32 && sizeof(RowCache<5>) == 48, "ABI layout");
+
+// A record also carries, in the 24 bits above its 40-bit slot index, a TAG of the table it was read from (a hash
+// of the table's address and capacity): a record left by a launch on another table -- the table has grown, or the
+// caller switched tables and did not zero the cache -- never matches, so its slot index is never used against the
+// wrong table (records outlive launches since round 4 and were trusted on a key match alone).  A table
+// rewritten IN PLACE (zero-filled, imported into) keeps its tag: the caller zero-fills the cache then, as before.
+Q_HD uint64_t cache_tag(const void* table, uint64_t mask) {
+  return (mix64((uint64_t)reinterpret_cast<uintptr_t>(table) ^ (mask * 0x9E3779B97F4A7C15ull)) >> 40) << 40;
+}
+constexpr uint64_t kCacheSlotMask = (1ull << 40) - 1ull;
+// VISIT ROWS (Q2048_FLAG_NO_NEW_ROWS).  With the key set closed a state without a row reads as the zero row the
+// defaultdict would have created -- and while the env STAYS in that state (invalid moves) that fresh row learns as the
+// defaultdict's would (Agent/main.py:43): the lane keeps it in the registers that otherwise carry the table's row, so
+// that the first invalid move's negative reward sends argmax on to the next action instead of repeating action 0 until
+// the stall rule ends the episode.  It is never part of the table and ends when the env leaves the state.  Across a
+// launch boundary it travels like any carried row, through the row cache, as a ROWLESS record: slot field all ones
+// (no table of 2^40 slots exists).  Only calls that carry the flag write or accept such records.
+constexpr uint64_t kCacheRowless = kCacheSlotMask;
 
 // ------------------------------------------------------------------------------------------
 // LINE SUMMARIES of a table whose key set is closed (include/q2048.h, Q2048_FLAG_LINE_SUMMARY): one 64-bit

@@ -257,6 +257,63 @@ Q_HD Board5 unpack_key(const Key5& k) {
   return b;
 }
 
+// ------------------------------------------------------------------------------------------
+// geometry: board type and TABLE KEY of a board side (the rest of the table's format is in q2048_core.hpp; like
+// it, this is the one definition the HIP library and the CPU twin compile).  A key word of 0 marks an empty slot.
+// ------------------------------------------------------------------------------------------
+template <int N> struct Geo;
+template <> struct Geo<4> {
+  using BoardT = Board;
+  struct Key { uint64_t k0; };
+};
+template <> struct Geo<5> {
+  using BoardT = Board5;
+  struct Key { uint64_t k0, k1; };
+};
+Q_HD bool key_eq(const Geo<4>::Key& a, const Geo<4>::Key& b) { return a.k0 == b.k0; }
+Q_HD bool key_eq(const Geo<5>::Key& a, const Geo<5>::Key& b) { return a.k0 == b.k0 && a.k1 == b.k1; }
+// 64 hash bits of a key: the low ones choose the home slot, the top 16 the deterministic mode's
+// sort bucket (a function of the state alone -- not of where its row ended up)
+Q_HD uint64_t key_hash(const Geo<4>::Key& k) { return mix64(k.k0); }
+Q_HD uint64_t key_hash(const Geo<5>::Key& k) { return mix64(k.k0 ^ (k.k1 * 0x9E3779B97F4A7C15ull)); }
+template <class Key>
+Q_HD uint64_t key_home(const Key& k, uint64_t mask) { return key_hash(k) & mask; }
+
+// The key of a board.  Independent mode salts it with the env id (private rows per env).  `overflow()` is called
+// when a tile above 2^15 does not fit its nibble (4x4 only): each library raises Q2048_STATUS_TILE_OVERFLOW its own
+// way.  (A callable and not a flag for the caller to test afterwards: the kernels keep their atomic where it always
+// was, between packing and salting -- behind the whole key it changed the instruction schedule of every
+// symmetry-folded kernel.)
+template <class F>
+Q_HD Geo<4>::Key state_key(const Board& b, uint64_t salt, const F& overflow) {
+  bool ov;
+  const uint64_t k = pack_key(b, ov) ^ salt;
+  if (ov) overflow();
+  return Geo<4>::Key{k != 0u ? k : 1u};  // 0 marks an empty slot
+}
+template <class F>
+Q_HD Geo<5>::Key state_key(const Board5& b, uint64_t salt, const F&) {
+  const Key5 k = pack_key(b);  // both words carry bit 63, so neither is ever 0
+  return Geo<5>::Key{k.k0 ^ (salt & 0x7fffffffffffffffull), k.k1 ^ (mix64(salt) & 0x3fffffffffffffffull)};
+}
+// Q2048_FLAG_SYMMETRIC (SYM, 4x4 only): the key of the board's canonical image -- the smallest of the eight mirror
+// images' keys, q2048_core.hpp -- salted AFTER canonicalisation; g = which image it is (0 without SYM).  Registers
+// only: no LDS, no load, and no atomic but the caller's.
+template <bool SYM, class BoardT, class F>
+Q_HD auto state_key_as(const BoardT& b, uint64_t salt, uint32_t& g, const F& overflow) {
+  if constexpr (SYM) {
+    bool ov;
+    const Canon c = canonical_key(pack_key(b, ov));
+    if (ov) overflow();
+    g = c.g;
+    const uint64_t k = c.key ^ salt;
+    return Geo<4>::Key{k != 0u ? k : 1u};
+  } else {
+    g = 0u;
+    return state_key(b, salt, overflow);
+  }
+}
+
 // memory image: uint8[25] row-major log2 tiles <-> fields
 Q_HD Board5 board5_from_bytes(const uint8_t* p) {
   Board5 b;

@@ -2,9 +2,10 @@
 //
 // The SAME C ABI (include/q2048.h: same names, argument meaning, error codes) on HOST memory, built from
 // the same per-lane arithmetic the HIP kernels inline (q2048_core.hpp / q2048_core5.hpp: SWAR slide, spawn,
-// closed-form game-over, reward, Philox draws, epsilon-greedy, TD fold) and the same table (32-byte slots,
-// the same hash, the same bucketised probe sequence): a table trained here IS a device table, byte for
-// byte, and the other way round.  Envs are split into contiguous ranges over std::threads (one thread for
+// closed-form game-over, reward, Philox draws, epsilon-greedy, TD fold) and the same table: its format (keys,
+// hash, bucketised probe sequence, probe limits, rows, row-cache records) is defined once, in those two headers,
+// and the argument checks once, in q2048_abi.hpp -- a table trained here IS a device table, byte for byte, and
+// the other way round.  Envs are split into contiguous ranges over std::threads (one thread for
 // small batches); rows are claimed with a compare-and-swap on the key word and Q values written with
 // 4-byte stores, as on the device -- so B = 1 (and private rows, and the deterministic step at any B) is
 // the reference's sequential loop (Agent/main.py:80-109), and a shared table with several threads is the
@@ -31,26 +32,19 @@
 #include <unordered_map>
 #include <vector>
 
-#include "q2048.h"
+#include "q2048_abi.hpp"
 #include "q2048_core5.hpp"
 
 namespace {
 using namespace q2048;
 using u64 = unsigned long long;
 
-// as the device: the limits that make a probe of a FULL table end (bulk moves and lookups / the learning paths)
-constexpr uint32_t kMaxProbe = 1u << 14, kRolloutProbe = 1u << 10;
-constexpr int kMaxCas = 16;
 constexpr int kMaxAwait = 1 << 20;
 
 static_assert(sizeof(q2048_aux) == 16 && sizeof(q2048_slot) == 32 && sizeof(q2048_episode) == 48, "ABI layout");
 static_assert(sizeof(Aux) == sizeof(q2048_aux), "core/ABI aux mismatch");
 
-// ---- geometry -------------------------------------------------------------------------------------------------
-template <int N> struct Geo;
-template <> struct Geo<4> { using BoardT = Board; struct Key { u64 k0; }; static constexpr int kCells = 16; };
-template <> struct Geo<5> { using BoardT = Board5; struct Key { u64 k0, k1; }; static constexpr int kCells = 25; };
-
+// ---- memory images of a board and its aux (the geometry Geo<N> and the table key: q2048_core5.hpp) --------------------
 inline void load_board(const uint8_t* boards, int64_t i, Board& b) { std::memcpy(&b, boards + 16 * i, 16); }
 inline void load_board(const uint8_t* boards, int64_t i, Board5& b) { b = board5_from_bytes(boards + 25 * i); }
 inline void store_board(uint8_t* boards, int64_t i, const Board& b) { std::memcpy(boards + 16 * i, &b, 16); }
@@ -66,60 +60,23 @@ inline void st_aux(q2048_aux* aux, int64_t i, const Aux& a) {
 }
 inline void status_or(uint32_t* status, uint32_t bits) { __atomic_fetch_or(status, bits, __ATOMIC_RELAXED); }
 
-inline Geo<4>::Key state_key(const Board& b, u64 salt, uint32_t* status) {
-  bool ov;
-  u64 k = pack_key(b, ov) ^ salt;
-  if (ov) status_or(status, Q2048_STATUS_TILE_OVERFLOW);
-  return Geo<4>::Key{k == 0ull ? 1ull : k};
-}
-inline Geo<5>::Key state_key(const Board5& b, u64 salt, uint32_t*) {
-  const Key5 k = pack_key(b);
-  return Geo<5>::Key{k.k0 ^ (salt & 0x7fffffffffffffffull), k.k1 ^ (mix64(salt) & 0x3fffffffffffffffull)};
-}
-// Q2048_FLAG_SYMMETRIC (4x4): the key of the board's canonical image, salted AFTER canonicalisation; g = which image
+// state keys: the shared construction (q2048_core5.hpp), with this library's way to raise TILE_OVERFLOW
 template <bool SYM, class BoardT>
 inline auto state_key_as(const BoardT& b, u64 salt, uint32_t* status, uint32_t& g) {
-  if constexpr (SYM) {
-    bool ov;
-    const Canon c = canonical_key(pack_key(b, ov));
-    if (ov) status_or(status, Q2048_STATUS_TILE_OVERFLOW);
-    g = c.g;
-    const u64 k = c.key ^ salt;
-    return Geo<4>::Key{k == 0ull ? 1ull : k};
-  } else {
-    g = 0u;
-    return state_key(b, salt, status);
-  }
+  return q2048::state_key_as<SYM>(b, salt, g, [status] { status_or(status, Q2048_STATUS_TILE_OVERFLOW); });
+}
+template <class BoardT>
+inline auto state_key(const BoardT& b, u64 salt, uint32_t* status) {
+  uint32_t g;
+  return state_key_as<false>(b, salt, status, g);
 }
 template <int N>
 inline typename Geo<N>::Key state_key_sym(bool sym, const typename Geo<N>::BoardT& b, u64 salt, uint32_t* status, uint32_t& g) {
   if constexpr (N == 4) { if (sym) return state_key_as<true>(b, salt, status, g); }
   return state_key_as<false>(b, salt, status, g);
 }
-inline bool key_eq(const Geo<4>::Key& a, const Geo<4>::Key& b) { return a.k0 == b.k0; }
-inline bool key_eq(const Geo<5>::Key& a, const Geo<5>::Key& b) { return a.k0 == b.k0 && a.k1 == b.k1; }
-inline u64 key_hash(const Geo<4>::Key& k) { return mix64(k.k0); }
-inline u64 key_hash(const Geo<5>::Key& k) { return mix64(k.k0 ^ (k.k1 * 0x9E3779B97F4A7C15ull)); }
 
-// ---- the table: the device's layout, hash and probe sequence ------------------------------------------------
-struct Seq { u64 line0, lmask; uint32_t off; };
-inline Seq seq_of(u64 hash, u64 mask) { return Seq{(hash & mask) >> 2, mask >> 2, (uint32_t)hash & 3u}; }
-inline u64 seq_slot(const Seq& s, uint32_t p) {
-  return (((s.line0 + (u64)(p >> 2)) & s.lmask) << 2) | (u64)((s.off + p) & 3u);
-}
-inline uint32_t seq_pos(const Seq& s, u64 slot) {
-  return ((uint32_t)(((slot >> 2) - s.line0) & s.lmask) << 2) | (((uint32_t)slot - s.off) & 3u);
-}
-inline uint32_t probe_limit(u64 mask, uint32_t maxp) { return mask >= (u64)maxp ? maxp : (uint32_t)mask + 1u; }
-
-struct Row { float q0, q1, q2, q3; };
-inline float row_get(const Row& r, int a) { return a == 0 ? r.q0 : a == 1 ? r.q1 : a == 2 ? r.q2 : r.q3; }
-inline void row_set(Row& r, int a, float v) { (a == 0 ? r.q0 : a == 1 ? r.q1 : a == 2 ? r.q2 : r.q3) = v; }
-// a row stored in the canonical frame, read in the frame of the env whose board is image g's pre-image
-inline Row row_env(const Row& r, uint32_t g) {
-  return Row{row_get(r, sym_action(g, 0)), row_get(r, sym_action(g, 1)), row_get(r, sym_action(g, 2)), row_get(r, sym_action(g, 3))};
-}
-
+// ---- the table: how this library touches it (its layout, hash and probe sequence: q2048_core.hpp) ----------------
 inline u64 ld_u64(const uint64_t* p) { return __atomic_load_n(p, __ATOMIC_ACQUIRE); }
 inline float ld_f32(const float* p) {
   const uint32_t u = __atomic_load_n(reinterpret_cast<const uint32_t*>(p), __ATOMIC_RELAXED);
@@ -155,7 +112,6 @@ inline bool slot_is(const q2048_slot* s, const Geo<5>::Key& key) {
 inline void publish(q2048_slot*, const Geo<4>::Key&) {}
 inline void publish(q2048_slot* s, const Geo<5>::Key& key) { __atomic_store_n(&s->reserved, key.k1, __ATOMIC_RELEASE); }
 
-constexpr int64_t kNoSlot = INT64_MIN;
 // slot index (>= 0) when present, else ~h (h = the empty slot that ended the probe) or kNoSlot (probe limit)
 template <class Key>
 inline int64_t probe_find(const q2048_slot* table, u64 mask, const Key& key, Row& row, uint32_t maxp = kRolloutProbe) {
@@ -253,23 +209,15 @@ inline float td_update(q2048_slot* slot, int a, float guess, float reward, float
 // env STAYS in it (invalid moves) that fresh row learns as the defaultdict's would (Agent/main.py:43); it is never part
 // of the table.  Inside a call it is the lane's carried row; between calls it travels through the caller's row cache
 // as a record whose slot field is all ones.  Every other record the device would write is written empty here.
-template <int N> struct RowCacheRec;
-template <> struct RowCacheRec<4> { uint64_t key; float q[4]; uint64_t slot; };
-template <> struct RowCacheRec<5> { uint64_t key; float q[4]; uint64_t key_hi; uint64_t slot; uint64_t pad; };
-static_assert(sizeof(RowCacheRec<4>) == 32 && sizeof(RowCacheRec<5>) == 48, "ABI layout");
-constexpr u64 kCacheSlotMask = (1ull << 40) - 1ull;
-inline u64 cache_tag(const q2048_slot* table, u64 mask) {
-  return (mix64((u64)reinterpret_cast<uintptr_t>(table) ^ (mask * 0x9E3779B97F4A7C15ull)) >> 40) << 40;
-}
-inline bool rec_key_is(const RowCacheRec<4>& r, const Geo<4>::Key& k) { return r.key == k.k0; }
-inline bool rec_key_is(const RowCacheRec<5>& r, const Geo<5>::Key& k) { return r.key == k.k0 && r.key_hi == k.k1; }
-inline void rec_set_key(RowCacheRec<4>& r, const Geo<4>::Key& k) { r.key = k.k0; }
-inline void rec_set_key(RowCacheRec<5>& r, const Geo<5>::Key& k) { r.key = k.k0; r.key_hi = k.k1; r.pad = 0; }
+inline bool rec_key_is(const RowCache<4>& r, const Geo<4>::Key& k) { return r.key == k.k0; }
+inline bool rec_key_is(const RowCache<5>& r, const Geo<5>::Key& k) { return r.key == k.k0 && r.key_hi == k.k1; }
+inline void rec_set_key(RowCache<4>& r, const Geo<4>::Key& k) { r.key = k.k0; }
+inline void rec_set_key(RowCache<5>& r, const Geo<5>::Key& k) { r.key = k.k0; r.key_hi = k.k1; r.pad = 0; }
 template <int N>
 inline bool visit_get(const void* cache, int64_t i, const q2048_slot* table, u64 mask, const typename Geo<N>::Key& key, Row& row) {
   if (cache == nullptr) return false;
-  const RowCacheRec<N>& r = static_cast<const RowCacheRec<N>*>(cache)[i];
-  if (!rec_key_is(r, key) || r.slot != (kCacheSlotMask | cache_tag(table, mask))) return false;
+  const RowCache<N>& r = static_cast<const RowCache<N>*>(cache)[i];
+  if (!rec_key_is(r, key) || r.slot != (kCacheRowless | cache_tag(table, mask))) return false;
   row = Row{r.q[0], r.q[1], r.q[2], r.q[3]};
   return true;
 }
@@ -277,20 +225,20 @@ template <int N>
 inline void visit_put(void* cache, int64_t i, const q2048_slot* table, u64 mask, const typename Geo<N>::Key& key, const Row& row,
                       bool rowless) {
   if (cache == nullptr) return;
-  RowCacheRec<N>& r = static_cast<RowCacheRec<N>*>(cache)[i];
+  RowCache<N>& r = static_cast<RowCache<N>*>(cache)[i];
   std::memset(&r, 0, sizeof r);                    // an empty record (this library never reads a row through the cache)
   if (!rowless) return;
   rec_set_key(r, key);
   r.q[0] = row.q0; r.q[1] = row.q1; r.q[2] = row.q2; r.q[3] = row.q3;
-  r.slot = kCacheSlotMask | cache_tag(table, mask);
+  r.slot = kCacheRowless | cache_tag(table, mask);
 }
 
 // q2048_rowcache_rebind: visit rows follow their table's rows into another allocation; every other record is emptied
 template <int N>
 void rowcache_rebind_n(void* row_cache, int64_t B, u64 tag_from, u64 tag_to) {
-  RowCacheRec<N>* c = static_cast<RowCacheRec<N>*>(row_cache);
+  RowCache<N>* c = static_cast<RowCache<N>*>(row_cache);
   for (int64_t i = 0; i < B; ++i) {
-    if (c[i].key != 0ull && c[i].slot == (kCacheSlotMask | tag_from)) c[i].slot = kCacheSlotMask | tag_to;
+    if (c[i].key != 0ull && c[i].slot == (kCacheRowless | tag_from)) c[i].slot = kCacheRowless | tag_to;
     else std::memset(&c[i], 0, sizeof c[i]);
   }
 }
@@ -338,28 +286,6 @@ void stats_merge(const std::vector<Stats>& parts, int used, int64_t* gi, double*
   }
 }
 
-// ---- argument checks: the device library's, word for word ---------------------------------------------------
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-inline int check_batch(int64_t B, int n) {
-  if (n != 4 && n != 5) return Q2048_ERR_UNSUPPORTED;
-  if (B < 0 || B > (int64_t)0x7fffffff * 256) return Q2048_ERR_SIZE;
-  return Q2048_OK;
-}
-inline int check_table(const void* table, int cap_log2) {
-  if (table == nullptr) return Q2048_ERR_NULL;
-  if (cap_log2 < 4 || cap_log2 > 40) return Q2048_ERR_SIZE;
-  if (!aligned16(table)) return Q2048_ERR_ALIGN;
-  return Q2048_OK;
-}
-constexpr uint32_t kAbiFlags = Q2048_FLAG_INDEPENDENT | Q2048_FLAG_SINGLE_ENV | Q2048_FLAG_TD_CAS | Q2048_FLAG_ENV_DQN |
-                               Q2048_FLAG_RESET_SHAPING | Q2048_FLAG_PLAY_ONLY | Q2048_FLAG_NO_LEARN |
-                               Q2048_FLAG_NO_NEW_ROWS | Q2048_FLAG_LINE_SUMMARY;   // (the last one: 4x4 accepted, not used --
-                                                                                   // slot by slot, same results; 5x5 with a side
-                                                                                   // array: used, fused_rollout_n)
-// (`also`: Q2048_FLAG_SYMMETRIC, for the entry points that take it -- the fused rollouts, the player, q_lookup)
-inline int check_flags(uint32_t flags, uint32_t refused = 0u, uint32_t also = 0u) {
-  return ((flags & ~(kAbiFlags | also)) || (flags & refused)) ? Q2048_ERR_FLAGS : Q2048_OK;
-}
 inline int env_bits(uint32_t flags) {
   return ((flags & Q2048_FLAG_ENV_DQN) ? kEnvDqn : 0) | ((flags & Q2048_FLAG_RESET_SHAPING) ? kEnvResetShaping : 0);
 }
@@ -881,26 +807,10 @@ int q2048_claim_timeouts(uint64_t* count_host) {
   return Q2048_OK;
 }
 
-const char* q2048_strerror(int code) {
-  switch (code) {
-    case Q2048_OK: return "ok";
-    case Q2048_ERR_NULL: return "a required pointer is NULL";
-    case Q2048_ERR_SIZE: return "size out of range (batch, steps, cap_log2 or key_words)";
-    case Q2048_ERR_ALIGN: return "boards/aux/table must be 16-byte aligned";
-    case Q2048_ERR_UNSUPPORTED: return "unsupported here (board side other than 4 or 5; device-only entry point on the host library)";
-    case Q2048_ERR_LAUNCH: return "HIP launch failed";
-    case Q2048_ERR_RANGE: return "scalar out of range (eps in [0,1], lr and gamma finite)";
-    case Q2048_ERR_FLAGS: return "flag bits this entry point does not take";
-    case Q2048_ERR_ALLOC: return "device memory could not be reserved, created or mapped";
-    case Q2048_ERR_VERIFY: return "a table failed its self-check";
-    case Q2048_ERR_BUSY: return "the table already takes part in a growth";
-    case Q2048_PENDING: return "still working (not an error)";
-    default: return "unknown error";
-  }
-}
+const char* q2048_strerror(int code) { return error_text(code); }
 size_t q2048_sizeof_aux(void) { return sizeof(q2048_aux); }
 size_t q2048_sizeof_slot(void) { return sizeof(q2048_slot); }
-size_t q2048_sizeof_rowcache(int n) { return n == 4 ? 32 : n == 5 ? 48 : 0; }
+size_t q2048_sizeof_rowcache(int n) { return n == 4 ? sizeof(RowCache<4>) : n == 5 ? sizeof(RowCache<5>) : 0; }
 int q2048_rowcache_rebind(void* row_cache, int64_t B, int n, const q2048_slot* from_table, int from_cap_log2,
                           const q2048_slot* to_table, int to_cap_log2, void*) {
   if (int e = check_batch(B, n)) return e;
@@ -1252,15 +1162,7 @@ inline float merge_value(int mode, float d, float s, float w, float one_minus_w)
 }  // namespace
 int q2048_table_merge(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, int src_cap_log2, int key_words,
                       int mode, float w, uint64_t* counters, uint32_t* status, void*) {
-  if (!dst || !src || !counters) return Q2048_ERR_NULL;
-  if (dst_cap_log2 < 4 || dst_cap_log2 > 40 || src_cap_log2 < 4 || src_cap_log2 > 40) return Q2048_ERR_SIZE;
-  if (key_words != 1 && key_words != 2) return Q2048_ERR_SIZE;
-  if (!aligned16(dst) || !aligned16(src)) return Q2048_ERR_ALIGN;
-  if (mode != Q2048_MERGE_ADD && mode != Q2048_MERGE_BLEND && mode != Q2048_MERGE_MAXABS) return Q2048_ERR_FLAGS;
-  if (!std::isfinite(w) || (mode == Q2048_MERGE_BLEND && !(w >= 0.0f && w <= 1.0f))) return Q2048_ERR_RANGE;
-  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), s0 = reinterpret_cast<uintptr_t>(src);
-  const uintptr_t d1 = d0 + (sizeof(q2048_slot) << dst_cap_log2), s1 = s0 + (sizeof(q2048_slot) << src_cap_log2);
-  if (s0 < d1 && d0 < s1) return Q2048_ERR_RANGE;
+  if (int e = check_merge(dst, dst_cap_log2, src, src_cap_log2, counters, key_words == 1 || key_words == 2, true, mode, w)) return e;
   const int64_t cap = (int64_t)1 << src_cap_log2;
   const u64 mask = (1ull << dst_cap_log2) - 1ull;
   const float one_minus_w = 1.0f - w;
@@ -1319,16 +1221,8 @@ int q2048_table_fold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, i
                      int mode, float w, uint64_t* counters, uint32_t* status, void*) {
   if (!dst || !src || !counters) return Q2048_ERR_NULL;
   if (key_words == 2) return Q2048_ERR_UNSUPPORTED;
-  if (key_words != 1) return Q2048_ERR_SIZE;
-  if (dst_cap_log2 < 4 || dst_cap_log2 > 40 || src_cap_log2 < 4 || src_cap_log2 > 40) return Q2048_ERR_SIZE;
-  if (!aligned16(dst) || !aligned16(src)) return Q2048_ERR_ALIGN;
-  if (fold != Q2048_FOLD_MEAN && fold != Q2048_FOLD_MEAN_TRAINED && fold != Q2048_FOLD_SUM && fold != Q2048_FOLD_MAXABS)
-    return Q2048_ERR_FLAGS;
-  if (mode != Q2048_MERGE_ADD && mode != Q2048_MERGE_BLEND && mode != Q2048_MERGE_MAXABS) return Q2048_ERR_FLAGS;
-  if (!std::isfinite(w) || (mode == Q2048_MERGE_BLEND && !(w >= 0.0f && w <= 1.0f))) return Q2048_ERR_RANGE;
-  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), s0 = reinterpret_cast<uintptr_t>(src);
-  const uintptr_t d1 = d0 + (sizeof(q2048_slot) << dst_cap_log2), s1 = s0 + (sizeof(q2048_slot) << src_cap_log2);
-  if (s0 < d1 && d0 < s1) return Q2048_ERR_RANGE;
+  const bool fold_ok = fold == Q2048_FOLD_MEAN || fold == Q2048_FOLD_MEAN_TRAINED || fold == Q2048_FOLD_SUM || fold == Q2048_FOLD_MAXABS;
+  if (int e = check_merge(dst, dst_cap_log2, src, src_cap_log2, counters, key_words == 1, fold_ok, mode, w)) return e;
   const int64_t cap = (int64_t)1 << src_cap_log2;
   const u64 mask = (1ull << dst_cap_log2) - 1ull, src_mask = (1ull << src_cap_log2) - 1ull;
   const float one_minus_w = 1.0f - w;

@@ -7,7 +7,10 @@
 //   aux     16 B per env   one dwordx4 per lane
 //   table   32 B slots     {u64 key, f32 q[4], u64 key_hi}; random access, one 128-B line (four
 //                          slots) per probe; the probe sequence visits the line's other three
-//                          slots before it moves to the next line (`Seq`)
+//                          slots before it moves to the next line (`Seq`).  The table's format -- keys,
+//                          hash, `Seq`, probe limits, rows, row-cache records -- is defined in q2048_core.hpp /
+//                          q2048_core5.hpp, the one definition the CPU twin (q2048_host.cpp) compiles too; the
+//                          argument checks both share are in q2048_abi.hpp
 // One board per lane.  Boards, aux and the carried Q row live in VGPRs for a whole launch;
 // per-step boolean statistics are wave ballots accumulated in SGPRs, rare per-episode
 // statistics go through LDS, and each block ends with one global atomic per statistic.
@@ -28,7 +31,7 @@
 #include <thread>
 #include <vector>
 
-#include "q2048.h"
+#include "q2048_abi.hpp"
 #include "q2048_core5.hpp"
 
 // Measurement variants (write-mode / ablation / sort-width / boards-per-thread bits in flags 8..23)
@@ -45,18 +48,6 @@ namespace {
 using namespace q2048;
 
 constexpr int kBlock = 256;
-// Probe limits: beyond them a lookup reads "absent" and an update drops (counted; status TABLE_FULL).  They are
-// what makes a probe of a FULL table end, not a load policy: at load 0.93 the longest cluster of a 2^22-slot
-// table is already thousands of slots (ln n / (a - 1 - ln a)), and round 3's limit of 256 made "full" mean
-// "load ~0.85" (a racing import at load 0.93 dropped rows).  Bulk moves of rows (import, the rehash of a growth)
-// and q2048_q_lookup take kMaxProbe = 2^14 slots: they must place and find every row of a table the caller sized.
-// The learning paths (rollouts, choose, update) take kRolloutProbe = 2^10: a lane of a rollout probes twice per
-// step, and on a fixed table that has filled up 2^14 dependent 16-byte loads per probe made a launch orders of
-// magnitude slower before TABLE_FULL became visible; 2^10 bounds that at ~load 0.93, where an
-// absent key's expected probe is 100 slots already.  (Or the whole table if smaller.)
-constexpr uint32_t kMaxProbe = 1u << 14, kRolloutProbe = 1u << 10;
-constexpr int kMaxCas = 16;      // TD compare-and-swap attempts before the update is simply stored
-
 static_assert(sizeof(q2048_aux) == 16 && sizeof(q2048_slot) == 32, "ABI layout");
 static_assert(sizeof(q2048_episode) == 48, "ABI layout");
 static_assert(offsetof(q2048_slot, q) == 8 && offsetof(q2048_slot, reserved) == 24, "ABI layout");
@@ -66,18 +57,8 @@ static_assert(Q2048_MIRROR_SEQ == Q2048_NSTAT_I + Q2048_NSTAT_F && Q2048_MIRROR_
 using u64 = unsigned long long;
 
 // ---------------------------------------------------------------------------------------------
-// geometry: board type, state key, HBM image
+// HBM images of a board and its aux (the geometry Geo<N> and the table key are in q2048_core5.hpp)
 // ---------------------------------------------------------------------------------------------
-template <int N> struct Geo;
-template <> struct Geo<4> {
-  using BoardT = Board;
-  struct Key { u64 k0; };
-};
-template <> struct Geo<5> {
-  using BoardT = Board5;
-  struct Key { u64 k0, k1; };
-};
-
 // LDS staging of 5x5 boards, PER WAVE: the 64 boards of a wave are 1600 contiguous bytes of HBM
 // (100 x 16 B, 16-byte aligned: 1600 = 100 * 16 and a block starts at a multiple of 6400), moved
 // with 16-byte accesses through the wave's own 1600-byte slice of LDS.  A wave is its own
@@ -176,68 +157,15 @@ __device__ __forceinline__ void st_aux(q2048_aux* aux, int64_t i, const Aux& a) 
   reinterpret_cast<uint4*>(aux)[i] = make_uint4(w.w0, w.w1, w.w2, w.w3);
 }
 
-// state keys.  Independent mode salts the key with the env id (private rows per env).
-__device__ __forceinline__ Geo<4>::Key state_key(const Board& b, u64 salt, uint32_t* status) {
-  bool ov;
-  u64 k = pack_key(b, ov) ^ salt;
-  if (ov) atomicOr(status, Q2048_STATUS_TILE_OVERFLOW);
-  return Geo<4>::Key{k == 0ull ? 1ull : k};  // 0 marks an empty slot
-}
-__device__ __forceinline__ Geo<5>::Key state_key(const Board5& b, u64 salt, uint32_t*) {
-  const Key5 k = pack_key(b);  // both words carry bit 63, so neither is ever 0
-  return Geo<5>::Key{k.k0 ^ (salt & 0x7fffffffffffffffull),
-                     k.k1 ^ (mix64(salt) & 0x3fffffffffffffffull)};
-}
-// Q2048_FLAG_SYMMETRIC (SYM, 4x4 only): the key of the board's canonical image -- the smallest of the eight mirror
-// images' keys, q2048_core.hpp -- salted AFTER canonicalisation; g = which image it is (0 without SYM).  Registers
-// only: no LDS, no load, no atomic.
+// state keys: the shared construction (q2048_core5.hpp), with this library's way to raise TILE_OVERFLOW
 template <bool SYM, class BoardT>
 __device__ __forceinline__ auto state_key_as(const BoardT& b, u64 salt, uint32_t* status, uint32_t& g) {
-  if constexpr (SYM) {
-    bool ov;
-    const Canon c = canonical_key(pack_key(b, ov));
-    if (ov) atomicOr(status, Q2048_STATUS_TILE_OVERFLOW);
-    g = c.g;
-    const u64 k = c.key ^ salt;
-    return Geo<4>::Key{k == 0ull ? 1ull : k};
-  } else {
-    g = 0u;
-    return state_key(b, salt, status);
-  }
+  return q2048::state_key_as<SYM>(b, salt, g, [status] { atomicOr(status, Q2048_STATUS_TILE_OVERFLOW); });
 }
-__device__ __forceinline__ bool key_eq(const Geo<4>::Key& a, const Geo<4>::Key& b) { return a.k0 == b.k0; }
-__device__ __forceinline__ bool key_eq(const Geo<5>::Key& a, const Geo<5>::Key& b) {
-  return a.k0 == b.k0 && a.k1 == b.k1;
-}
-// 64 hash bits of a key: the low ones choose the home slot, the top 16 the deterministic mode's
-// sort bucket (a function of the state alone -- not of where its row ended up)
-__device__ __forceinline__ u64 key_hash(const Geo<4>::Key& k) { return mix64(k.k0); }
-__device__ __forceinline__ u64 key_hash(const Geo<5>::Key& k) {
-  return mix64(k.k0 ^ (k.k1 * 0x9E3779B97F4A7C15ull));
-}
-template <class Key>
-__device__ __forceinline__ u64 key_home(const Key& k, u64 mask) { return key_hash(k) & mask; }
-
-// Probe sequence of a key: BUCKETISED.  A miss moves the whole 128-byte line (4 slots) the probed
-// slot lies in, and what a lookup costs is the number of lines it touches, so a
-// collision is resolved inside the line already fetched: the sequence starts at the home slot
-// (hash & mask), visits the other three slots of that line cyclically -- L2 hits -- and only then
-// moves on to the next line, same order.  Plain linear probing left the line at the first collision
-// of every key whose home is a line's last slot.  (Slots are 32 B; with a 128-byte aligned table
-// a group of four is exactly one line.  Any 16-byte aligned table works.)
-struct Seq { u64 line0, lmask; uint32_t off; };
-__device__ __forceinline__ Seq seq_of(u64 hash, u64 mask) {
-  return Seq{(hash & mask) >> 2, mask >> 2, (uint32_t)hash & 3u};
-}
-__device__ __forceinline__ u64 seq_slot(const Seq& s, uint32_t p) {   // p-th slot of the sequence
-  return (((s.line0 + (u64)(p >> 2)) & s.lmask) << 2) | (u64)((s.off + p) & 3u);
-}
-__device__ __forceinline__ uint32_t seq_pos(const Seq& s, u64 slot) { // inverse, for a slot on the sequence
-  return ((uint32_t)(((slot >> 2) - s.line0) & s.lmask) << 2) | (((uint32_t)slot - s.off) & 3u);
-}
-
-__device__ __forceinline__ uint32_t probe_limit(u64 mask, uint32_t maxp) {
-  return mask >= (u64)maxp ? maxp : (uint32_t)mask + 1u;
+template <class BoardT>
+__device__ __forceinline__ auto state_key(const BoardT& b, u64 salt, uint32_t* status) {
+  uint32_t g;
+  return state_key_as<false>(b, salt, status, g);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -247,26 +175,10 @@ __device__ __forceinline__ uint32_t probe_limit(u64 mask, uint32_t maxp) {
 // brand-new row, which reads as the zero row it still is for the reader.  5x5 keys take two
 // words: one compare-and-swap claims the first, its owner publishes the second (see `confirm`).
 // ---------------------------------------------------------------------------------------------
-struct Row { float q0, q1, q2, q3; };
-
 __device__ __forceinline__ u64 ld_u64(const void* p) {
   return __hip_atomic_load(const_cast<u64*>(reinterpret_cast<const u64*>(p)), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ float row_get(const Row& r, int a) {
-  return a == 0 ? r.q0 : a == 1 ? r.q1 : a == 2 ? r.q2 : r.q3;
-}
-__device__ __forceinline__ void row_set(Row& r, int a, float v) {
-  r.q0 = a == 0 ? v : r.q0; r.q1 = a == 1 ? v : r.q1;
-  r.q2 = a == 2 ? v : r.q2; r.q3 = a == 3 ? v : r.q3;
-}
-// a row stored in the canonical frame, read in the frame of the env whose board has the canonical image g:
-// Q_env[a] = Q_canon[pi_g(a)] (Q2048_FLAG_SYMMETRIC)
-__device__ __forceinline__ Row row_env(const Row& r, uint32_t g) {
-  return Row{row_get(r, sym_action(g, 0)), row_get(r, sym_action(g, 1)), row_get(r, sym_action(g, 2)),
-             row_get(r, sym_action(g, 3))};
-}
-
 // `confirm`: the slot's first key word equals key.k0 (this lane just set it, or found it so).
 // Does the slot hold `key`?  4x4: yes.  5x5 keys have a second word, and a claim is ONE
 // compare-and-swap (scattered device-scope atomics are the scarcest resource of the path: two per
@@ -313,7 +225,6 @@ __device__ __forceinline__ bool confirm(q2048_slot* s, const Geo<5>::Key& key, b
 // Lookup.  Returns the slot index (>= 0) when the key is present; otherwise ~h (< 0) where h is
 // the empty slot that ended the probe -- the place an insert of this key would claim -- or
 // kNoSlot when the probe limit was hit.  `created` stays false (lookups create nothing).
-constexpr int64_t kNoSlot = INT64_MIN;
 // The cost of the table is the NUMBER of scattered requests a lane issues, whatever line they
 // hit, so the probe reads {key, q0, q1} with ONE
 // 16-byte load and the other half of the slot only on a key match.  The load carries sc1 like
@@ -953,39 +864,10 @@ __global__ __launch_bounds__(kBlock) void k_encode_onehot(const uint8_t* boards,
 // ---------------------------------------------------------------------------------------------
 // agent kernels
 // ---------------------------------------------------------------------------------------------
-// Row cache of the 4-call API (optional, caller-owned, one record per env): what the fused rollout
-// carries in registers from one step to the next -- the row this env read as s' in its last
-// update, with its slot -- handed from one q_update call to the next q_choose / q_update through
-// HBM as a coalesced stream.  s of step t + 1 is s' of step t unless an episode began, so the
-// update then needs ONE scattered row read (s') instead of two, and a greedy choose none.  A
-// record is used only when its key equals the key of the board actually passed in (0 = empty), so
-// any calling pattern is correct; like the register-carried row it does not see what OTHER envs
-// wrote to that row since.
-template <int N> struct RowCache;
-template <> struct RowCache<4> { u64 key; float q[4]; u64 slot; };                      // 32 B
-template <> struct RowCache<5> { u64 key; float q[4]; u64 key_hi; u64 slot; u64 pad; }; // 48 B
-static_assert(sizeof(RowCache<4>) == 32 && sizeof(RowCache<5>) == 48, "ABI layout");
-
-// A record also carries, in the 24 bits above its 40-bit slot index, a TAG of the table it was read from (a hash
-// of the table's address and capacity): a record left by a launch on another table -- the table has grown, or the
-// caller switched tables and did not zero the cache -- never matches, so its slot index is never used against the
-// wrong table (records outlive launches since round 4 and were trusted on a key match alone).  A table
-// rewritten IN PLACE (zero-filled, imported into) keeps its tag: the caller zero-fills the cache then, as before.
-__host__ __device__ __forceinline__ u64 cache_tag(const q2048_slot* table, u64 mask) {
-  return (mix64((u64)reinterpret_cast<uintptr_t>(table) ^ (mask * 0x9E3779B97F4A7C15ull)) >> 40) << 40;
-}
-constexpr u64 kCacheSlotMask = (1ull << 40) - 1ull;
-// VISIT ROWS (Q2048_FLAG_NO_NEW_ROWS).  With the key set closed a state without a row reads as the zero row the
-// defaultdict would have created -- and while the env STAYS in that state (invalid moves) that fresh row learns as the
-// defaultdict's would (Agent/main.py:43): the lane keeps it in the registers that otherwise carry the table's row, so
-// that the first invalid move's negative reward sends argmax on to the next action instead of repeating action 0 until
-// the stall rule ends the episode.  It is never part of the table and ends when the env leaves the state.  Across a
-// launch boundary it travels like any carried row, through the row cache, as a ROWLESS record: slot field all ones
-// (no table of 2^40 slots exists).  Only calls that carry the flag write or accept such records.
-constexpr u64 kCacheRowless = kCacheSlotMask;
+// the row cache of the 4-call API (RowCache<N>, its table tag and its rowless records: q2048_core.hpp)
 __device__ __forceinline__ bool cache_slot(u64 s, bool rowless_ok, int64_t& slot) {
   const u64 v = s & kCacheSlotMask;
-  if (v == kCacheRowless) { slot = INT64_MIN; return rowless_ok; }   // (INT64_MIN = kNoSlot, defined below)
+  if (v == kCacheRowless) { slot = kNoSlot; return rowless_ok; }
   slot = (int64_t)v;
   return true;
 }
@@ -2442,21 +2324,8 @@ __global__ __launch_bounds__(kBlock) void k_table_probe(q2048_slot* table, u64 m
 // ---------------------------------------------------------------------------------------------
 // host side of the ABI
 // ---------------------------------------------------------------------------------------------
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline unsigned grid_for(int64_t B) { return (unsigned)((B + kBlock - 1) / kBlock); }
 inline int launch_status() { return hipGetLastError() == hipSuccess ? Q2048_OK : Q2048_ERR_LAUNCH; }
-inline int check_batch(int64_t B, int n) {
-  if (n != 4 && n != 5) return Q2048_ERR_UNSUPPORTED;
-  // one block per 256 envs and HIP caps grid.x at 2^31 - 1 blocks
-  if (B < 0 || B > (int64_t)0x7fffffff * kBlock) return Q2048_ERR_SIZE;
-  return Q2048_OK;
-}
-inline int check_table(const void* table, int cap_log2) {
-  if (table == nullptr) return Q2048_ERR_NULL;
-  if (cap_log2 < 4 || cap_log2 > 40) return Q2048_ERR_SIZE;
-  if (!aligned16(table)) return Q2048_ERR_ALIGN;
-  return Q2048_OK;
-}
 // launches kernel<4> or kernel<5>
 #define Q2048_LAUNCH(kernel, n, B, stream, ...)                                                   \
   do {                                                                                            \
@@ -2542,20 +2411,8 @@ inline int fused_mode(uint32_t flags, int n, const void* side) {   // play-only 
   return sym | ((flags & Q2048_FLAG_TD_CAS) ? kModeCas : kModeLearn) | (frozen ? kModeFrozen : 0) |
          ((frozen && (n == 4 || side != nullptr) && (flags & Q2048_FLAG_LINE_SUMMARY)) ? kModeSummary : 0);   // (5x5: only with a side array)
 }
-// flag bits outside the ABI are an argument error (experiment builds also take bits 8..23)
-constexpr uint32_t kAbiFlags = Q2048_FLAG_INDEPENDENT | Q2048_FLAG_SINGLE_ENV | Q2048_FLAG_TD_CAS |
-                               Q2048_FLAG_ENV_DQN | Q2048_FLAG_RESET_SHAPING | Q2048_FLAG_PLAY_ONLY |
-                               Q2048_FLAG_NO_LEARN | Q2048_FLAG_NO_NEW_ROWS | Q2048_FLAG_LINE_SUMMARY;
 constexpr size_t kOptsSizeNoSide = offsetof(q2048_rollout_opts, line_summary);   // the layout before `line_summary`
 static_assert(kOptsSizeNoSide == 56 && sizeof(q2048_rollout_opts) == 64, "ABI layout");
-// (`also`: Q2048_FLAG_SYMMETRIC, for the entry points that take it -- the fused rollouts, the player, q_lookup)
-inline int check_flags(uint32_t flags, uint32_t refused = 0u, uint32_t also = 0u) {
-  uint32_t allowed = kAbiFlags | also;
-#ifdef Q2048_EXPERIMENTS
-  allowed |= 0x00ffff00u;
-#endif
-  return ((flags & ~allowed) || (flags & refused)) ? Q2048_ERR_FLAGS : Q2048_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -2578,23 +2435,7 @@ int q2048_claim_timeouts(uint64_t* count_host) {
 size_t q2048_sizeof_aux(void) { return sizeof(q2048_aux); }
 size_t q2048_sizeof_slot(void) { return sizeof(q2048_slot); }
 
-const char* q2048_strerror(int code) {
-  switch (code) {
-    case Q2048_OK: return "ok";
-    case Q2048_ERR_NULL: return "a required pointer is NULL";
-    case Q2048_ERR_SIZE: return "size out of range (batch, steps, cap_log2 or key_words)";
-    case Q2048_ERR_ALIGN: return "boards/aux/table must be 16-byte aligned";
-    case Q2048_ERR_UNSUPPORTED: return "unsupported board side (n must be 4 or 5)";
-    case Q2048_ERR_LAUNCH: return "HIP launch failed";
-    case Q2048_ERR_RANGE: return "scalar out of range (eps in [0,1], lr and gamma finite)";
-    case Q2048_ERR_FLAGS: return "flag bits this entry point does not take";
-    case Q2048_ERR_ALLOC: return "device memory could not be reserved, created or mapped";
-    case Q2048_ERR_VERIFY: return "a table failed its self-check (a fresh table not all zeros, or rows lost while growing)";
-    case Q2048_ERR_BUSY: return "the table already takes part in a growth (finish or abort that one first)";
-    case Q2048_PENDING: return "still working (not an error)";
-    default: return "unknown error";
-  }
-}
+const char* q2048_strerror(int code) { return error_text(code); }
 
 int q2048_env_init(uint8_t* boards, q2048_aux* aux, int64_t B, int n, uint64_t seed,
                    uint64_t env_id0, void* stream) {
@@ -3136,15 +2977,7 @@ int q2048_table_import(q2048_slot* table, int cap_log2, const uint64_t* keys, co
   } while (0)
 int q2048_table_merge(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, int src_cap_log2, int key_words,
                       int mode, float w, uint64_t* counters, uint32_t* status, void* stream) {
-  if (!dst || !src || !counters) return Q2048_ERR_NULL;
-  if (dst_cap_log2 < 4 || dst_cap_log2 > 40 || src_cap_log2 < 4 || src_cap_log2 > 40) return Q2048_ERR_SIZE;
-  if (key_words != 1 && key_words != 2) return Q2048_ERR_SIZE;
-  if (!aligned16(dst) || !aligned16(src)) return Q2048_ERR_ALIGN;
-  if (mode != Q2048_MERGE_ADD && mode != Q2048_MERGE_BLEND && mode != Q2048_MERGE_MAXABS) return Q2048_ERR_FLAGS;
-  if (!std::isfinite(w) || (mode == Q2048_MERGE_BLEND && !(w >= 0.0f && w <= 1.0f))) return Q2048_ERR_RANGE;
-  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), s0 = reinterpret_cast<uintptr_t>(src);
-  const uintptr_t d1 = d0 + (sizeof(q2048_slot) << dst_cap_log2), s1 = s0 + (sizeof(q2048_slot) << src_cap_log2);
-  if (s0 < d1 && d0 < s1) return Q2048_ERR_RANGE;                      // the two tables overlap (src == dst included)
+  if (int e = check_merge(dst, dst_cap_log2, src, src_cap_log2, counters, key_words == 1 || key_words == 2, true, mode, w)) return e;
   const u64 cap = 1ull << src_cap_log2, mask = (1ull << dst_cap_log2) - 1ull;
   const u64 want = (cap + kBlock - 1) / kBlock;
   const dim3 grid((unsigned)(want < 2048 ? want : 2048));              // the growth's move: 8 blocks of 4 waves per CU
@@ -3158,16 +2991,8 @@ int q2048_table_fold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, i
                      int mode, float w, uint64_t* counters, uint32_t* status, void* stream) {
   if (!dst || !src || !counters) return Q2048_ERR_NULL;
   if (key_words == 2) return Q2048_ERR_UNSUPPORTED;                    // (5x5 has no folded table)
-  if (key_words != 1) return Q2048_ERR_SIZE;
-  if (dst_cap_log2 < 4 || dst_cap_log2 > 40 || src_cap_log2 < 4 || src_cap_log2 > 40) return Q2048_ERR_SIZE;
-  if (!aligned16(dst) || !aligned16(src)) return Q2048_ERR_ALIGN;
-  if (fold != Q2048_FOLD_MEAN && fold != Q2048_FOLD_MEAN_TRAINED && fold != Q2048_FOLD_SUM && fold != Q2048_FOLD_MAXABS)
-    return Q2048_ERR_FLAGS;
-  if (mode != Q2048_MERGE_ADD && mode != Q2048_MERGE_BLEND && mode != Q2048_MERGE_MAXABS) return Q2048_ERR_FLAGS;
-  if (!std::isfinite(w) || (mode == Q2048_MERGE_BLEND && !(w >= 0.0f && w <= 1.0f))) return Q2048_ERR_RANGE;
-  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), s0 = reinterpret_cast<uintptr_t>(src);
-  const uintptr_t d1 = d0 + (sizeof(q2048_slot) << dst_cap_log2), s1 = s0 + (sizeof(q2048_slot) << src_cap_log2);
-  if (s0 < d1 && d0 < s1) return Q2048_ERR_RANGE;                      // the two tables overlap (src == dst included)
+  const bool fold_ok = fold == Q2048_FOLD_MEAN || fold == Q2048_FOLD_MEAN_TRAINED || fold == Q2048_FOLD_SUM || fold == Q2048_FOLD_MAXABS;
+  if (int e = check_merge(dst, dst_cap_log2, src, src_cap_log2, counters, key_words == 1, fold_ok, mode, w)) return e;
   const u64 cap = 1ull << src_cap_log2, mask = (1ull << dst_cap_log2) - 1ull;
   const u64 want = (cap + kBlock - 1) / kBlock;
   const dim3 grid((unsigned)(want < 2048 ? want : 2048));              // the merge's grid: a grid-stride pass over src

@@ -7,7 +7,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 CXX ?= g++
 CC ?= gcc
 ROCM ?= /opt/rocm
-DEPS := $(CSRC)/q2048_core.hpp $(CSRC)/q2048_core5.hpp $(CSRC)/q2048_luts.inc include/q2048.h
+DEPS := $(CSRC)/q2048_core.hpp $(CSRC)/q2048_core5.hpp $(CSRC)/q2048_luts.inc $(CSRC)/q2048_abi.hpp include/q2048.h
 
 all: $(CSRC)/libq2048_hip.so $(CSRC)/libq2048_host.so oracle/liboracle.so
 

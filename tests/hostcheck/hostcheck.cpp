@@ -270,6 +270,24 @@ void hc_kth_set_bit32(const uint32_t* mask, const uint8_t* k, int64_t n, uint8_t
 }
 
 uint64_t hc_mix64(uint64_t x) { return mix64(x); }
+
+// ---- the table's format (q2048_core.hpp / q2048_core5.hpp): what tests/table_model.py restates independently ----
+void hc_key_hash(const uint64_t* keys, int key_words, int64_t n, uint64_t* out) {
+  for (int64_t i = 0; i < n; ++i)
+    out[i] = key_words == 1 ? key_hash(Geo<4>::Key{keys[i]}) : key_hash(Geo<5>::Key{keys[2 * i], keys[2 * i + 1]});
+}
+void hc_seq_slot(const uint64_t* hash, const uint32_t* pos, int cap_log2, int64_t n, uint64_t* out) {
+  for (int64_t i = 0; i < n; ++i) out[i] = seq_slot(seq_of(hash[i], (1ull << cap_log2) - 1ull), pos[i]);
+}
+void hc_seq_pos(const uint64_t* hash, const uint64_t* slot, int cap_log2, int64_t n, uint32_t* out) {
+  for (int64_t i = 0; i < n; ++i) out[i] = seq_pos(seq_of(hash[i], (1ull << cap_log2) - 1ull), slot[i]);
+}
+uint32_t hc_probe_limit(int cap_log2, int rollout) {
+  return probe_limit((1ull << cap_log2) - 1ull, rollout ? kRolloutProbe : kMaxProbe);
+}
+uint64_t hc_cache_tag(uint64_t address, uint64_t mask) {
+  return cache_tag(reinterpret_cast<const void*>((uintptr_t)address), mask);
+}
 uint64_t hc_lane_salt(uint64_t id) { return lane_salt(id); }
 int hc_sizeof_aux(void) { return (int)sizeof(Aux); }
 
