@@ -364,7 +364,9 @@ class BatchedQLearningAgent:
                     same experience, so `freeze_load` binds that much later.  `fused_rollout`, `play_rollout`,
                     `q_values`, statistics, growth, freezing, checkpoints and `merge_from` work as without it;
                     everything the caller sees (actions, `q_values`, the episode log) is in the env's own frame.
-                    `export_rows` / `export_dict` return the CANONICAL states only (one per orbit).  The 4-call API
+                    `export_rows` / `export_dict` return the CANONICAL states only (one per orbit;
+                    `export_dict(unfold=True)` returns every image, and a plain agent's `unfold_from` takes the
+                    whole table over, for the paths that only understand plain tables).  The 4-call API
                     (`choose_action`, `update_q_value`) and `deterministic_rollout` raise ValueError; a folded
                     checkpoint loads only into a folded agent (and a plain one only into a plain agent).
     row_cache       `choose_action` / `update_q_value` hand the row an env read as next_state on to
@@ -1068,12 +1070,23 @@ class BatchedQLearningAgent:
         k = keys[:got].cpu().numpy().view(np.uint64)
         return (k[:, 0] if words == 1 else k), q[:got].cpu().numpy()
 
-    def export_dict(self) -> dict:
+    def export_dict(self, unfold: bool = False) -> dict:
         """The table in the reference's form: {tuple of 4 tuples of raw tile values ->
         np.float64[4]} (Agent/main.py:16,82).  Shared-table mode only.  A symmetric agent's table holds the
-        CANONICAL states only -- one board per orbit of the eight symmetries, its row in that board's frame."""
+        CANONICAL states only -- one board per orbit of the eight symmetries, its row in that board's frame.
+        unfold=True: a symmetric agent's table over ALL images instead, every board with the row `q_values` gives
+        for it -- what the reference's loop needs, which knows nothing of canonical images; the table is unfolded on
+        the device into a scratch plain agent (`unfold_from`) and that one is exported.  A plain agent's table is
+        what it is either way."""
         if self.flags & N.FLAG_INDEPENDENT:
             raise ValueError("salted keys of independent mode do not decode to boards")
+        if unfold and self.symmetric:
+            self.finish_growth()
+            room = max(4, int(np.ceil(np.log2(16.0 * max(self._rows_exact(), 1)))))   # eight images per row at load <= 0.5
+            plain = BatchedQLearningAgent(1, capacity_log2=room, device=self.device, placement="plain", row_cache=False,
+                                          freeze_load=None)
+            plain.unfold_from(self)
+            return plain.export_dict()
         keys, q = self.export_rows()
         out, n = {}, self.board_size
         for k, row in zip(keys.tolist(), q.astype(np.float64)):
@@ -1320,6 +1333,72 @@ class BatchedQLearningAgent:
             warnings.warn("table_fold placed rows deeper than the learning paths probe (2^10 slots): q_values finds "
                           "them, choose / update / rollouts read them as absent -- fold into a larger table")
         return {"read": read, "orbits": orbits, "created": created, "combined": combined, "dropped": dropped}
+
+    def unfold_from(self, other: "BatchedQLearningAgent", mode: str = "add", weight: float = 1.0) -> dict:
+        """Unfolds `other`'s SYMMETRY-FOLDED table into this plain one on the device (q2048_table_unfold), `fold_from`'s
+        inverse: every row of `other` becomes one row per mirror image of its board -- 8, or 4, 2, 1 for boards that
+        are their own mirror images -- each in that image's own frame, exactly what `other` answers when it is asked
+        about that board, and each finds or creates its row here, combined with it by `mode` / `weight` as
+        `merge_from` combines a row.  The way out of a folded table for everything that only understands plain ones
+        (`choose_action`, `update_q_value`, `deterministic_rollout`, the reference's own loop over `export_dict`).
+        `other` is only read.  float32, every product and sum rounded on its own: a float32 numpy model gives the
+        same bits.  The frozen rule and the row bookkeeping are `merge_from`'s; sizing takes the upper bound
+        rows + 8 * other's rows: a table that can grow grows first until that fits half of it, one that cannot
+        raises ValueError when it would pass load 0.9 (nothing is launched then).
+        Returns the call's counters: {"read", "skipped", "written", "created", "combined", "dropped"}; read == other's
+        rows, written == created + combined + dropped.  skipped counts rows whose key is not canonical: a folded
+        table never holds one, so anything but 0 raises RuntimeError (the table is corrupted)."""
+        if not isinstance(other, BatchedQLearningAgent) or other is self:
+            raise ValueError("unfold_from takes another BatchedQLearningAgent")
+        if other.device != self.device:
+            raise ValueError("the two agents live on different devices")
+        if self.board_size != 4 or other.board_size != 4:
+            raise ValueError("symmetry folding is built for board size 4 only")
+        if self.symmetric:
+            raise ValueError("unfold_from needs a plain destination (symmetric=False); merge_from combines two folded "
+                             "tables")
+        if not other.symmetric:
+            raise ValueError("the source is a plain table: merge_from combines two tables of one kind")
+        if (self.flags | other.flags) & N.FLAG_INDEPENDENT:
+            raise ValueError("keys salted per env (independent=True, Q2048_FLAG_INDEPENDENT) do not decode to boards "
+                             "and cannot be unfolded")
+        if mode not in self._MERGE_MODES:
+            raise ValueError(f"mode must be one of {sorted(self._MERGE_MODES)}")
+        weight = float(weight)
+        if not np.isfinite(weight) or (mode == "blend" and not 0.0 <= weight <= 1.0):
+            raise ValueError("weight must be finite, and in [0, 1] for mode 'blend'")
+        if self.frozen:
+            raise ValueError("this agent's key set is closed (frozen): an unfold would create rows its visit rows and "
+                             "line summaries do not know")
+        self.finish_growth()
+        other.finish_growth()
+        rows, rows_other = self._rows_exact(), other._rows_exact()
+        total = rows + 8 * rows_other                     # (an upper bound: a row has at most eight images)
+        while self.growable and total * 2 > (1 << self.capacity_log2) and self.capacity_log2 < self.max_capacity_log2:
+            self.grow_table(min(self.max_capacity_log2, max(self.capacity_log2 + 1, int(np.ceil(np.log2(2.0 * total))))),
+                            _rows=rows)
+        if total > 0.9 * (1 << self.capacity_log2):
+            raise ValueError("table too small for the unfold (load factor could exceed 0.9)")
+        self.invalidate_row_cache()
+        self._summarised, self._side = False, None        # (rows arrive: line summaries stop describing the table)
+        counters = torch.zeros(6, dtype=torch.int64, device=self.device)
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)    # this call's own word (the agent's is sticky)
+        N.check(self._L.q2048_table_unfold(_ptr(self.table), self.capacity_log2, _ptr(other.table), other.capacity_log2, 1,
+                                           self._MERGE_MODES[mode], weight, _ptr(counters), _ptr(status),
+                                           _stream(self.device)), "table_unfold")
+        read, skipped, written, created, combined, dropped = (int(v) for v in counters.tolist())
+        code = int(status.item())
+        self._rebase_rows(rows + created)
+        if code & N.STATUS_TABLE_FULL:
+            raise RuntimeError(f"table_unfold dropped {dropped} rows (probe limit)")
+        if skipped:
+            raise RuntimeError(f"table_unfold skipped {skipped} rows of the folded table whose key is not canonical: "
+                               "the source table is corrupted")
+        if code & N.STATUS_DEEP_ROW:
+            warnings.warn("table_unfold placed rows deeper than the learning paths probe (2^10 slots): q_values finds "
+                          "them, choose / update / rollouts read them as absent -- unfold into a larger table")
+        return {"read": read, "skipped": skipped, "written": written, "created": created, "combined": combined,
+                "dropped": dropped}
 
     def recount_rows(self) -> int:
         """Counts the occupied slots (one streaming pass, synchronising) and makes that the base of the row

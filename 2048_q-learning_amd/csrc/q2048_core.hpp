@@ -912,6 +912,47 @@ Q_HD bool fold_orbit(uint64_t m, const float q[4], const Find& find, uint64_t& c
 }
 
 // ------------------------------------------------------------------------------------------
+// UNFOLDING A SYMMETRY-FOLDED TABLE INTO A PLAIN ONE (include/q2048.h, q2048_table_unfold; kernel and CPU twin both
+// walk an orbit through unfold_orbit): the fold's inverse.  The source row (c, Qc) -- c a canonical key, Qc in the
+// canonical frame -- becomes one row per MEMBER of c's orbit (the fold's members, in its order), each in the
+// member's own frame: Q_m[a] = Qc[pi_g(a)], g = canonical_key(m).g, what the fused rollout reads when it meets m.
+// ------------------------------------------------------------------------------------------
+// image_h(k) for one h (key_images computes all eight; this one is for a loop that is not unrolled)
+Q_HD uint64_t key_image(uint64_t k, uint32_t h) {
+  uint64_t o = (h & 1u) ? key_transpose(k) : k;                      // h odd: the images of T b
+  o = ((0x9cu >> h) & 1u) ? key_flip_h(o) : o;                       // H for h in {2, 3, 4, 7}
+  return ((0xc6u >> h) & 1u) ? key_flip_v(o) : o;                    // V for h in {1, 2, 6, 7}
+}
+// Calls emit(member key, member row) for every member of the orbit of `c`, in ascending h, and returns how many
+// there are (8, 4, 2 or 1); returns 0 and emits nothing when `c` is not a canonical key (such a row has no place
+// in a folded table: its orbit belongs to the row of canonical_key(c).key).  Distinct canonical keys have
+// disjoint orbits, so a caller that gives every source row to one thread has one writer per destination row.
+// The member loop is a loop, not eight copies of `emit`: a member costs a find-or-create in memory, and beside
+// that the arithmetic of recomputing its key and its g (canonical_key(m).g itself -- no table of inverses to
+// keep true for boards with a stabiliser) is free.
+template <class Emit>
+Q_HD uint32_t unfold_orbit(uint64_t c, const Row& qc, const Emit& emit) {
+  uint64_t img[8];
+  key_images(c, img);
+  uint32_t first = 1u;                           // bit h: image h is not the image of a smaller h
+#pragma unroll
+  for (int h = 1; h < 8; ++h) {
+    if (img[h] < c) return 0u;                   // (canonical_key(c).key != c)
+    bool repeat = false;
+#pragma unroll
+    for (int j = 0; j < h; ++j) repeat |= img[j] == img[h];
+    first |= (repeat ? 0u : 1u) << h;
+  }
+#pragma unroll 1
+  for (uint32_t h = 0; h < 8u; ++h) {            // (h = 0: c itself, g = 0, the row as it is)
+    if (!((first >> h) & 1u)) continue;
+    const uint64_t m = key_image(c, h);
+    emit(m, row_env(qc, canonical_key(m).g));
+  }
+  return popc(first);
+}
+
+// ------------------------------------------------------------------------------------------
 // row-tuple linear Q (BASELINE configs[1]: "flat-array Q over row-tuple features").  NOT the
 // reference's learner (its Q is keyed by the whole board, Agent/main.py:82): Q(s,a) is the sum
 // over the four rows r of W[r][idx_r(s)][a] with idx_r = pack_row(row r); same epsilon-greedy

@@ -1278,6 +1278,61 @@ int q2048_table_fold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, i
   return Q2048_OK;
 }
 
+// the device's unfold (k_table_unfold), value for value: the same walk of the orbit (unfold_orbit, q2048_core.hpp),
+// one find-or-create in `dst` per member, the merge's arithmetic; slots of `src` split over the threads (a source
+// row's whole orbit is written by the thread that read the row, and orbits of distinct canonical keys are disjoint)
+int q2048_table_unfold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, int src_cap_log2, int key_words, int mode,
+                       float w, uint64_t* counters, uint32_t* status, void*) {
+  if (!dst || !src || !counters) return Q2048_ERR_NULL;
+  if (key_words == 2) return Q2048_ERR_UNSUPPORTED;
+  if (int e = check_merge(dst, dst_cap_log2, src, src_cap_log2, counters, key_words == 1, true, mode, w)) return e;
+  const int64_t cap = (int64_t)1 << src_cap_log2;
+  const u64 mask = (1ull << dst_cap_log2) - 1ull;
+  const float one_minus_w = 1.0f - w;
+  struct Part { uint64_t read = 0, skipped = 0, created = 0, combined = 0, dropped = 0; uint32_t bits = 0; };
+  std::vector<Part> parts((size_t)threads_for(cap));
+  Part* part = parts.data();
+  const int used = parallel_ranges(cap, [=](int64_t lo, int64_t hi, int t) {
+    Part p;
+    const auto emit = [&p, dst, mask, mode, w, one_minus_w](uint64_t m, const Row& r) {
+      const float q[4] = {r.q0, r.q1, r.q2, r.q3};
+      const Geo<4>::Key key{(u64)m};
+      const u64 hash = key_hash(key);
+      bool inserted;
+      const int64_t slot = probe_insert(dst, mask, key, hash & mask, inserted, kMaxProbe);
+      if (slot < 0) { ++p.dropped; p.bits |= Q2048_STATUS_TABLE_FULL; return; }
+      if (inserted) {
+        ++p.created;
+        if (seq_pos(seq_of(hash, mask), (u64)slot) >= probe_limit(mask, kRolloutProbe)) p.bits |= Q2048_STATUS_DEEP_ROW;
+        for (int a = 0; a < 4; ++a) st_f32(&dst[slot].q[a], mode == Q2048_MERGE_ADD ? mul_rn(w, q[a]) : q[a]);
+      } else {
+        ++p.combined;
+        for (int a = 0; a < 4; ++a) st_f32(&dst[slot].q[a], merge_value(mode, ld_f32(&dst[slot].q[a]), q[a], w, one_minus_w));
+      }
+    };
+    for (int64_t i = lo; i < hi; ++i) {
+      const q2048_slot& s = src[i];
+      if (s.key == 0ull) continue;
+      ++p.read;
+      if (unfold_orbit(s.key, Row{s.q[0], s.q[1], s.q[2], s.q[3]}, emit) == 0u) ++p.skipped;
+    }
+    part[t] = p;
+  });
+  uint32_t bits = 0u;
+  for (int t = 0; t < used; ++t) {
+    const Part& p = parts[(size_t)t];
+    counters[0] += p.read;
+    counters[1] += p.skipped;
+    counters[2] += p.created + p.combined + p.dropped;
+    counters[3] += p.created;
+    counters[4] += p.combined;
+    counters[5] += p.dropped;
+    bits |= p.bits;
+  }
+  if (bits && status != nullptr) status_or(status, bits);
+  return Q2048_OK;
+}
+
 int q2048_canonicalize(const uint8_t* boards, int64_t B, int n, uint8_t* boards_out, uint8_t* sym_out, void*) {
   if (int e = check_batch(B, n)) return e;
   if (n != 4) return Q2048_ERR_UNSUPPORTED;

@@ -2304,6 +2304,77 @@ void launch_fold(int mode, dim3 grid, hipStream_t stream, const q2048_slot* src,
                        one_minus_w, counters, status);
 }
 
+// Unfold (q2048_table_unfold): the fold's inverse, for a symmetry-folded `src` and a PLAIN `dst`.  A lane streams
+// `src` as the merge does, and an occupied slot that holds a canonical key sends one row per member of its orbit
+// (unfold_orbit, q2048_core.hpp: the member's key, the row in the member's frame) through the merge's find-or-create
+// and its arithmetic -- up to eight of them, one after the other.  Distinct canonical keys have disjoint orbits and
+// one lane writes its whole orbit, so no two lanes ever meet on a dst row: the only races are the slot claims.  A
+// key that is not canonical is counted and skipped.  counters[0..5] += rows read / skipped / members / created /
+// combined / dropped, one atomic per counter and block.
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_table_unfold(const q2048_slot* src, u64 src_cap, q2048_slot* dst, u64 dst_mask,
+                                                         float w, float one_minus_w, u64* counters, uint32_t* status) {
+  const u32x4* t16 = reinterpret_cast<const u32x4*>(src);
+  u64 read = 0ull, skipped = 0ull, created = 0ull, combined = 0ull, dropped = 0ull;
+  uint32_t bits = 0u;
+  const auto emit = [&](uint64_t m, const Row& s) {
+    const Geo<4>::Key key{(u64)m};
+    bool inserted;
+    const int64_t slot = probe_insert(dst, dst_mask, key, key_home(key, dst_mask), inserted, kMaxProbe);
+    if (slot < 0) { ++dropped; bits |= Q2048_STATUS_TABLE_FULL; return; }
+    float r0, r1, r2, r3;
+    if (inserted) {
+      ++created;
+      if (seq_pos(seq_of(key_hash(key), dst_mask), (u64)slot) >= probe_limit(dst_mask, kRolloutProbe)) bits |= Q2048_STATUS_DEEP_ROW;
+      if constexpr (MODE == Q2048_MERGE_ADD) { r0 = __fmul_rn(w, s.q0); r1 = __fmul_rn(w, s.q1); r2 = __fmul_rn(w, s.q2); r3 = __fmul_rn(w, s.q3); }
+      else { r0 = s.q0; r1 = s.q1; r2 = s.q2; r3 = s.q3; }
+    } else {
+      ++combined;
+      const u64 lo = ld_u64(&dst[slot].q[0]), hi = ld_u64(&dst[slot].q[2]);
+      r0 = merge_value<MODE>(bits_f32((uint32_t)lo), s.q0, w, one_minus_w);
+      r1 = merge_value<MODE>(bits_f32((uint32_t)(lo >> 32)), s.q1, w, one_minus_w);
+      r2 = merge_value<MODE>(bits_f32((uint32_t)hi), s.q2, w, one_minus_w);
+      r3 = merge_value<MODE>(bits_f32((uint32_t)(hi >> 32)), s.q3, w, one_minus_w);
+    }
+    uint2* q = reinterpret_cast<uint2*>(dst[slot].q);                    // 8-byte aligned (offset 8 of a 32-B slot)
+    q[0] = make_uint2(f32_bits(r0), f32_bits(r1));
+    q[1] = make_uint2(f32_bits(r2), f32_bits(r3));
+  };
+  for (u64 i = (u64)blockIdx.x * kBlock + threadIdx.x; i < src_cap; i += (u64)gridDim.x * kBlock) {
+    const u32x4 a = __builtin_nontemporal_load(&t16[2ull * i]);          // {key, q0, q1}
+    const u64 k = (u64)a.x | ((u64)a.y << 32);
+    if (k == 0ull) continue;
+    ++read;
+    const u32x4 b = __builtin_nontemporal_load(&t16[2ull * i + 1ull]);   // {q2, q3, summary word: not looked at}
+    if (unfold_orbit(k, Row{bits_f32(a.z), bits_f32(a.w), bits_f32(b.x), bits_f32(b.y)}, emit) == 0u) ++skipped;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    read += __shfl_xor(read, d); skipped += __shfl_xor(skipped, d); created += __shfl_xor(created, d);
+    combined += __shfl_xor(combined, d); dropped += __shfl_xor(dropped, d); bits |= __shfl_xor(bits, d);
+  }
+  __shared__ u64 wc[5][kBlock / 64];
+  __shared__ uint32_t wb[kBlock / 64];
+  if ((threadIdx.x & 63u) == 0u) {
+    const uint32_t wv = threadIdx.x >> 6;
+    wc[0][wv] = read; wc[1][wv] = skipped; wc[2][wv] = created; wc[3][wv] = combined; wc[4][wv] = dropped; wb[wv] = bits;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 n = 0ull, k = 0ull, c = 0ull, m = 0ull, f = 0ull;
+    uint32_t sb = 0u;
+#pragma unroll
+    for (int v = 0; v < kBlock / 64; ++v) { n += wc[0][v]; k += wc[1][v]; c += wc[2][v]; m += wc[3][v]; f += wc[4][v]; sb |= wb[v]; }
+    if (n) atomicAdd(&counters[0], n);
+    if (k) atomicAdd(&counters[1], k);
+    if (c + m + f) atomicAdd(&counters[2], c + m + f);
+    if (c) atomicAdd(&counters[3], c);
+    if (m) atomicAdd(&counters[4], m);
+    if (f) atomicAdd(&counters[5], f);
+    if (sb && status != nullptr) atomicOr(status, sb);
+  }
+}
+
 // Placement probe: `steps` scattered device-scope atomic ORs of 0 per lane into key words chosen
 // like the rollout chooses rows -- the table's write-side request pattern with no effect on its
 // contents (x | 0 == x).  The host times it: where in device memory a table lies moves the
@@ -3003,6 +3074,26 @@ int q2048_table_fold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, i
   else if (fold == Q2048_FOLD_MEAN_TRAINED) launch_fold<Q2048_FOLD_MEAN_TRAINED>(mode, grid, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
   else if (fold == Q2048_FOLD_SUM) launch_fold<Q2048_FOLD_SUM>(mode, grid, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
   else launch_fold<Q2048_FOLD_MAXABS>(mode, grid, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
+  return launch_status();
+}
+
+int q2048_table_unfold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, int src_cap_log2, int key_words, int mode,
+                       float w, uint64_t* counters, uint32_t* status, void* stream) {
+  if (!dst || !src || !counters) return Q2048_ERR_NULL;
+  if (key_words == 2) return Q2048_ERR_UNSUPPORTED;                    // (5x5 has no folded table)
+  if (int e = check_merge(dst, dst_cap_log2, src, src_cap_log2, counters, key_words == 1, true, mode, w)) return e;
+  const u64 cap = 1ull << src_cap_log2, mask = (1ull << dst_cap_log2) - 1ull;
+  const u64 want = (cap + kBlock - 1) / kBlock;
+  const dim3 grid((unsigned)(want < 2048 ? want : 2048));              // the merge's grid: a grid-stride pass over src
+  const float one_minus_w = 1.0f - w;
+  u64* ctr = reinterpret_cast<u64*>(counters);
+  const hipStream_t s = (hipStream_t)stream;
+  if (mode == Q2048_MERGE_ADD)
+    hipLaunchKernelGGL(k_table_unfold<Q2048_MERGE_ADD>, grid, dim3(kBlock), 0, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
+  else if (mode == Q2048_MERGE_BLEND)
+    hipLaunchKernelGGL(k_table_unfold<Q2048_MERGE_BLEND>, grid, dim3(kBlock), 0, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
+  else
+    hipLaunchKernelGGL(k_table_unfold<Q2048_MERGE_MAXABS>, grid, dim3(kBlock), 0, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
   return launch_status();
 }
 

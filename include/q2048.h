@@ -65,7 +65,8 @@ extern "C" {
                                q2048_table_merge (combine two tables on the device) arrived without a bump as well: a
                                caller detects it by its symbol; so did q2048_play_rollout (the greedy player over the
                                legal moves, one launch) and Q2048_FLAG_SYMMETRIC (one row for a board's eight mirror
-                               images), detected by the symbol q2048_canonicalize */
+                               images), detected by the symbol q2048_canonicalize; q2048_table_fold and
+                               q2048_table_unfold (into and out of a folded table) likewise, each by its symbol */
 
 /* return codes */
 #define Q2048_OK 0
@@ -838,6 +839,40 @@ int q2048_table_merge(q2048_slot *dst, int dst_cap_log2, const q2048_slot *src, 
 #define Q2048_FOLD_MAXABS 3
 int q2048_table_fold(q2048_slot *dst, int dst_cap_log2, const q2048_slot *src, int src_cap_log2, int key_words,
                      int fold, int mode, float w, uint64_t *counters, uint32_t *status, void *stream);
+
+/* Unfolds a SYMMETRY-FOLDED table into a PLAIN one on the device: the fold's inverse, and the way out of a folded table
+ * for every path that only understands plain ones (q2048_q_choose / _update, q2048_det_rollout, the reference's own
+ * loop over an exported dict).  `src` is a symmetry-folded 4x4 table, `dst` a plain one that may already hold rows
+ * (Q2048_FLAG_SYMMETRIC above: images, canonical image, pi_g; q2048_table_fold: the members of an orbit and their
+ * order).  Arrived without an ABI bump, detected by its symbol.  For every occupied source row with key c and row Qc:
+ *   NOT CANONICAL  canonical_key(c).key != c: the row is skipped and counted, no status bit is set -- unfolding it would
+ *             let two source rows meet on one destination row.  (A table the folded kernels wrote holds none.)
+ *   MEMBERS   image_h(c), h = 0..7, in ascending h; an h whose key equals that of a smaller h is left out (boards with a
+ *             stabiliser have 4, 2 or 1 distinct images).
+ *   FRAME     The inverse of the fold's.  A member m gets the row in ITS OWN frame, as the fused rollout reads it when
+ *             it meets that board: Q_m[a] = Qc[pi_g(a)], g = the smallest g with image_g(m) = c.  Member h = 0 is c
+ *             itself, with Qc unchanged.
+ *   mode, w   Every member row finds or creates the row of m in `dst` and is combined with it exactly as
+ *             q2048_table_merge combines a source row: its arithmetic (float32, every product and sum rounded on its
+ *             own, 1 - w computed once on the host), its created-row rule (ADD creates w * q, the others q).
+ *   counters  device uint64[6], ADDED to: [0] occupied src rows read, [1] src rows skipped as not canonical, [2] member
+ *             rows produced, [3] rows created in dst, [4] rows combined with an existing dst row, [5] member rows
+ *             dropped (no slot within the bulk probe limit); [2] = [3] + [4] + [5] = the sum of the distinct image
+ *             counts of the canonical rows read.
+ *   status    may be NULL; Q2048_STATUS_TABLE_FULL / Q2048_STATUS_DEEP_ROW as q2048_table_merge.
+ * One streaming pass over `src` and up to eight find-or-creates in `dst` per occupied slot.  Distinct canonical keys
+ * have disjoint orbits and one lane writes all members of its orbit, so exactly one lane writes each dst row: the only
+ * races are the slot claims, the result depends on the two tables' ROWS only, and a float32 model on the host gives the
+ * same bits.  Stream-ordered.  Nothing else may write `src` or touch `dst` while the call is in flight.  `src` is never
+ * written; the `reserved` words of both tables are neither read nor written (line summaries in `src` are harmless, those
+ * of `dst` are stale afterwards, as after a merge).  Keys salted by Q2048_FLAG_INDEPENDENT cannot be told from board
+ * keys and must not be passed.
+ * Errors, in the order of q2048_table_fold: dst, src or counters NULL -> Q2048_ERR_NULL; key_words == 2 ->
+ * Q2048_ERR_UNSUPPORTED (5x5 has no folded table); key_words not 1 or 2, or a cap_log2 outside 4..40 -> Q2048_ERR_SIZE;
+ * a table not 16-byte aligned -> Q2048_ERR_ALIGN; an unknown mode -> Q2048_ERR_FLAGS; w not finite, or outside [0, 1]
+ * with Q2048_MERGE_BLEND -> Q2048_ERR_RANGE; the two tables' byte ranges overlap -> Q2048_ERR_RANGE. */
+int q2048_table_unfold(q2048_slot *dst, int dst_cap_log2, const q2048_slot *src, int src_cap_log2, int key_words,
+                       int mode, float w, uint64_t *counters, uint32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -24,10 +24,19 @@ travels through a Python dict.
                           be mixed.  One plain input with --fold is the converter of a plain file.  Without --fold a
                           mix is refused and nothing is folded.
 
+  --unfold                the output is a PLAIN table: every symmetry-folded input is unfolded on its way in -- each of
+                          its rows becomes the rows of its board's eight mirror images (4, 2 or 1 for boards that are
+                          their own images), each in that image's own frame (q2048_table_unfold,
+                          `BatchedQLearningAgent.unfold_from`) -- and --mode acts between inputs as before.  Plain
+                          inputs merge as they are.  One folded input with --unfold is the converter of a folded file:
+                          the way to `train.py --deterministic`, the 4-call API and the reference's own loop.  Not
+                          together with --fold.
+
     python train.py --gpus 8 --num-envs 8388608 --episodes 40 --save models/q.pt
     python merge_tables.py --out models/q_merged.pt models/q.pt.rank*
     python evaluate.py --model models/q_merged.pt
     python merge_tables.py --fold mean_trained --out models/q_folded.pt models/q_plain.pt
+    python merge_tables.py --unfold --out models/q_plain.pt models/q_folded.pt
 
 Hyper-parameters, epsilon schedule, seed and training progress come from the first input; the statistics vectors are
 summed and the draw counter is the largest of the inputs'.  Prints one JSON line.
@@ -55,8 +64,13 @@ def parse_args(argv=None):
     p.add_argument("--mode", choices=["mean", "sum", "maxabs", "first", "last"], default="mean")
     p.add_argument("--fold", choices=["mean", "mean_trained", "sum", "maxabs"], default=None,
                    help="write a symmetry-folded table: plain inputs are folded on their way in (see above)")
+    p.add_argument("--unfold", action="store_true",
+                   help="write a plain table: symmetry-folded inputs are unfolded on their way in (see above)")
     p.add_argument("--device", default="cuda", help='"cuda[:i]", or "cpu" for the host twin of the kernels')
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.unfold and args.fold is not None:
+        p.error("--unfold and --fold exclude each other: the output is either plain or symmetry-folded")
+    return args
 
 
 def _capacity_for(rows: int) -> int:
@@ -80,9 +94,9 @@ def main(argv=None):
         if int(sd["board_size"]) != int(first["board_size"]):
             raise SystemExit(f"{path}: board size {sd['board_size']}, {args.inputs[0]} has {first['board_size']}")
         folded_in.append(bool(sd.get("symmetric", False)))
-        if args.fold is None and folded_in[-1] != folded_in[0]:
+        if args.fold is None and not args.unfold and folded_in[-1] != folded_in[0]:
             raise SystemExit(f"{path} and {args.inputs[0]}: a symmetry-folded table (train.py --symmetric) and a plain "
-                             "one cannot be merged (--fold folds the plain ones)")
+                             "one cannot be merged (--fold folds the plain ones, --unfold unfolds the folded ones)")
         if int(sd["flags"]) & FLAG_INDEPENDENT:
             raise SystemExit(f"{path} was trained with private rows per env (Q2048_FLAG_INDEPENDENT): its keys are "
                              "salted by env id and mean nothing in another learner's table")
@@ -101,7 +115,11 @@ def main(argv=None):
 
     if args.fold is not None and n != 4:
         raise SystemExit(f"--fold: symmetry folding is built for board size 4 only, {args.inputs[0]} has {n}")
-    dst = agent_of(_capacity_for(sum(rows_in)), args.fold is not None or folded_in[0])
+    if args.unfold and n != 4 and any(folded_in):
+        raise SystemExit(f"--unfold: symmetry folding is built for board size 4 only, {args.inputs[0]} has {n}")
+    # (--unfold: a folded row becomes up to eight)
+    bound = sum(8 * r if args.unfold and f else r for r, f in zip(rows_in, folded_in))
+    dst = agent_of(_capacity_for(bound), not args.unfold and (args.fold is not None or folded_in[0]))
     mode, weight = {"mean": ("add", 1.0 / K), "sum": ("add", 1.0), "maxabs": ("maxabs", 1.0),
                     "first": ("blend", 0.0), "last": ("blend", 1.0)}[args.mode]
     merges = []
@@ -113,6 +131,8 @@ def main(argv=None):
         del sd
         if dst.symmetric and not folded:              # (--fold: a plain input enters through its orbits)
             merges.append(dst.fold_from(scratch, fold=args.fold, mode=mode, weight=weight))
+        elif folded and not dst.symmetric:            # (--unfold: a folded input enters through its images)
+            merges.append(dst.unfold_from(scratch, mode=mode, weight=weight))
         else:
             merges.append(dst.merge_from(scratch, mode=mode, weight=weight))
         if dst.on_gpu:
@@ -123,6 +143,9 @@ def main(argv=None):
     out.update(first)                                 # hyper-parameters, schedule, seed, progress: the first input's
     out.update({"capacity_log2": dst.capacity_log2, "stats_i": stats_i, "stats_f": stats_f, "ctr": ctr,
                 "merged": {"inputs": [os.path.basename(p) for p in args.inputs], "mode": args.mode}})
+    if args.unfold:
+        out.pop("symmetric", None)                    # (the first input's, if that one was folded)
+        out["merged"]["unfolded_inputs"] = [os.path.basename(p) for p, f in zip(args.inputs, folded_in) if f]
     if args.fold is not None:
         out["symmetric"] = True
         out["merged"].update({"fold": args.fold, "folded_inputs": [os.path.basename(p) for p, f in
@@ -134,6 +157,8 @@ def main(argv=None):
               "capacity_log2": dst.capacity_log2, "seconds": round(time.time() - t0, 3)}
     if args.fold is not None:
         report["fold"] = args.fold
+    if args.unfold:
+        report["unfold"] = True
     print(json.dumps(report))
     return out
 

@@ -112,6 +112,12 @@ def parse_args(argv=None):
                         "action the mean over the images with a row / over the images whose entry was ever trained / "
                         "the sum / the entry of largest magnitude).  Schedule, statistics and draw counter resume as "
                         "without it; the saved visit rows are dropped.  Without --fold a plain file is refused")
+    p.add_argument("--unfold", action="store_true",
+                   help="with --resume FOLDED, without --symmetric: the file holds a SYMMETRY-FOLDED table; unfold it into "
+                        "this run's plain one (q2048_table_unfold: every row becomes the rows of its board's eight mirror "
+                        "images, each in that image's own frame) -- how a folded file continues under --deterministic or "
+                        "in the one-env loop.  Schedule, statistics and draw counter resume as without it; the saved "
+                        "visit rows are dropped.  Without --unfold a folded file is refused")
     p.add_argument("--launch-timeout", type=float, default=86400.0,
                    help="self-launched ranks (--gpus N > 1 outside torchrun) are stopped after this many seconds")
     p.add_argument("--stop-epoch", type=int, default=0, help="stop (and --save) once this many epochs of the "
@@ -155,7 +161,10 @@ def train_single(args, pkg):
     first_episode = 0
     if args.resume:
         sd = _load(args.resume, 0)
-        agent._b.load_state_dict(sd)
+        if args.unfold:
+            _unfold_into(pkg, agent._b, sd, args, agent._b.device)
+        else:
+            agent._b.load_state_dict(sd)
         first_episode = _resume_schedule(agent._b, sd, args, 1)
     log_file = args.log                                                                # :71
     with open(log_file, mode="w", newline="") as file:                                 # :74-76
@@ -235,6 +244,8 @@ def train_batched(args, pkg):
         sd = _load(args.resume, rank)
         if args.fold:
             _fold_into(pkg, agent, sd, args, dev)
+        elif args.unfold:
+            _unfold_into(pkg, agent, sd, args, dev)
         else:
             agent.load_state_dict(sd)
         epoch0 = _resume_schedule(agent, sd, args, shard.total_envs)
@@ -433,6 +444,33 @@ def _fold_into(pkg, agent, sd, args, dev):
     print(f"folded {args.resume}: {out['read']} plain rows -> {out['created']} rows ({args.fold})", flush=True)
 
 
+def _unfold_into(pkg, agent, sd, args, dev):
+    """--resume FOLDED --unfold: `_fold_into`'s sibling.  Everything but the table loads as always (an empty plain
+    table), then the file's folded table is loaded into a scratch symmetric agent and unfolded into the run's
+    (BatchedQLearningAgent.unfold_from)."""
+    import numpy as np
+
+    if not sd.get("symmetric", False):
+        raise SystemExit(f"--unfold: {args.resume} already holds a plain table; resume it without --unfold")
+    if int(sd["board_size"]) != 4:
+        raise SystemExit(f"--unfold: {args.resume} has board size {sd['board_size']}; symmetry folding is built for 4 only")
+    table = {k: sd[k] for k in ("keys", "q", "table") if k in sd}
+    head = {k: v for k, v in sd.items() if k not in ("keys", "q", "table", "visit_rows", "symmetric")}
+    head.update({"keys": np.zeros((0,), np.uint64), "q": np.zeros((0, 4), np.float32)})
+    agent.load_state_dict(head)                   # schedule, statistics, counters; the table starts empty
+    rows = len(table["q"]) if "q" in table else 0
+    cap = int(sd["capacity_log2"]) if "table" in table else max(16, (2 * max(rows, 1) - 1).bit_length())
+    scratch = pkg.BatchedQLearningAgent(1, learning_rate=sd["lr"], discount_factor=sd["gamma"], capacity_log2=cap,
+                                        device=dev, board_size=4, placement="plain", freeze_load=None, row_cache=False,
+                                        symmetric=True)
+    scratch.load_state_dict({**head, **table, "symmetric": True})
+    try:
+        out = agent.unfold_from(scratch, mode="add", weight=1.0)
+    except ValueError as exc:
+        raise SystemExit(f"--unfold: {exc} (up to eight rows per row of {args.resume}: raise --capacity-log2)")
+    print(f"unfolded {args.resume}: {out['read']} folded rows -> {out['created']} rows", flush=True)
+
+
 def _load(path, rank):
     import torch
 
@@ -471,6 +509,12 @@ def main(argv=None):
             raise SystemExit("--fold folds a plain file into a symmetry-folded table: it needs --symmetric")
         if not args.resume:
             raise SystemExit("--fold says how the plain file of --resume is folded: it needs --resume")
+    if args.unfold:
+        if args.symmetric:
+            raise SystemExit("--unfold unfolds a folded file into a PLAIN table: not together with --symmetric (a "
+                             "folded file resumes under --symmetric as it is)")
+        if not args.resume:
+            raise SystemExit("--unfold says that the file of --resume is symmetry-folded: it needs --resume")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # the parent of the job has made no GPU call: one fresh process per rank (launch.py)
         spec = importlib.util.spec_from_file_location(
