@@ -1921,7 +1921,8 @@ __global__ __launch_bounds__(kBlock) void k_rt_update(float* w, const uint8_t* s
 __global__ __launch_bounds__(kBlock) void k_rt_fused_rollout(
     uint8_t* boards, q2048_aux* aux, float* w, int64_t B, int steps, double eps, double lr,
     double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f,
-    uint32_t* /*status: nothing data-dependent can go wrong on this path*/) {
+    uint32_t* /*status: nothing data-dependent can go wrong on this path -- a cell >= 16 is not reported, it
+                aliases by pack_row's mask (16 reads the entries of cell 0: test_lookup_at_the_edges)*/) {
   __shared__ BlockStats bs;
   stats_clear(bs);
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;

@@ -430,6 +430,13 @@ class RowTupleAgent:
         buf = (C.c_float * (4 * 65536 * 4)).from_address(self._w)
         return np.frombuffer(buf, dtype=np.float32).reshape(4, 65536, 4).copy()
 
+    def set_weights(self, w) -> None:
+        """Loads float32 [4, 65536, 4] weights (copied; the argument is left alone)."""
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        if w.shape != (4, 65536, 4):
+            raise ValueError("weights must have shape (4, 65536, 4)")
+        C.memmove(self._w, w.ctypes.data, w.nbytes)
+
     def choose_action(self, board, draw_eps, draw_act) -> int:
         return lib().orc_rt_choose(self._w, _u8(self._b(board)), self.epsilon, int(draw_eps),
                                    int(draw_act), None)
