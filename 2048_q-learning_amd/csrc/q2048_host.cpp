@@ -15,9 +15,11 @@
 // fallback: the package loads it only when asked for by name, and nothing of oracle/ is linked or called.
 // `stream` arguments are ignored (every call is complete when it returns).  Not here: the chunked device
 // allocator (q2048_table_alloc / _reserve / _grow*: Q2048_ERR_UNSUPPORTED -- host tables are the caller's
-// plain memory) and the row cache as an optimisation (rows that exist are read from the table every time; the
-// records the device would leave are written as EMPTY ones).  The one thing the cache carries that is not an
-// optimisation IS here: the visit row of a state without a row under Q2048_FLAG_NO_NEW_ROWS (a ROWLESS record).
+// plain memory) and, in the ROLLOUTS, the row cache as an optimisation (rows that exist are read from the table
+// every time; the records a device rollout would leave are written as EMPTY ones -- what the cache carries that is
+// not an optimisation IS there: the visit row of a state without a row under Q2048_FLAG_NO_NEW_ROWS, a ROWLESS
+// record).  q2048_q_choose_cached / q2048_q_update_cached keep the whole cache as include/q2048.h defines it: a
+// record that matches is USED instead of the table's row, and the update leaves the device's record byte for byte.
 // Threads: Q2048_HOST_THREADS (default: the hardware's, at most one per 2048 envs), read at every call.
 //
 //   g++ -O3 -std=c++17 -fPIC -shared -pthread -I include -I 2048_q-learning_amd/csrc \
@@ -233,6 +235,38 @@ inline void visit_put(void* cache, int64_t i, const q2048_slot* table, u64 mask,
   r.slot = kCacheRowless | cache_tag(table, mask);
 }
 
+// ---- the row cache of q2048_q_choose_cached / q2048_q_update_cached (include/q2048.h), as the kernels keep it ------
+// A record is used when its key is the key of the board passed in AND it carries this table's tag: the row is then
+// the record's (it does not see what was written to the table since) and `slot` its slot -- kNoSlot for a rowless
+// record, which only a call with Q2048_FLAG_NO_NEW_ROWS accepts.
+template <int N>
+inline bool cache_get(const void* cache, int64_t i, const q2048_slot* table, u64 mask, const typename Geo<N>::Key& key, Row& row,
+                      int64_t& slot, bool rowless_ok) {
+  if (cache == nullptr) return false;
+  const RowCache<N>& r = static_cast<const RowCache<N>*>(cache)[i];
+  if (!rec_key_is(r, key) || (r.slot & ~kCacheSlotMask) != cache_tag(table, mask)) return false;
+  const u64 v = r.slot & kCacheSlotMask;
+  if (v == kCacheRowless && !rowless_ok) return false;
+  slot = v == kCacheRowless ? kNoSlot : (int64_t)v;
+  row = Row{r.q[0], r.q[1], r.q[2], r.q[3]};
+  return true;
+}
+// the record an update leaves: the row read as next_state with its slot; without a row, the visit row (`rowless`)
+// or nothing to remember (key 0)
+inline void rec_set_hi(RowCache<4>&, const Geo<4>::Key&) {}
+inline void rec_set_hi(RowCache<5>& r, const Geo<5>::Key& k) { r.key_hi = k.k1; }
+template <int N>
+inline void cache_put(void* cache, int64_t i, const q2048_slot* table, u64 mask, const typename Geo<N>::Key& key, const Row& row,
+                      int64_t slot, bool rowless) {
+  if (cache == nullptr) return;
+  RowCache<N>& r = static_cast<RowCache<N>*>(cache)[i];
+  std::memset(&r, 0, sizeof r);
+  r.key = (slot >= 0 || rowless) ? key.k0 : 0ull;
+  rec_set_hi(r, key);
+  r.q[0] = row.q0; r.q[1] = row.q1; r.q[2] = row.q2; r.q[3] = row.q3;
+  r.slot = (slot >= 0 ? ((u64)slot & kCacheSlotMask) : kCacheRowless) | cache_tag(table, mask);
+}
+
 // q2048_rowcache_rebind: visit rows follow their table's rows into another allocation; every other record is emptied
 template <int N>
 void rowcache_rebind_n(void* row_cache, int64_t B, u64 tag_from, u64 tag_to) {
@@ -407,7 +441,9 @@ void q_choose_impl_n(const q2048_slot* table, u64 mask, const uint8_t* boards, i
       else {
         Row r;
         const auto key = state_key(b, salt, status);
-        if (probe_find(table, mask, key, r) < 0 && frozen) visit_get<N>(cache, i, table, mask, key, r);   // the env's visit row
+        int64_t slot;
+        // the env's record (closed key set: also its visit row), else the table
+        if (!cache_get<N>(cache, i, table, mask, key, r, slot, frozen)) probe_find(table, mask, key, r);
         act = argmax4(r.q0, r.q1, r.q2, r.q3);
       }
       actions[i] = (uint8_t)act;
@@ -452,8 +488,10 @@ void q_update_impl_n(q2048_slot* table, u64 mask, const uint8_t* s, const uint8_
       const auto key_n = state_key(b_n, salt, status);
       Row rs, rn;
       bool ins_s = false, ins_n = false;
-      const int64_t slot = find_or_create(table, mask, key_s, rs, ins_s, create);     // q_table[state] (:43)
-      if (slot < 0 && !create) visit_get<N>(cache, i, table, mask, key_s, rs);       // closed key set: the env's visit row
+      // q_table[state] (:43): the row this env carried over from its last update (closed key set: or its visit row),
+      // else the table's, created when absent
+      int64_t slot = kNoSlot;
+      if (!cache_get<N>(cache, i, table, mask, key_s, rs, slot, !create)) slot = find_or_create(table, mask, key_s, rs, ins_s, create);
       rn = rs;
       const bool same = key_eq(key_n, key_s);
       int64_t slot_n = slot;
@@ -461,13 +499,14 @@ void q_update_impl_n(q2048_slot* table, u64 mask, const uint8_t* s, const uint8_
       st.i[Q2048_ST_INSERTS] += (uint64_t)ins_s + (uint64_t)ins_n;
       const float max_next = max4(rn.q0, rn.q1, rn.q2, rn.q3);
       if (slot >= 0) {
-        td_update(&table[slot], act, row_get(rs, act), reward[i], max_next, done[i] != 0, lr, gamma, cas, tdc);
+        const float nq = td_update(&table[slot], act, row_get(rs, act), reward[i], max_next, done[i] != 0, lr, gamma, cas, tdc);
+        if (same) row_set(rn, act, nq);                           // the row it stays on just changed (:100)
       } else {
         st.i[Q2048_ST_DROPS] += 1;
         if (create) status_or(status, Q2048_STATUS_TABLE_FULL);   // (closed key set: the caller's policy)
         else if (same) row_set(rn, act, td_value(row_get(rs, act), reward[i], max_next, done[i] != 0, lr, gamma));
       }
-      visit_put<N>(cache, i, table, mask, key_n, rn, !create && slot_n < 0);
+      cache_put<N>(cache, i, table, mask, key_n, rn, slot_n, !create);
     }
     st.i[Q2048_ST_CAS_RETRY] += tdc.retries;
     st.i[Q2048_ST_CAS_FALLBACK] += tdc.fallbacks;

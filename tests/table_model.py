@@ -330,3 +330,93 @@ def random_rows(rng, rows, key_words):
     keys = keys[np.sort(first)][:rows]
     assert len(keys) == rows
     return (keys if key_words == 2 else keys[:, 0]), rng.standard_normal((rows, 4)).astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The 4-call API (q_choose / q_update and their row cache), restated from include/q2048.h and the comments of
+# csrc/q2048_core.hpp / q2048_core5.hpp.
+#   state key   4x4: key4_of_cells ^ salt, and 1 where that is 0 (0 marks an empty slot).  5x5: word 0 ^ (salt with bit 63
+#               cleared), word 1 ^ (mix64(salt) with bits 62 and 63 cleared): both words keep their bit 63.
+#   salt        0, or with Q2048_FLAG_INDEPENDENT mix64(global env id + 0x2048) | 1.
+#   record      one per env.  n = 4 (32 bytes): key, four float32 values, slot.  n = 5 (48 bytes): key, four values, the
+#               second key word, slot, a pad that is 0.  `slot` = the row's slot index in its low 40 bits -- all ones for
+#               a ROWLESS record, the visit row of a state without a row -- and the table's 24-bit tag above them.
+#               A record whose key is 0 is empty, whatever else it holds.
+#   td_value    Agent/main.py:41-43 in float64 with the product and the sum rounded separately, rounded to float32 once.
+# ---------------------------------------------------------------------------------------------------------------
+FLAG_INDEPENDENT, FLAG_TD_CAS, FLAG_NO_NEW_ROWS = 1, 4, 128
+CACHE_SLOT_MASK = (1 << 40) - 1
+ROWLESS = CACHE_SLOT_MASK
+RECORD = {4: np.dtype([("key", "<u8"), ("q", "<f4", (4,)), ("slot", "<u8")]),
+          5: np.dtype([("key", "<u8"), ("q", "<f4", (4,)), ("key_hi", "<u8"), ("slot", "<u8"), ("pad", "<u8")])}
+assert RECORD[4].itemsize == 32 and RECORD[5].itemsize == 48
+
+
+def lane_salt(env_ids):
+    """The salt of Q2048_FLAG_INDEPENDENT for these global env ids (uint64, wrapping)."""
+    with np.errstate(over="ignore"):
+        return mix64(np.asarray(env_ids, dtype=U) + U(0x2048)) | U(1)
+
+
+def state_key(cells, n, salt=None):
+    """The table key of boards [R, n * n] (uint8 log2 tiles): uint64 [R] for n = 4, [R, 2] for n = 5.  salt: None (a
+    shared table) or uint64 [R]."""
+    if n == 4:
+        k = key4_of_cells(cells)
+        if salt is not None:
+            k = k ^ np.asarray(salt, dtype=U)
+        return np.where(k == 0, U(1), k)
+    k = key5_of_cells(cells)
+    if salt is not None:
+        salt = np.asarray(salt, dtype=U)
+        k = np.stack([k[:, 0] ^ (salt & U(BIT63 - 1)), k[:, 1] ^ (mix64(salt) & U((1 << 62) - 1))], axis=1)
+    return k
+
+
+def cache_tag(address, cap_log2):
+    """The 24-bit tag (in bits 40..63) of the table at `address` with 2^cap_log2 slots."""
+    mask = (1 << cap_log2) - 1
+    return int(mix64(U((address ^ (mask * GOLDEN)) & _M64))) & ~CACHE_SLOT_MASK & _M64
+
+
+def pack_records(n, keys, q, slots, tag):
+    """Records for these rows: keys [R] / [R, 2], q float32 [R, 4], slots int (ROWLESS for a visit row), one tag."""
+    k = keys2d(keys, 1 if n == 4 else 2)
+    rec = np.zeros(len(k), RECORD[n])
+    rec["key"] = k[:, 0]
+    if n == 5:
+        rec["key_hi"] = k[:, 1]
+    rec["q"] = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 4)
+    rec["slot"] = np.asarray(slots, dtype=U) | U(tag)
+    return rec
+
+
+def unpack_records(n, rec):
+    """-> dict of keys [R, key_words], q bits uint32 [R, 4], slot (low 40 bits), tag, rowless, pad (n = 5, else zeros)."""
+    rec = np.asarray(rec).view(RECORD[n]).reshape(-1)
+    keys = rec["key"][:, None] if n == 4 else np.stack([rec["key"], rec["key_hi"]], axis=1)
+    slot = rec["slot"] & U(CACHE_SLOT_MASK)
+    return dict(keys=keys, qbits=np.ascontiguousarray(rec["q"]).view(np.uint32), slot=slot,
+                tag=rec["slot"] & ~U(CACHE_SLOT_MASK), rowless=slot == U(ROWLESS),
+                pad=rec["pad"] if n == 5 else np.zeros(len(rec), U))
+
+
+def td_value(q_sa, reward, max_next, done, lr, gamma):
+    """The new Q[s][a]: float32 inputs widened to float64, `gamma * max_next`, `reward + that * (0 if done else 1)`,
+    `lr * (target - q)` and `q + that` each rounded on its own (Python floats: no fused multiply-add), then one
+    rounding to float32."""
+    q, r, m = float(np.float32(q_sa)), float(np.float32(reward)), float(np.float32(max_next))
+    bootstrap = float(gamma) * m
+    target = r + bootstrap * (0.0 if done else 1.0)
+    step = float(lr) * (target - q)
+    return np.float32(q + step)
+
+
+def find_slot(image, key, key_words):
+    """The slot that holds `key` (a tuple of key_words ints) in an image, or -1: by scanning the words, not by probing."""
+    hit = image[:, 0] == U(key[0])
+    if key_words == 2:
+        hit &= image[:, 3] == U(key[1])
+    at = np.flatnonzero(hit)
+    assert len(at) <= 1
+    return int(at[0]) if len(at) else -1
