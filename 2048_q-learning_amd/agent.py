@@ -1130,6 +1130,9 @@ class BatchedQLearningAgent:
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
+        if sd.get("kind") == "row_tuple":         # (a file without "kind" is a hash table: every earlier checkpoint)
+            raise ValueError("this checkpoint holds row-tuple weights (BatchedRowTupleAgent), not a hash table: the "
+                             "two kinds do not load into each other")
         if sd["board_size"] != self.board_size:
             raise ValueError("checkpoint was taken with another board size")
         if bool(sd.get("symmetric", False)) != self.symmetric:
@@ -1449,6 +1452,7 @@ class BatchedRowTupleAgent:
         self.seed, self.env_id0, self.ctr, self.board_size = int(seed), int(env_id0), 0, 4
         self.weights = torch.zeros((4, 65536, 4), dtype=torch.float32, device=self.device)
         self.stats_i, self.stats_f = new_stats_vectors(self.device)
+        self._play_stats = None                   # the player's own statistics (play_rollout / play_stats)
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     epsilon = property(lambda self: self.schedule.epsilon,
@@ -1509,6 +1513,37 @@ class BatchedRowTupleAgent:
         env.ctr += int(steps)
         self.ctr += int(steps)
 
+    def play_rollout(self, env: BatchedGame2048Env, steps: int, epsilon: float = 0.0) -> None:
+        """The greedy player on the weights (q2048_rt_play_rollout), `BatchedQLearningAgent.play_rollout` with this
+        learner's row: `steps` steps of every env in ONE launch, each the first maximum of `q_values(board)` over the
+        moves that CHANGE the board (with probability `epsilon` a uniformly drawn legal move instead), the env step,
+        and on done the episode statistics and the reset.  The weights are only read.  The player is a function of
+        (weights, env): seed, env_id0 and the step counter are the ENV's, and so is its profile (`fused_rollout`
+        keeps refusing profiles); `env.ctr` advances, `agent.ctr` does not.  Statistics go to a buffer of the
+        player's own (`play_stats`), never into the training statistics."""
+        if env.device != self.device:
+            raise ValueError("env and agent live on different devices")
+        if env.board_size != 4:
+            raise ValueError("the row-tuple learner plays 4x4 boards only")
+        if self._play_stats is None:
+            self._play_stats = new_stats_vectors(self.device)
+        si, sf = self._play_stats
+        N.check(self._L.q2048_rt_play_rollout(
+            _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), env.num_envs, int(steps), float(epsilon), env.seed,
+            env.env_id0, env.ctr & 0xFFFFFFFF, env.env_flags, _ptr(si), _ptr(sf), _ptr(self.status),
+            _stream(self.device)), "rt_play_rollout")
+        env.ctr += int(steps)
+
+    def play_stats(self, reset: bool = False) -> dict:
+        """Synchronising host copy of the player's statistics (the dict of `stats()`; inserts and drops are 0)."""
+        if self._play_stats is None:
+            self._play_stats = new_stats_vectors(self.device)
+        out = stats_dict(*(v.cpu().numpy() for v in self._play_stats))   # (read before the reset: on "cpu" these are views)
+        if reset:
+            for v in self._play_stats:
+                v.zero_()
+        return out
+
     def stats(self, reset: bool = False) -> dict:
         si, sf = self.stats_i.cpu().numpy(), self.stats_f.cpu().numpy()
         if reset:
@@ -1522,6 +1557,38 @@ class BatchedRowTupleAgent:
             self.status.zero_()
             raise ValueError("an action outside 0..3 was passed to update_q_value()")
         return s
+
+    # -- checkpoint / resume ------------------------------------------------------------------
+    def state_dict(self, compact: bool = True) -> dict:
+        """Host copy of the learner: {"kind": "row_tuple"}, the weights (float32 [4, 65536, 4]), lr / gamma, the
+        epsilon schedule, seed / env_id0 / ctr and the two statistics vectors.  (`compact` is the hash-table
+        agent's choice between rows and raw table; there is one form here.)"""
+        return {"kind": "row_tuple", "board_size": 4, "weights": self.weights.to("cpu", copy=True), "lr": self.lr,
+                "gamma": self.gamma, "schedule": dict(vars(self.schedule)), "seed": self.seed, "env_id0": self.env_id0,
+                "ctr": self.ctr, "stats_i": self.stats_i.to("cpu", copy=True),
+                "stats_f": self.stats_f.to("cpu", copy=True)}
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Everything is validated before anything of this agent, on the host or the device, is written."""
+        if sd.get("kind") != "row_tuple":
+            raise ValueError("this checkpoint holds a hash table (BatchedQLearningAgent), not row-tuple weights: the "
+                             "two kinds do not load into each other")
+        if int(sd["board_size"]) != 4:
+            raise ValueError("row-tuple weights are 4x4 only")
+        w, si, sf = sd["weights"], sd["stats_i"], sd["stats_f"]
+        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or tuple(w.shape) != (4, 65536, 4):
+            raise ValueError("weights must be a float32 tensor of shape (4, 65536, 4), got "
+                             f"{getattr(w, 'dtype', type(w).__name__)} {tuple(getattr(w, 'shape', ()))}")
+        if not isinstance(si, torch.Tensor) or si.dtype != torch.int64 or tuple(si.shape) != (N.NSTAT_I,) or \
+                not isinstance(sf, torch.Tensor) or sf.dtype != torch.float64 or tuple(sf.shape) != (N.NSTAT_F,):
+            raise ValueError(f"stats_i / stats_f must be int64 [{N.NSTAT_I}] / float64 [{N.NSTAT_F}]")
+        schedule, ctr, seed, env_id0 = dict(sd["schedule"]), int(sd["ctr"]), int(sd["seed"]), int(sd["env_id0"])
+        lr, gamma = float(sd["lr"]), float(sd["gamma"])
+        self.weights.copy_(w)
+        self.stats_i.copy_(si)
+        self.stats_f.copy_(sf)
+        self.ctr, self.seed, self.env_id0, self.lr, self.gamma = ctr, seed, env_id0, lr, gamma
+        vars(self.schedule).update(schedule)
 
 
 def new_stats_vectors(device):

@@ -55,6 +55,19 @@ static inline int check_merge(const void* dst, int dst_cap_log2, const void* src
   return Q2048_OK;
 }
 
+// What q2048_rt_play_rollout checks, in the order of q2048_play_rollout: B, flags (the env-profile bits and nothing
+// else: Q2048_FLAG_INDEPENDENT and Q2048_FLAG_SYMMETRIC mean nothing to weights), NULL, alignment, steps, eps.
+static inline int check_rt_play(const void* boards, const void* aux, const void* weights, int64_t B, int64_t steps,
+                                double eps, uint32_t flags, const void* status) {
+  if (int e = check_batch(B, 4)) return e;
+  if (int e = check_flags(flags, kAbiFlags & ~(Q2048_FLAG_ENV_DQN | Q2048_FLAG_RESET_SHAPING))) return e;
+  if (!boards || !aux || !weights || !status) return Q2048_ERR_NULL;
+  if (!aligned16(boards) || !aligned16(aux) || !aligned16(weights)) return Q2048_ERR_ALIGN;
+  if (steps < 0 || steps > (1 << 30)) return Q2048_ERR_SIZE;
+  if (!(eps >= 0.0 && eps <= 1.0)) return Q2048_ERR_RANGE;
+  return Q2048_OK;
+}
+
 // q2048_strerror
 static inline const char* error_text(int code) {
   switch (code) {

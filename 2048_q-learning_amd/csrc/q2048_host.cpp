@@ -1535,5 +1535,53 @@ int q2048_rt_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, int6
   stats_merge(parts, used, stats_i, stats_f);
   return Q2048_OK;
 }
+// the greedy player on weights: play_rollout_n's loop with q2048_rt_lookup's row (rt_q of rt_gather); the same
+// legal_mask / play_action as the kernel, envs split over the threads, the weights only read
+int q2048_rt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
+                          uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                          double* stats_f, uint32_t* status, void*) {
+  if (int e = check_rt_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  const uint64_t eps_t = eps_threshold(eps);
+  const ImageLuts lut{&g_lut_image};
+  const int env = env_bits(flags);
+  const int T = threads_for(B);
+  std::vector<Stats> parts((size_t)T);
+  Stats* sp = parts.data();
+  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+    Stats& st = sp[tid];
+    for (int64_t i = lo; i < hi; ++i) {
+      const uint64_t id = env_id0 + (uint64_t)i;
+      Board b;
+      load_board(boards, i, b);
+      Aux a = ld_aux(aux, i);
+      const DrawPrep prep = draws_prepare(seed, id, kStreamStep);
+      double reward_sum = 0.0;
+      for (int64_t t = 0; t < steps; ++t) {
+        const Draws x = draws_at(prep, ctr0 + (uint32_t)t);
+        Draws y{0u, 0u, 0u, 0u};
+        if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+        const Row q = rt_q(rt_gather(weights, b));
+        bool explored;
+        const int act = play_action(legal_mask(b), q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
+        const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+        st.i[Q2048_ST_VALID] += o.valid != 0;
+        st.i[Q2048_ST_EXPLORE] += explored;
+        reward_sum += (double)o.reward;
+        if (o.done) {
+          st.i[Q2048_ST_EPISODES] += 1;
+          st.episode(a, o.max_log2);
+          begin_episode(b, a, seed, id, (env & kEnvResetShaping) != 0);
+        }
+      }
+      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
+      st.f[Q2048_SF_REWARD] += reward_sum;
+      store_board(boards, i, b);
+      st_aux(aux, i, a);
+    }
+  });
+  stats_merge(parts, used, stats_i, stats_f);
+  return Q2048_OK;
+}
 
 }  // extern "C"

@@ -1978,6 +1978,78 @@ __global__ __launch_bounds__(kBlock) void k_rt_fused_rollout(
   stats_flush(bs, stats_i, stats_f);
 }
 
+// the greedy player on weights (q2048_rt_play_rollout): k_play_rollout's loop with q2048_rt_lookup's row -- per step
+// the four entries of the state (requested together, one wait), rt_q, the trial-move mask, play_action, the env
+// step on the step's own draws, and on done the episode statistics and the reset.  One lane per env, board and aux
+// in registers for the launch, one LutImage per workgroup in LDS; every loop is bounded by `steps`, no lane waits
+// for another.  W is only read: the launch boundary orders it against the training launches of the stream (the
+// vector L1 starts a kernel invalid), so the loads are PLAIN loads, not the learner's agent-scope sc1 ones -- nothing
+// writes W while this runs, and the entries most lanes share (rows of few tiles) may then be served from the CU's L1.
+// A kernel of its own, not k_play_rollout templated on a row source: no existing instantiation changes.
+__device__ __forceinline__ RtRows rt_gather_readonly(const float* w, const Board& b) {
+  u32x4 v0, v1, v2, v3;
+  asm volatile(
+      "global_load_dwordx4 %0, %4, off\n\tglobal_load_dwordx4 %1, %5, off\n\t"
+      "global_load_dwordx4 %2, %6, off\n\tglobal_load_dwordx4 %3, %7, off\n\t"
+      "s_waitcnt vmcnt(0)"
+      : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3)
+      : "v"(rt_addr(w, 0, pack_row(b.r0))), "v"(rt_addr(w, 1, pack_row(b.r1))),
+        "v"(rt_addr(w, 2, pack_row(b.r2))), "v"(rt_addr(w, 3, pack_row(b.r3)))
+      : "memory");
+  return RtRows{rt_row(v0), rt_row(v1), rt_row(v2), rt_row(v3)};
+}
+template <int ENV>
+__global__ __launch_bounds__(kBlock) void k_rt_play_rollout(
+    uint8_t* boards, q2048_aux* aux, const float* w, int64_t B, int steps, double eps, uint64_t seed,
+    uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
+  __shared__ BlockStats bs;
+  __shared__ Stage<4> st;
+  __shared__ LutImage lut_lds;
+  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
+  if (threadIdx.x < kLutImageDoubles)
+    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
+  stats_clear(bs);                                        // (its barrier publishes the image too)
+  const ImageLuts lut{&lut_lds};
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  Board b = load_board(boards, i, B, st);
+  if (i < B) {
+    const uint64_t id = env_id0 + (uint64_t)i;
+    Aux a = ld_aux(aux, i);
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
+    double reward_sum = 0.0;
+    const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
+    const uint64_t eps_t = eps_threshold(eps);
+    for (int t = 0; t < steps; ++t) {
+      const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
+      Draws y{0u, 0u, 0u, 0u};
+      if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+      const Row q = rt_q(rt_gather_readonly(w, b));
+      bool explored;
+      const int act = play_action(legal_mask(b), q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
+      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+      if (o.done) {
+        episode_stats(bs, a, o.max_log2);
+        begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
+      }
+      n_valid += wave_count(o.valid != 0);
+      n_explore += wave_count(explored);
+      n_done += wave_count(o.done != 0);
+      reward_sum += (double)o.reward;
+    }
+    st_aux(aux, i, a);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+    const uint32_t n_active = wave_count(true);
+    if (wave_leader()) {
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  store_board(boards, i, B, b, st);
+  stats_flush(bs, stats_i, stats_f);
+}
+
 // ---------------------------------------------------------------------------------------------
 // table utilities
 // ---------------------------------------------------------------------------------------------
@@ -3015,6 +3087,21 @@ int q2048_rt_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, int6
   hipLaunchKernelGGL(k_rt_fused_rollout, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream,
                      boards, aux, weights, B, (int)steps, eps, lr, gamma, seed, env_id0, ctr0, stats_i,
                      stats_f, status);
+  return launch_status();
+}
+
+int q2048_rt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
+                          uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                          double* stats_f, uint32_t* status, void* stream) {
+  if (int e = check_rt_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+#define Q2048_LAUNCH_RT_PLAY(E)                                                                                    \
+  case E:                                                                                                          \
+    hipLaunchKernelGGL((k_rt_play_rollout<E>), dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, boards,    \
+                       aux, weights, B, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);                   \
+    break;
+  switch (env_bits(flags) & 3) { Q2048_LAUNCH_RT_PLAY(0) Q2048_LAUNCH_RT_PLAY(1) Q2048_LAUNCH_RT_PLAY(2) Q2048_LAUNCH_RT_PLAY(3) }
+#undef Q2048_LAUNCH_RT_PLAY
   return launch_status();
 }
 

@@ -3,8 +3,9 @@
 
 The reference's README lists an `evaluate.py` ("script per la valutazione e il testing",
 README.md:52) that its repository does not contain.  This is that script for the MI355X path: it
-loads a learner written by `train.py --save`, plays `--episodes` games per env with the stored
-values -- rows are read, nothing is created or written -- and prints one JSON line: games, mean
+loads a learner written by `train.py --save` (a hash table, or -- "kind": "row_tuple" -- the row-tuple learner's
+weights: the file says which, and the JSON line then carries "agent": "row-tuple"), plays `--episodes` games per env
+with the stored values -- rows are read, nothing is created or written -- and prints one JSON line: games, mean
 score / return, max-tile histogram.  Two policies:
 
   --policy legal (default)   argmax of the stored row over the moves that CHANGE the board (the trial-move
@@ -67,6 +68,8 @@ def main(argv=None):
 
     pkg = importlib.import_module("2048_q-learning_amd")
     sd = torch.load(args.model, map_location="cpu", weights_only=False)
+    if sd.get("kind") == "row_tuple":
+        return main_row_tuple(args, torch, pkg, sd)
     n, rows = int(sd["board_size"]), len(sd["q"])
     cap = max(int(sd["capacity_log2"]), 4) if "table" in sd else max(16, (2 * max(rows, 1) - 1).bit_length())
     agent = pkg.BatchedQLearningAgent(1, learning_rate=sd["lr"], discount_factor=sd["gamma"],
@@ -105,8 +108,45 @@ def main(argv=None):
     return st
 
 
+def main_row_tuple(args, torch, pkg, sd):
+    """A file of `train.py --agent row-tuple --save`: the same three policies on a `BatchedRowTupleAgent`.  There are no
+    rows to count: what must not change is the weights, all 4 MiB, bit for bit."""
+    agent = pkg.BatchedRowTupleAgent(1, learning_rate=sd["lr"], discount_factor=sd["gamma"],
+                                     exploration_rate=args.epsilon, seed=args.seed, device=args.device)
+    agent.load_state_dict(sd)
+    agent.seed, agent.ctr, agent.epsilon = args.seed, 0, args.epsilon     # evaluation has its own draws
+    agent.stats(reset=True)
+    env = pkg.BatchedGame2048Env(args.num_envs, 4, args.device, args.seed, agent.env_id0,
+                                 profile=args.env_profile, reset_shaping_state=args.reset_shaping_state)
+    before = agent.weights.to("cpu", copy=True)
+    target, t0 = args.episodes * args.num_envs, time.time()
+    if args.policy == "legal" and args.fused:
+        st = play_fused(agent, env, args, target)
+    elif args.policy == "legal":
+        st = play_legal_moves(torch, agent, env, args, target)
+    else:
+        agent.lr = 0.0                            # the lr = 0 agent: every delta is +-0 (a trained weight is never -0)
+        st = agent.stats()
+        while st["episodes"] < target and env.ctr < args.max_steps:
+            for _ in range(4):
+                agent.fused_rollout(env, args.steps_per_launch)
+            st = agent.stats()
+    assert torch.equal(before.view(torch.int32), agent.weights.cpu().view(torch.int32))   # nothing was learnt
+    out = {"model": args.model, "agent": "row-tuple", "board_size": 4, "epsilon": args.epsilon, "policy": args.policy,
+           "envs": args.num_envs, "games": st["episodes"], "env_steps": st["steps"],
+           "mean_score": st["mean_score"], "mean_return": st["mean_return"],
+           "valid_move_frac": st["valid_moves"] / max(st["steps"], 1),
+           "max_tile_hist": {str(k): v for k, v in st["max_tile_hist"].items()},
+           "best_tile": max(st["max_tile_hist"], default=0),
+           "seconds": round(time.time() - t0, 3)}
+    if args.fused:
+        out["fused"] = True
+    print(json.dumps(out))
+    return st
+
+
 def play_fused(agent, env, args, target) -> dict:
-    """`play_legal_moves` in one launch per `--steps-per-launch` steps (`BatchedQLearningAgent.play_rollout`): the same
+    """`play_legal_moves` in one launch per `--steps-per-launch` steps (`play_rollout` of either agent class): the same
     cadence -- the number of finished games is read once per launch -- and, at --epsilon 0, the same games."""
     agent.play_stats(reset=True)
     st = agent.play_stats()

@@ -66,7 +66,8 @@ extern "C" {
                                caller detects it by its symbol; so did q2048_play_rollout (the greedy player over the
                                legal moves, one launch) and Q2048_FLAG_SYMMETRIC (one row for a board's eight mirror
                                images), detected by the symbol q2048_canonicalize; q2048_table_fold and
-                               q2048_table_unfold (into and out of a folded table) likewise, each by its symbol */
+                               q2048_table_unfold (into and out of a folded table) likewise, each by its symbol;
+                               q2048_rt_play_rollout (the greedy player on row-tuple weights) too, by its symbol */
 
 /* return codes */
 #define Q2048_OK 0
@@ -733,7 +734,11 @@ int q2048_encode_onehot(const uint8_t *boards, int64_t B, int dtype, void *out, 
  * Same epsilon-greedy / TD target as Agent/main.py:34-43; the error is spread evenly over the
  * four weights, each written as (value read + delta) -- concurrent lanes race per weight and the
  * last writer wins (summing all lanes' deltas would scale the step size by the batch size).
- * 4x4 boards only. */
+ * 4x4 boards only.
+ * A cell >= 16 is not an error on this family: the row index takes each cell's low nibble, so 16 reads the entries
+ * of an empty cell and nothing reports it.
+ * The family: _choose / _lookup / _update (the four-call loop), _fused_rollout (the learner, `steps` steps per launch)
+ * and _play_rollout (the greedy player over the legal moves, `steps` steps per launch, weights only read). */
 int q2048_rt_choose(const float *weights, const uint8_t *boards, int64_t B, double eps,
                     uint64_t seed, uint64_t env_id0, uint32_t ctr, uint8_t *actions, void *stream);
 int q2048_rt_lookup(const float *weights, const uint8_t *boards, int64_t B, float *q_out,
@@ -745,6 +750,34 @@ int q2048_rt_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weights, int6
                            int64_t steps, double eps, double lr, double gamma, uint64_t seed,
                            uint64_t env_id0, uint32_t ctr0, int64_t *stats_i, double *stats_f,
                            uint32_t *status, void *stream);
+
+/* The GREEDY PLAYER ON WEIGHTS: q2048_play_rollout's loop with a different row source, 4x4 only -- what trained
+ * weights are worth when only moves that change the board are made, `steps` steps for B envs in ONE launch.  It
+ * replaces the loop rt_lookup / legal_moves / env_step / env_reset(done).  One step of one env (lane i = global env
+ * env_id0 + i, counter ctr0 + t):
+ *   row     BY DEFINITION what q2048_rt_lookup returns for the board: per action a,
+ *           (W[0][i0][a] + W[1][i1][a]) + (W[2][i2][a] + W[3][i3][a]) in float32 with that association, i_r the low
+ *           nibbles of row r's four cells (a cell >= 16 aliases, see above);
+ *   mask, action, explore, step
+ *           exactly q2048_play_rollout's: the trial-move mask of q2048_legal_moves; the first maximum of the row over
+ *           the legal moves (ascending, strict >), action 0 with no legal move; the DRAW CONTRACT of the player -- one
+ *           Philox call per step, the env explores iff x0 < ceil(eps * 2^32) AND it has a legal move, its move is then
+ *           the k-th legal one in ascending order, k = (x1 * n_legal) >> 32, and a step without a legal move is not
+ *           counted as explored; x2, x3 of the same call spawn (Q2048_FLAG_ENV_DQN: the DQN path's env, words 0, 1 of
+ *           stream 2); on done the episode statistics, then the reset of q2048_fused_rollout.
+ * Written: boards, aux and the statistics (steps, valid, explore, episodes, the score / return sums, the max-tile
+ * histogram, the reward sum, ADDED to stats_i / stats_f; either may be NULL) -- nothing else.  `weights` is const: all
+ * 4 MiB are bit-identical afterwards, and `status` is required and never written.  The result is a function of
+ * (weights, boards, aux, seed, env ids, counter) at any B.  On the device the weights are read with plain loads:
+ * launches on one stream order them against q2048_rt_fused_rollout / q2048_rt_update.
+ * flags: Q2048_FLAG_ENV_DQN, Q2048_FLAG_RESET_SHAPING; any other bit -- Q2048_FLAG_INDEPENDENT and
+ * Q2048_FLAG_SYMMETRIC included, neither means anything to weights -- is Q2048_ERR_FLAGS.  Argument errors, checked on
+ * the host before anything is launched, in this order: B (Q2048_ERR_SIZE), flags, boards / aux / weights / status NULL,
+ * their 16-byte alignment (boards, aux, weights), steps < 0 or > 2^30 (Q2048_ERR_SIZE), eps outside [0, 1]
+ * (Q2048_ERR_RANGE).  A refused call writes nothing.  B == 0 or steps == 0: checked, then nothing happens, Q2048_OK. */
+int q2048_rt_play_rollout(uint8_t *boards, q2048_aux *aux, const float *weights, int64_t B, int64_t steps,
+                          double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
+                          int64_t *stats_i, double *stats_f, uint32_t *status, void *stream);
 
 /* Inverse of q2048_table_export (resume / load a table trained elsewhere): inserts `rows`
  * (key, q[4]) pairs into the table, key_words as above.  A key already present has its row

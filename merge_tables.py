@@ -89,6 +89,9 @@ def main(argv=None):
     first, rows_in, folded_in, stats_i, stats_f, ctr = None, [], [], None, None, 0
     for path in args.inputs:
         sd = torch.load(path, map_location="cpu", weights_only=False)
+        if sd.get("kind") == "row_tuple":
+            raise SystemExit(f"{path} holds row-tuple weights, not a hash table: the two kinds do not mix, and averaging "
+                             "weight replicas is not built")
         if first is None:
             first = {k: v for k, v in sd.items() if k not in ("keys", "q", "table", "env", "visit_rows")}
         if int(sd["board_size"]) != int(first["board_size"]):

@@ -99,7 +99,8 @@ def parse_args(argv=None):
                    help="shaped = QLearningBase's Game2048_env (the reference's tabular path); nopenalty = "
                         "the DQN path's env (Deep_QLearning/environment/Game2048_nopenalty_env.py: reward = "
                         "merge score or -10, done = game over)")
-    p.add_argument("--save", default="", help="write the trained learner (Q-table rows, epsilon schedule, counters) "
+    p.add_argument("--save", default="", help="write the trained learner (Q-table rows -- or, --agent row-tuple, the "
+                   "4 MiB of weights under \"kind\": \"row_tuple\" --, epsilon schedule, counters) "
                    "to this file when training ends -- the models/ directory of the reference's README; "
                    "evaluate.py and --resume read it")
     p.add_argument("--resume", default="", help="continue from a file written by --save (same agent arguments): "
@@ -125,8 +126,9 @@ def parse_args(argv=None):
     p.add_argument("--summary", default="", help="after the run, write the per-episode log's summary row "
                    "(layout of the reference's plots/summary_statistics_cleaned.csv) to this CSV")
     p.add_argument("--eval-every", type=int, default=0,
-                   help="batched mode, hash-table agent: every N epochs measure the table as a PLAYER -- greedy over the "
-                        "moves that change the board (evaluate.py --policy legal --fused, q2048_play_rollout) on a "
+                   help="batched mode, either agent: every N epochs measure the learner as a PLAYER -- greedy over the "
+                        "moves that change the board (evaluate.py --policy legal --fused, q2048_play_rollout / "
+                        "q2048_rt_play_rollout) on a "
                         "separate env batch with its own seed, between two training launches on the training stream. "
                         "The table is only read and training's draws, counters and statistics are untouched: the run "
                         "trains what it trains without the flag.  0 (default) = off")
@@ -237,8 +239,6 @@ def train_batched(args, pkg):
                                           symmetric=args.symmetric)
     if args.deterministic and args.agent != "hash":
         raise SystemExit("--deterministic applies to the hash-table agent")
-    if (args.save or args.resume) and args.agent != "hash":
-        raise SystemExit("--save / --resume apply to the hash-table agent")
     epoch0 = 0
     if args.resume:
         sd = _load(args.resume, rank)
@@ -286,8 +286,6 @@ def train_batched(args, pkg):
     best_tile, grown, reports, said_frozen = 0, 0, 0, False
     evaluator = None
     if args.eval_every > 0:
-        if args.agent != "hash":
-            raise SystemExit("--eval-every applies to the hash-table agent")
         evaluator = _Evaluator(args, pkg, agent, dev, rank, world, epoch)
     agent.train_progress = {"epoch": epoch}
     agent.train_env = env
@@ -354,7 +352,7 @@ def train_batched(args, pkg):
 
 
 class _Evaluator:
-    """--eval-every: the table as a greedy player over the legal moves (`BatchedQLearningAgent.play_rollout`) on an
+    """--eval-every: the learner as a greedy player over the legal moves (`play_rollout` of either agent class) on an
     env batch of its own -- its own seed, derived from --seed; its own step counter -- queued on the training stream
     between two training launches.  The player reads the table and writes its env batch and its own statistics:
     the training env, the agent's counters, row cache, statistics and growth bookkeeping never see it."""
@@ -510,6 +508,8 @@ def main(argv=None):
         if not args.resume:
             raise SystemExit("--fold says how the plain file of --resume is folded: it needs --resume")
     if args.unfold:
+        if args.agent != "hash":
+            raise SystemExit("--unfold unfolds a hash table: not with --agent row-tuple")
         if args.symmetric:
             raise SystemExit("--unfold unfolds a folded file into a PLAIN table: not together with --symmetric (a "
                              "folded file resumes under --symmetric as it is)")
