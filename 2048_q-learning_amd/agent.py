@@ -1211,6 +1211,56 @@ class BatchedQLearningAgent:
 
     _MERGE_MODES = {"add": N.MERGE_ADD, "blend": N.MERGE_BLEND, "maxabs": N.MERGE_MAXABS}
 
+    def _combine_begin(self, other, what: str, kind_checks, mode: str, weight: float, rows_per_row: int, n_counters: int):
+        """The common front of merge_from / fold_from / unfold_from (`what`: "merge", "fold", "unfold"): the checks of
+        `other`, then the caller's own (`kind_checks()` raises), then mode, weight and the frozen rule; both growths
+        finished; the table sized for rows + rows_per_row * other's rows, an upper bound of the rows afterwards; row
+        cache and summaries invalidated.  Returns (rows, weight, counters, status): this agent's rows before the call,
+        and the call's own zeroed counters and status word (the agent's status is sticky)."""
+        if not isinstance(other, BatchedQLearningAgent) or other is self:
+            raise ValueError(f"{what}_from takes another BatchedQLearningAgent")
+        if other.device != self.device:
+            raise ValueError("the two agents live on different devices")
+        kind_checks()
+        if mode not in self._MERGE_MODES:
+            raise ValueError(f"mode must be one of {sorted(self._MERGE_MODES)}")
+        weight = float(weight)
+        if not np.isfinite(weight) or (mode == "blend" and not 0.0 <= weight <= 1.0):
+            raise ValueError("weight must be finite, and in [0, 1] for mode 'blend'")
+        if self.frozen:
+            raise ValueError(f"this agent's key set is closed (frozen): {'an' if what[0] in 'aeiou' else 'a'} {what} "
+                             "would create rows its visit rows and line summaries do not know")
+        self.finish_growth()
+        other.finish_growth()
+        rows = self._rows_exact()
+        total = rows + rows_per_row * other._rows_exact()
+        while self.growable and total * 2 > (1 << self.capacity_log2) and self.capacity_log2 < self.max_capacity_log2:
+            self.grow_table(min(self.max_capacity_log2, max(self.capacity_log2 + 1, int(np.ceil(np.log2(2.0 * total))))),
+                            _rows=rows)
+        if total > 0.9 * (1 << self.capacity_log2):
+            raise ValueError(f"table too small for the {what} (load factor could exceed 0.9)")
+        self.invalidate_row_cache()
+        self._summarised, self._side = False, None        # (rows arrive: line summaries stop describing the table)
+        return (rows, weight, torch.zeros(n_counters, dtype=torch.int64, device=self.device),
+                torch.zeros(1, dtype=torch.int32, device=self.device))
+
+    def _combine_end(self, what: str, unit: str, rows: int, counters, status, verify=None) -> list:
+        """The common back: reads the call's counters ([..., created, combined, dropped]) and status, rebases the row
+        bookkeeping (rows before + rows created), raises on TABLE_FULL, lets `verify(counts)` raise, warns on DEEP_ROW.
+        Returns the counters as ints."""
+        counts = [int(v) for v in counters.tolist()]
+        created, dropped = counts[-3], counts[-1]
+        code = int(status.item())
+        self._rebase_rows(rows + created)
+        if code & N.STATUS_TABLE_FULL:
+            raise RuntimeError(f"table_{what} dropped {dropped} {unit} (probe limit)")
+        if verify is not None:
+            verify(counts)
+        if code & N.STATUS_DEEP_ROW:
+            warnings.warn(f"table_{what} placed rows deeper than the learning paths probe (2^10 slots): q_values finds "
+                          f"them, choose / update / rollouts read them as absent -- {what} into a larger table")
+        return counts
+
     def merge_from(self, other: "BatchedQLearningAgent", mode: str = "add", weight: float = 1.0) -> dict:
         """Combines `other`'s table into this one on the device (q2048_table_merge): every row of `other` finds or
         creates its row here -- the replicas of a job, or two checkpoints, become one table without a trip through
@@ -1226,46 +1276,18 @@ class BatchedQLearningAgent:
         key set is closed (`frozen`) is refused: its visit rows and line summaries describe a key set the merge would
         change.  The row bookkeeping stays exact without a counting pass (rows before + rows created).
         Returns the call's counters: {"read", "created", "combined", "dropped"}; read == other's rows."""
-        if not isinstance(other, BatchedQLearningAgent) or other is self:
-            raise ValueError("merge_from takes another BatchedQLearningAgent")
-        if other.device != self.device:
-            raise ValueError("the two agents live on different devices")
-        if other.board_size != self.board_size:
-            raise ValueError("the two agents have different board sizes")
-        if other.symmetric != self.symmetric:
-            raise ValueError("a symmetry-folded table (symmetric=True) and a plain one cannot be merged")
-        if mode not in self._MERGE_MODES:
-            raise ValueError(f"mode must be one of {sorted(self._MERGE_MODES)}")
-        weight = float(weight)
-        if not np.isfinite(weight) or (mode == "blend" and not 0.0 <= weight <= 1.0):
-            raise ValueError("weight must be finite, and in [0, 1] for mode 'blend'")
-        if self.frozen:
-            raise ValueError("this agent's key set is closed (frozen): a merge would create rows its visit rows and "
-                             "line summaries do not know")
-        self.finish_growth()
-        other.finish_growth()
-        rows, rows_other = self._rows_exact(), other._rows_exact()
-        total = rows + rows_other                         # (an upper bound of the rows afterwards: keys may be shared)
-        while self.growable and total * 2 > (1 << self.capacity_log2) and self.capacity_log2 < self.max_capacity_log2:
-            self.grow_table(min(self.max_capacity_log2, max(self.capacity_log2 + 1, int(np.ceil(np.log2(2.0 * total))))),
-                            _rows=rows)
-        if total > 0.9 * (1 << self.capacity_log2):
-            raise ValueError("table too small for the merge (load factor could exceed 0.9)")
-        self.invalidate_row_cache()
-        self._summarised, self._side = False, None        # (rows arrive: line summaries stop describing the table)
-        counters = torch.zeros(4, dtype=torch.int64, device=self.device)
-        status = torch.zeros(1, dtype=torch.int32, device=self.device)    # this call's own word (the agent's is sticky)
+        def kind_checks():
+            if other.board_size != self.board_size:
+                raise ValueError("the two agents have different board sizes")
+            if other.symmetric != self.symmetric:
+                raise ValueError("a symmetry-folded table (symmetric=True) and a plain one cannot be merged")
+
+        # (rows + other's rows bounds the rows afterwards: keys may be shared)
+        rows, weight, counters, status = self._combine_begin(other, "merge", kind_checks, mode, weight, 1, 4)
         N.check(self._L.q2048_table_merge(_ptr(self.table), self.capacity_log2, _ptr(other.table), other.capacity_log2,
                                           1 if self.board_size == 4 else 2, self._MERGE_MODES[mode], weight,
                                           _ptr(counters), _ptr(status), _stream(self.device)), "table_merge")
-        read, created, combined, dropped = (int(v) for v in counters.tolist())
-        code = int(status.item())
-        self._rebase_rows(rows + created)
-        if code & N.STATUS_TABLE_FULL:
-            raise RuntimeError(f"table_merge dropped {dropped} rows (probe limit)")
-        if code & N.STATUS_DEEP_ROW:
-            warnings.warn("table_merge placed rows deeper than the learning paths probe (2^10 slots): q_values finds "
-                          "them, choose / update / rollouts read them as absent -- merge into a larger table")
+        read, created, combined, dropped = self._combine_end("merge", "rows", rows, counters, status)
         return {"read": read, "created": created, "combined": combined, "dropped": dropped}
 
     _FOLD_KINDS = {"mean": N.FOLD_MEAN, "mean_trained": N.FOLD_MEAN_TRAINED, "sum": N.FOLD_SUM, "maxabs": N.FOLD_MAXABS}
@@ -1287,54 +1309,26 @@ class BatchedQLearningAgent:
         be told from boards and are refused.
         Returns the call's counters: {"read", "orbits", "created", "combined", "dropped"}; read == other's rows,
         orbits == created + combined + dropped."""
-        if not isinstance(other, BatchedQLearningAgent) or other is self:
-            raise ValueError("fold_from takes another BatchedQLearningAgent")
-        if other.device != self.device:
-            raise ValueError("the two agents live on different devices")
-        if self.board_size != 4 or other.board_size != 4:
-            raise ValueError("symmetry folding is built for board size 4 only")
-        if not self.symmetric:
-            raise ValueError("fold_from needs a symmetry-folded destination (symmetric=True); merge_from combines two "
-                             "tables of one kind")
-        if other.symmetric:
-            raise ValueError("the source is already symmetry-folded: merge_from combines two folded tables")
-        if (self.flags | other.flags) & N.FLAG_INDEPENDENT:
-            raise ValueError("keys salted per env (independent=True, Q2048_FLAG_INDEPENDENT) do not decode to boards "
-                             "and cannot be folded")
-        if fold not in self._FOLD_KINDS:
-            raise ValueError(f"fold must be one of {sorted(self._FOLD_KINDS)}")
-        if mode not in self._MERGE_MODES:
-            raise ValueError(f"mode must be one of {sorted(self._MERGE_MODES)}")
-        weight = float(weight)
-        if not np.isfinite(weight) or (mode == "blend" and not 0.0 <= weight <= 1.0):
-            raise ValueError("weight must be finite, and in [0, 1] for mode 'blend'")
-        if self.frozen:
-            raise ValueError("this agent's key set is closed (frozen): a fold would create rows its visit rows and "
-                             "line summaries do not know")
-        self.finish_growth()
-        other.finish_growth()
-        rows, rows_other = self._rows_exact(), other._rows_exact()
-        total = rows + rows_other                         # (an upper bound: an orbit has at least one row in `other`)
-        while self.growable and total * 2 > (1 << self.capacity_log2) and self.capacity_log2 < self.max_capacity_log2:
-            self.grow_table(min(self.max_capacity_log2, max(self.capacity_log2 + 1, int(np.ceil(np.log2(2.0 * total))))),
-                            _rows=rows)
-        if total > 0.9 * (1 << self.capacity_log2):
-            raise ValueError("table too small for the fold (load factor could exceed 0.9)")
-        self.invalidate_row_cache()
-        self._summarised, self._side = False, None        # (rows arrive: line summaries stop describing the table)
-        counters = torch.zeros(5, dtype=torch.int64, device=self.device)
-        status = torch.zeros(1, dtype=torch.int32, device=self.device)    # this call's own word (the agent's is sticky)
+        def kind_checks():
+            if self.board_size != 4 or other.board_size != 4:
+                raise ValueError("symmetry folding is built for board size 4 only")
+            if not self.symmetric:
+                raise ValueError("fold_from needs a symmetry-folded destination (symmetric=True); merge_from combines "
+                                 "two tables of one kind")
+            if other.symmetric:
+                raise ValueError("the source is already symmetry-folded: merge_from combines two folded tables")
+            if (self.flags | other.flags) & N.FLAG_INDEPENDENT:
+                raise ValueError("keys salted per env (independent=True, Q2048_FLAG_INDEPENDENT) do not decode to "
+                                 "boards and cannot be folded")
+            if fold not in self._FOLD_KINDS:
+                raise ValueError(f"fold must be one of {sorted(self._FOLD_KINDS)}")
+
+        # (rows + other's rows is an upper bound: an orbit has at least one row in `other`)
+        rows, weight, counters, status = self._combine_begin(other, "fold", kind_checks, mode, weight, 1, 5)
         N.check(self._L.q2048_table_fold(_ptr(self.table), self.capacity_log2, _ptr(other.table), other.capacity_log2, 1,
                                          self._FOLD_KINDS[fold], self._MERGE_MODES[mode], weight, _ptr(counters),
                                          _ptr(status), _stream(self.device)), "table_fold")
-        read, orbits, created, combined, dropped = (int(v) for v in counters.tolist())
-        code = int(status.item())
-        self._rebase_rows(rows + created)
-        if code & N.STATUS_TABLE_FULL:
-            raise RuntimeError(f"table_fold dropped {dropped} orbits (probe limit)")
-        if code & N.STATUS_DEEP_ROW:
-            warnings.warn("table_fold placed rows deeper than the learning paths probe (2^10 slots): q_values finds "
-                          "them, choose / update / rollouts read them as absent -- fold into a larger table")
+        read, orbits, created, combined, dropped = self._combine_end("fold", "orbits", rows, counters, status)
         return {"read": read, "orbits": orbits, "created": created, "combined": combined, "dropped": dropped}
 
     def unfold_from(self, other: "BatchedQLearningAgent", mode: str = "add", weight: float = 1.0) -> dict:
@@ -1351,55 +1345,30 @@ class BatchedQLearningAgent:
         Returns the call's counters: {"read", "skipped", "written", "created", "combined", "dropped"}; read == other's
         rows, written == created + combined + dropped.  skipped counts rows whose key is not canonical: a folded
         table never holds one, so anything but 0 raises RuntimeError (the table is corrupted)."""
-        if not isinstance(other, BatchedQLearningAgent) or other is self:
-            raise ValueError("unfold_from takes another BatchedQLearningAgent")
-        if other.device != self.device:
-            raise ValueError("the two agents live on different devices")
-        if self.board_size != 4 or other.board_size != 4:
-            raise ValueError("symmetry folding is built for board size 4 only")
-        if self.symmetric:
-            raise ValueError("unfold_from needs a plain destination (symmetric=False); merge_from combines two folded "
-                             "tables")
-        if not other.symmetric:
-            raise ValueError("the source is a plain table: merge_from combines two tables of one kind")
-        if (self.flags | other.flags) & N.FLAG_INDEPENDENT:
-            raise ValueError("keys salted per env (independent=True, Q2048_FLAG_INDEPENDENT) do not decode to boards "
-                             "and cannot be unfolded")
-        if mode not in self._MERGE_MODES:
-            raise ValueError(f"mode must be one of {sorted(self._MERGE_MODES)}")
-        weight = float(weight)
-        if not np.isfinite(weight) or (mode == "blend" and not 0.0 <= weight <= 1.0):
-            raise ValueError("weight must be finite, and in [0, 1] for mode 'blend'")
-        if self.frozen:
-            raise ValueError("this agent's key set is closed (frozen): an unfold would create rows its visit rows and "
-                             "line summaries do not know")
-        self.finish_growth()
-        other.finish_growth()
-        rows, rows_other = self._rows_exact(), other._rows_exact()
-        total = rows + 8 * rows_other                     # (an upper bound: a row has at most eight images)
-        while self.growable and total * 2 > (1 << self.capacity_log2) and self.capacity_log2 < self.max_capacity_log2:
-            self.grow_table(min(self.max_capacity_log2, max(self.capacity_log2 + 1, int(np.ceil(np.log2(2.0 * total))))),
-                            _rows=rows)
-        if total > 0.9 * (1 << self.capacity_log2):
-            raise ValueError("table too small for the unfold (load factor could exceed 0.9)")
-        self.invalidate_row_cache()
-        self._summarised, self._side = False, None        # (rows arrive: line summaries stop describing the table)
-        counters = torch.zeros(6, dtype=torch.int64, device=self.device)
-        status = torch.zeros(1, dtype=torch.int32, device=self.device)    # this call's own word (the agent's is sticky)
+        def kind_checks():
+            if self.board_size != 4 or other.board_size != 4:
+                raise ValueError("symmetry folding is built for board size 4 only")
+            if self.symmetric:
+                raise ValueError("unfold_from needs a plain destination (symmetric=False); merge_from combines two "
+                                 "folded tables")
+            if not other.symmetric:
+                raise ValueError("the source is a plain table: merge_from combines two tables of one kind")
+            if (self.flags | other.flags) & N.FLAG_INDEPENDENT:
+                raise ValueError("keys salted per env (independent=True, Q2048_FLAG_INDEPENDENT) do not decode to "
+                                 "boards and cannot be unfolded")
+
+        def not_corrupted(counts):
+            if counts[1]:
+                raise RuntimeError(f"table_unfold skipped {counts[1]} rows of the folded table whose key is not "
+                                   "canonical: the source table is corrupted")
+
+        # (rows + 8 * other's rows is an upper bound: a row has at most eight images)
+        rows, weight, counters, status = self._combine_begin(other, "unfold", kind_checks, mode, weight, 8, 6)
         N.check(self._L.q2048_table_unfold(_ptr(self.table), self.capacity_log2, _ptr(other.table), other.capacity_log2, 1,
                                            self._MERGE_MODES[mode], weight, _ptr(counters), _ptr(status),
                                            _stream(self.device)), "table_unfold")
-        read, skipped, written, created, combined, dropped = (int(v) for v in counters.tolist())
-        code = int(status.item())
-        self._rebase_rows(rows + created)
-        if code & N.STATUS_TABLE_FULL:
-            raise RuntimeError(f"table_unfold dropped {dropped} rows (probe limit)")
-        if skipped:
-            raise RuntimeError(f"table_unfold skipped {skipped} rows of the folded table whose key is not canonical: "
-                               "the source table is corrupted")
-        if code & N.STATUS_DEEP_ROW:
-            warnings.warn("table_unfold placed rows deeper than the learning paths probe (2^10 slots): q_values finds "
-                          "them, choose / update / rollouts read them as absent -- unfold into a larger table")
+        read, skipped, written, created, combined, dropped = self._combine_end("unfold", "rows", rows, counters, status,
+                                                                               verify=not_corrupted)
         return {"read": read, "skipped": skipped, "written": written, "created": created, "combined": combined,
                 "dropped": dropped}
 

@@ -278,6 +278,13 @@ Q_HD uint64_t key_hash(const Geo<4>::Key& k) { return mix64(k.k0); }
 Q_HD uint64_t key_hash(const Geo<5>::Key& k) { return mix64(k.k0 ^ (k.k1 * 0x9E3779B97F4A7C15ull)); }
 template <class Key>
 Q_HD uint64_t key_home(const Key& k, uint64_t mask) { return key_hash(k) & mask; }
+// DEEP_ROW: `slot`, on the key's probe sequence, lies beyond the learning paths' probe limit (only at loads above
+// ~0.93).  q_lookup / export find such a row, choose / update / the rollouts read it as absent: the bulk operations
+// that may place one (import, merge, fold, unfold) tell their caller.
+template <class Key>
+Q_HD bool deep_row(const Key& k, uint64_t mask, uint64_t slot) {
+  return seq_pos(seq_of(key_hash(k), mask), slot) >= probe_limit(mask, kRolloutProbe);
+}
 
 // The key of a board.  Independent mode salts it with the env id (private rows per env).  `overflow()` is called
 // when a tile above 2^15 does not fit its nibble (4x4 only): each library raises Q2048_STATUS_TILE_OVERFLOW its own

@@ -834,6 +834,64 @@ inline void rt_scatter(float* w, const Board& b, const RtRows& e, int act, float
   const uint32_t idx[4] = {pack_row(b.r0), pack_row(b.r1), pack_row(b.r2), pack_row(b.r3)};
   for (int r = 0; r < 4; ++r) st_f32(rt_entry(w, r, idx[r]) + act, row_get(e.e[r], act) + d);
 }
+
+// ---- bulk moves of rows into a table (import, merge, fold, unfold) ----------------------------------------------
+// the one- or two-word key of a table, as the type the probes are compiled for: f(Geo<4>::Key) or f(Geo<5>::Key)
+template <class F>
+inline void with_key(int key_words, u64 k0, u64 k1, F&& f) {
+  if (key_words == 1) f(Geo<4>::Key{k0});
+  else f(Geo<5>::Key{k0, k1});
+}
+
+// The device's find-or-create-and-combine (combine_into, q2048_kernels.hip), value for value, for merge, fold and
+// unfold: float32, the product rounded before the sum sees it (the volatile keeps a compiler that contracts by default
+// from fusing the two).  Slots of `src` are split over the threads, every thread counts into its own Part, and the
+// callers see to it that one thread alone brings a given key: one writer per dst row.
+inline float mul_rn(float a, float b) { volatile float p = a * b; return p; }
+inline float merge_value(int mode, float d, float s, float w, float one_minus_w) {
+  if (mode == Q2048_MERGE_ADD) return d + mul_rn(w, s);
+  if (mode == Q2048_MERGE_BLEND) { const float keep = mul_rn(one_minus_w, d); return keep + mul_rn(w, s); }
+  return std::fabs(s) > std::fabs(d) ? s : d;
+}
+struct Part { uint64_t lead[2] = {0, 0}, created = 0, combined = 0, dropped = 0; uint32_t bits = 0; };   // lead: read, skipped
+template <class Key>
+inline void combine_into(q2048_slot* dst, u64 mask, const Key& key, const float q[4], int mode, float w, float one_minus_w,
+                         Part& p) {
+  bool inserted;
+  const int64_t slot = probe_insert(dst, mask, key, key_home(key, mask), inserted, kMaxProbe);
+  if (slot < 0) { ++p.dropped; p.bits |= Q2048_STATUS_TABLE_FULL; return; }
+  if (inserted) {
+    ++p.created;
+    if (deep_row(key, mask, (u64)slot)) p.bits |= Q2048_STATUS_DEEP_ROW;
+    for (int a = 0; a < 4; ++a) st_f32(&dst[slot].q[a], mode == Q2048_MERGE_ADD ? mul_rn(w, q[a]) : q[a]);
+  } else {
+    ++p.combined;
+    for (int a = 0; a < 4; ++a) st_f32(&dst[slot].q[a], merge_value(mode, ld_f32(&dst[slot].q[a]), q[a], w, one_minus_w));
+  }
+}
+// walk(lo, hi, part) over the slots [0, cap) of the source, split over the threads; then
+// counters += {the first `lead` of part.lead, rows written (created + combined + dropped), created, combined, dropped}
+template <class Walk>
+inline void combine_ranges(int64_t cap, int lead, uint64_t* counters, uint32_t* status, Walk walk) {
+  std::vector<Part> parts((size_t)threads_for(cap));
+  Part* part = parts.data();
+  const int used = parallel_ranges(cap, [=](int64_t lo, int64_t hi, int t) {
+    Part p;
+    walk(lo, hi, p);
+    part[t] = p;
+  });
+  uint32_t bits = 0u;
+  for (int t = 0; t < used; ++t) {
+    const Part& p = parts[(size_t)t];
+    for (int l = 0; l < lead; ++l) counters[l] += p.lead[l];
+    counters[lead] += p.created + p.combined + p.dropped;
+    counters[lead + 1] += p.created;
+    counters[lead + 2] += p.combined;
+    counters[lead + 3] += p.dropped;
+    bits |= p.bits;
+  }
+  if (bits && status != nullptr) status_or(status, bits);
+}
 }  // namespace
 
 extern "C" {
@@ -1167,91 +1225,36 @@ int q2048_table_import(q2048_slot* table, int cap_log2, const uint64_t* keys, co
   if (!aligned16(q)) return Q2048_ERR_ALIGN;
   const u64 mask = (1ull << cap_log2) - 1ull;
   parallel_ranges(rows, [=](int64_t lo, int64_t hi, int) {
-    for (int64_t i = lo; i < hi; ++i) {
-      bool inserted;
-      int64_t slot;
-      u64 hash;
-      if (key_words == 1) {
-        const Geo<4>::Key key{(u64)keys[i]};
-        hash = key_hash(key);
-        slot = probe_insert(table, mask, key, hash & mask, inserted, kMaxProbe);
-      } else {
-        const Geo<5>::Key key{(u64)keys[2 * i], (u64)keys[2 * i + 1]};
-        hash = key_hash(key);
-        slot = probe_insert(table, mask, key, hash & mask, inserted, kMaxProbe);
-      }
-      if (slot < 0) { status_or(status, Q2048_STATUS_TABLE_FULL); continue; }
-      // beyond the learning paths' probe limit: lookup / export find the row, choose / update / rollouts do not
-      if (seq_pos(seq_of(hash, mask), (u64)slot) >= probe_limit(mask, kRolloutProbe)) status_or(status, Q2048_STATUS_DEEP_ROW);
-      for (int a = 0; a < 4; ++a) st_f32(&table[slot].q[a], q[4 * i + a]);
-    }
+    for (int64_t i = lo; i < hi; ++i)
+      with_key(key_words, keys[key_words * i], key_words == 2 ? keys[2 * i + 1] : 0ull, [&](const auto& key) {
+        bool inserted;
+        const int64_t slot = probe_insert(table, mask, key, key_home(key, mask), inserted, kMaxProbe);
+        if (slot < 0) { status_or(status, Q2048_STATUS_TABLE_FULL); return; }
+        if (deep_row(key, mask, (u64)slot)) status_or(status, Q2048_STATUS_DEEP_ROW);
+        for (int a = 0; a < 4; ++a) st_f32(&table[slot].q[a], q[4 * i + a]);
+      });
   });
   return Q2048_OK;
 }
 
-// the device's merge (k_table_merge), value for value: float32, the product rounded before the sum sees it (the
-// volatile keeps a compiler that contracts by default from fusing the two), slots of `src` split over the threads
-namespace {
-inline float mul_rn(float a, float b) { volatile float p = a * b; return p; }
-inline float merge_value(int mode, float d, float s, float w, float one_minus_w) {
-  if (mode == Q2048_MERGE_ADD) return d + mul_rn(w, s);
-  if (mode == Q2048_MERGE_BLEND) { const float keep = mul_rn(one_minus_w, d); return keep + mul_rn(w, s); }
-  return std::fabs(s) > std::fabs(d) ? s : d;
-}
-}  // namespace
+// the device's merge (k_table_merge): every occupied row of `src` (rows read == rows written: no leading counter)
 int q2048_table_merge(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, int src_cap_log2, int key_words,
                       int mode, float w, uint64_t* counters, uint32_t* status, void*) {
   if (int e = check_merge(dst, dst_cap_log2, src, src_cap_log2, counters, key_words == 1 || key_words == 2, true, mode, w)) return e;
-  const int64_t cap = (int64_t)1 << src_cap_log2;
   const u64 mask = (1ull << dst_cap_log2) - 1ull;
   const float one_minus_w = 1.0f - w;
-  struct Part { uint64_t created = 0, combined = 0, dropped = 0; uint32_t bits = 0; };
-  std::vector<Part> parts((size_t)threads_for(cap));
-  Part* part = parts.data();
-  const int used = parallel_ranges(cap, [=](int64_t lo, int64_t hi, int t) {
-    Part p;
+  combine_ranges((int64_t)1 << src_cap_log2, 0, counters, status, [=](int64_t lo, int64_t hi, Part& p) {
     for (int64_t i = lo; i < hi; ++i) {
       const q2048_slot& s = src[i];
       if (s.key == 0ull) continue;
-      bool inserted;
-      int64_t slot;
-      u64 hash;
-      if (key_words == 1) {
-        const Geo<4>::Key key{(u64)s.key};
-        hash = key_hash(key);
-        slot = probe_insert(dst, mask, key, hash & mask, inserted, kMaxProbe);
-      } else {
-        const Geo<5>::Key key{(u64)s.key, (u64)s.reserved};
-        hash = key_hash(key);
-        slot = probe_insert(dst, mask, key, hash & mask, inserted, kMaxProbe);
-      }
-      if (slot < 0) { ++p.dropped; p.bits |= Q2048_STATUS_TABLE_FULL; continue; }
-      if (inserted) {
-        ++p.created;
-        if (seq_pos(seq_of(hash, mask), (u64)slot) >= probe_limit(mask, kRolloutProbe)) p.bits |= Q2048_STATUS_DEEP_ROW;
-        for (int a = 0; a < 4; ++a) st_f32(&dst[slot].q[a], mode == Q2048_MERGE_ADD ? mul_rn(w, s.q[a]) : s.q[a]);
-      } else {
-        ++p.combined;
-        for (int a = 0; a < 4; ++a) st_f32(&dst[slot].q[a], merge_value(mode, ld_f32(&dst[slot].q[a]), s.q[a], w, one_minus_w));
-      }
+      with_key(key_words, s.key, s.reserved, [&](const auto& key) { combine_into(dst, mask, key, s.q, mode, w, one_minus_w, p); });
     }
-    part[t] = p;
   });
-  uint32_t bits = 0u;
-  for (int t = 0; t < used; ++t) {
-    const Part& p = parts[(size_t)t];
-    counters[0] += p.created + p.combined + p.dropped;
-    counters[1] += p.created;
-    counters[2] += p.combined;
-    counters[3] += p.dropped;
-    bits |= p.bits;
-  }
-  if (bits && status != nullptr) status_or(status, bits);
   return Q2048_OK;
 }
 
-// the device's fold (k_table_fold), value for value: the same walk of the orbit (fold_orbit, q2048_core.hpp), the
-// leader's one find-or-create in `dst`, the merge's arithmetic; slots of `src` split over the threads
+// the device's fold (k_table_fold): the same walk of the orbit (fold_orbit, q2048_core.hpp), the leader's one
+// combine_into; leads with rows read
 namespace {
 static_assert(Q2048_FOLD_MEAN == kFoldMean && Q2048_FOLD_MEAN_TRAINED == kFoldMeanTrained && Q2048_FOLD_SUM == kFoldSum &&
               Q2048_FOLD_MAXABS == kFoldMaxAbs, "q2048.h / q2048_core.hpp");
@@ -1262,14 +1265,9 @@ int q2048_table_fold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, i
   if (key_words == 2) return Q2048_ERR_UNSUPPORTED;
   const bool fold_ok = fold == Q2048_FOLD_MEAN || fold == Q2048_FOLD_MEAN_TRAINED || fold == Q2048_FOLD_SUM || fold == Q2048_FOLD_MAXABS;
   if (int e = check_merge(dst, dst_cap_log2, src, src_cap_log2, counters, key_words == 1, fold_ok, mode, w)) return e;
-  const int64_t cap = (int64_t)1 << src_cap_log2;
   const u64 mask = (1ull << dst_cap_log2) - 1ull, src_mask = (1ull << src_cap_log2) - 1ull;
   const float one_minus_w = 1.0f - w;
-  struct Part { uint64_t read = 0, created = 0, combined = 0, dropped = 0; uint32_t bits = 0; };
-  std::vector<Part> parts((size_t)threads_for(cap));
-  Part* part = parts.data();
-  const int used = parallel_ranges(cap, [=](int64_t lo, int64_t hi, int t) {
-    Part p;
+  combine_ranges((int64_t)1 << src_cap_log2, 1, counters, status, [=](int64_t lo, int64_t hi, Part& p) {
     const auto find = [src, src_mask](uint64_t k, float out[4]) {
       Row row;
       const bool present = probe_find(src, src_mask, Geo<4>::Key{(u64)k}, row, kMaxProbe) >= 0;
@@ -1279,7 +1277,7 @@ int q2048_table_fold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, i
     for (int64_t i = lo; i < hi; ++i) {
       const q2048_slot& s = src[i];
       if (s.key == 0ull) continue;
-      ++p.read;
+      ++p.lead[0];
       uint64_t canon;
       float r[4];
       const bool leads = fold == Q2048_FOLD_MEAN           ? fold_orbit<kFoldMean>(s.key, s.q, find, canon, r)
@@ -1287,88 +1285,34 @@ int q2048_table_fold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, i
                          : fold == Q2048_FOLD_SUM          ? fold_orbit<kFoldSum>(s.key, s.q, find, canon, r)
                                                            : fold_orbit<kFoldMaxAbs>(s.key, s.q, find, canon, r);
       if (!leads) continue;                                  // another row leads this orbit
-      const Geo<4>::Key key{(u64)canon};
-      const u64 hash = key_hash(key);
-      bool inserted;
-      const int64_t slot = probe_insert(dst, mask, key, hash & mask, inserted, kMaxProbe);
-      if (slot < 0) { ++p.dropped; p.bits |= Q2048_STATUS_TABLE_FULL; continue; }
-      if (inserted) {
-        ++p.created;
-        if (seq_pos(seq_of(hash, mask), (u64)slot) >= probe_limit(mask, kRolloutProbe)) p.bits |= Q2048_STATUS_DEEP_ROW;
-        for (int a = 0; a < 4; ++a) st_f32(&dst[slot].q[a], mode == Q2048_MERGE_ADD ? mul_rn(w, r[a]) : r[a]);
-      } else {
-        ++p.combined;
-        for (int a = 0; a < 4; ++a) st_f32(&dst[slot].q[a], merge_value(mode, ld_f32(&dst[slot].q[a]), r[a], w, one_minus_w));
-      }
+      combine_into(dst, mask, Geo<4>::Key{(u64)canon}, r, mode, w, one_minus_w, p);
     }
-    part[t] = p;
   });
-  uint32_t bits = 0u;
-  for (int t = 0; t < used; ++t) {
-    const Part& p = parts[(size_t)t];
-    counters[0] += p.read;
-    counters[1] += p.created + p.combined + p.dropped;
-    counters[2] += p.created;
-    counters[3] += p.combined;
-    counters[4] += p.dropped;
-    bits |= p.bits;
-  }
-  if (bits && status != nullptr) status_or(status, bits);
   return Q2048_OK;
 }
 
-// the device's unfold (k_table_unfold), value for value: the same walk of the orbit (unfold_orbit, q2048_core.hpp),
-// one find-or-create in `dst` per member, the merge's arithmetic; slots of `src` split over the threads (a source
-// row's whole orbit is written by the thread that read the row, and orbits of distinct canonical keys are disjoint)
+// the device's unfold (k_table_unfold): the same walk of the orbit (unfold_orbit, q2048_core.hpp), one combine_into
+// per member (a source row's whole orbit is written by the thread that read the row, and orbits of distinct
+// canonical keys are disjoint); leads with rows read, rows skipped
 int q2048_table_unfold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, int src_cap_log2, int key_words, int mode,
                        float w, uint64_t* counters, uint32_t* status, void*) {
   if (!dst || !src || !counters) return Q2048_ERR_NULL;
   if (key_words == 2) return Q2048_ERR_UNSUPPORTED;
   if (int e = check_merge(dst, dst_cap_log2, src, src_cap_log2, counters, key_words == 1, true, mode, w)) return e;
-  const int64_t cap = (int64_t)1 << src_cap_log2;
   const u64 mask = (1ull << dst_cap_log2) - 1ull;
   const float one_minus_w = 1.0f - w;
-  struct Part { uint64_t read = 0, skipped = 0, created = 0, combined = 0, dropped = 0; uint32_t bits = 0; };
-  std::vector<Part> parts((size_t)threads_for(cap));
-  Part* part = parts.data();
-  const int used = parallel_ranges(cap, [=](int64_t lo, int64_t hi, int t) {
-    Part p;
+  combine_ranges((int64_t)1 << src_cap_log2, 2, counters, status, [=](int64_t lo, int64_t hi, Part& p) {
     const auto emit = [&p, dst, mask, mode, w, one_minus_w](uint64_t m, const Row& r) {
       const float q[4] = {r.q0, r.q1, r.q2, r.q3};
-      const Geo<4>::Key key{(u64)m};
-      const u64 hash = key_hash(key);
-      bool inserted;
-      const int64_t slot = probe_insert(dst, mask, key, hash & mask, inserted, kMaxProbe);
-      if (slot < 0) { ++p.dropped; p.bits |= Q2048_STATUS_TABLE_FULL; return; }
-      if (inserted) {
-        ++p.created;
-        if (seq_pos(seq_of(hash, mask), (u64)slot) >= probe_limit(mask, kRolloutProbe)) p.bits |= Q2048_STATUS_DEEP_ROW;
-        for (int a = 0; a < 4; ++a) st_f32(&dst[slot].q[a], mode == Q2048_MERGE_ADD ? mul_rn(w, q[a]) : q[a]);
-      } else {
-        ++p.combined;
-        for (int a = 0; a < 4; ++a) st_f32(&dst[slot].q[a], merge_value(mode, ld_f32(&dst[slot].q[a]), q[a], w, one_minus_w));
-      }
+      combine_into(dst, mask, Geo<4>::Key{(u64)m}, q, mode, w, one_minus_w, p);
     };
     for (int64_t i = lo; i < hi; ++i) {
       const q2048_slot& s = src[i];
       if (s.key == 0ull) continue;
-      ++p.read;
-      if (unfold_orbit(s.key, Row{s.q[0], s.q[1], s.q[2], s.q[3]}, emit) == 0u) ++p.skipped;
+      ++p.lead[0];
+      if (unfold_orbit(s.key, Row{s.q[0], s.q[1], s.q[2], s.q[3]}, emit) == 0u) ++p.lead[1];
     }
-    part[t] = p;
   });
-  uint32_t bits = 0u;
-  for (int t = 0; t < used; ++t) {
-    const Part& p = parts[(size_t)t];
-    counters[0] += p.read;
-    counters[1] += p.skipped;
-    counters[2] += p.created + p.combined + p.dropped;
-    counters[3] += p.created;
-    counters[4] += p.combined;
-    counters[5] += p.dropped;
-    bits |= p.bits;
-  }
-  if (bits && status != nullptr) status_or(status, bits);
   return Q2048_OK;
 }
 

@@ -29,6 +29,7 @@
 #include <map>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "q2048_abi.hpp"
@@ -2146,63 +2147,103 @@ __global__ __launch_bounds__(kBlock) void k_table_import(q2048_slot* table, u64 
   bool inserted;
   const int64_t slot = probe_insert(table, mask, key, key_home(key, mask), inserted, kMaxProbe);
   if (slot < 0) { atomicOr(status, Q2048_STATUS_TABLE_FULL); return; }
-  // placed beyond the learning paths' probe limit (only at loads above ~0.93): q_lookup / export find the row,
-  // choose / update / the rollouts read it as absent -- the caller is told
-  if (seq_pos(seq_of(key_hash(key), mask), (u64)slot) >= probe_limit(mask, kRolloutProbe)) atomicOr(status, Q2048_STATUS_DEEP_ROW);
+  if (deep_row(key, mask, (u64)slot)) atomicOr(status, Q2048_STATUS_DEEP_ROW);
   const float4 v = reinterpret_cast<const float4*>(q)[i];
   table[slot].q[0] = v.x; table[slot].q[1] = v.y; table[slot].q[2] = v.z; table[slot].q[3] = v.w;
 }
 
-// Growth (q2048_table_grow): every occupied row of `old_t` is inserted into `new_t` (zero-filled, larger)
-// in ONE streaming pass -- consecutive lanes read consecutive slots (32 B each, non-temporal), an
-// occupied one claims its slot in the new table with the find-or-create of the rollout (the first
-// access is the claiming compare-and-swap at the key's new home) and writes its four values.  Keys of
-// one table are distinct, so no two lanes ever insert the same key; counters[0] += rows moved,
-// counters[1] += rows that found no slot or found their key already there (expected: 0; the host
-// refuses the new table otherwise).
-template <int WORDS>
-__global__ __launch_bounds__(kBlock) void k_table_rehash(const q2048_slot* old_t, u64 old_cap, q2048_slot* new_t,
-                                                         u64 new_mask, u64* counters) {
-  const u32x4* t16 = reinterpret_cast<const u32x4*>(old_t);
-  u64 moved = 0ull, failed = 0ull;
-  for (u64 i = (u64)blockIdx.x * kBlock + threadIdx.x; i < old_cap; i += (u64)gridDim.x * kBlock) {
+// ---- what the bulk moves of rows (growth, merge, fold, unfold) share ----
+// The streaming read of a whole table: one grid-stride pass, consecutive lanes on consecutive slots, 32 B each in two
+// non-temporal 16-byte loads -- the second one only for an occupied slot, which is handed to row(k0, k1, q): the key
+// word, the slot's last word (the 5x5 key's second word, or a summary word nobody looks at) and the four values.
+template <class F>
+__device__ __forceinline__ void stream_rows(const q2048_slot* table, u64 cap, const F& row) {
+  const u32x4* t16 = reinterpret_cast<const u32x4*>(table);
+  for (u64 i = (u64)blockIdx.x * kBlock + threadIdx.x; i < cap; i += (u64)gridDim.x * kBlock) {
     const u32x4 a = __builtin_nontemporal_load(&t16[2ull * i]);          // {key, q0, q1}
     const u64 k = (u64)a.x | ((u64)a.y << 32);
     if (k == 0ull) continue;
-    const u32x4 w = __builtin_nontemporal_load(&t16[2ull * i + 1ull]);   // {q2, q3, second key word}
-    typename Geo<WORDS == 1 ? 4 : 5>::Key key;
-    key.k0 = k;
-    if constexpr (WORDS == 2) key.k1 = (u64)w.z | ((u64)w.w << 32);
-    bool inserted;
-    const int64_t slot = probe_insert(new_t, new_mask, key, key_home(key, new_mask), inserted, kMaxProbe);
-    if (slot < 0 || !inserted) { ++failed; continue; }
-    uint2* q = reinterpret_cast<uint2*>(new_t[slot].q);                  // 8-byte aligned (offset 8 of a 32-B slot)
-    q[0] = make_uint2(a.z, a.w);
-    q[1] = make_uint2(w.x, w.y);
-    ++moved;
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) { moved += __shfl_xor(moved, d); failed += __shfl_xor(failed, d); }
-  __shared__ u64 wm[kBlock / 64], wf[kBlock / 64];
-  if ((threadIdx.x & 63u) == 0u) { wm[threadIdx.x >> 6] = moved; wf[threadIdx.x >> 6] = failed; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    u64 m = 0ull, f = 0ull;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) { m += wm[w]; f += wf[w]; }
-    if (m) atomicAdd(&counters[0], m);
-    if (f) atomicAdd(&counters[1], f);
+    const u32x4 b = __builtin_nontemporal_load(&t16[2ull * i + 1ull]);   // {q2, q3, second key word}
+    row(k, (u64)b.z | ((u64)b.w << 32), Row{bits_f32(a.z), bits_f32(a.w), bits_f32(b.x), bits_f32(b.y)});
   }
 }
+template <int WORDS>
+__device__ __forceinline__ typename Geo<WORDS == 1 ? 4 : 5>::Key table_key(u64 k0, u64 k1) {
+  typename Geo<WORDS == 1 ? 4 : 5>::Key key;
+  key.k0 = k0;
+  if constexpr (WORDS == 2) key.k1 = k1;
+  return key;
+}
+__device__ __forceinline__ void store_row(q2048_slot* slot, float r0, float r1, float r2, float r3) {
+  uint2* q = reinterpret_cast<uint2*>(slot->q);                          // 8-byte aligned (offset 8 of a 32-B slot)
+  q[0] = make_uint2(f32_bits(r0), f32_bits(r1));
+  q[1] = make_uint2(f32_bits(r2), f32_bits(r3));
+}
 
-// Merge (q2048_table_merge): the growth's move with a destination that may already hold the key.  Every occupied row
-// of `src` finds or creates its row in `dst` -- the same streaming read, the same claiming compare-and-swap at the
-// key's home -- and a created row takes the source's values (ADD: w * q_src, the defaultdict's zero row + w * q_src),
-// a row that was there is read (two 8-byte loads), combined and written back (two 8-byte stores).  Keys of one table
-// are distinct, so no two lanes ever meet on a dst row: the only races are the slot claims `probe_insert` / `confirm`
-// resolve.  float32, product and sum rounded separately (no contraction: Q2048_NO_CONTRACT, checked in the ISA -- v_pk_mul_f32 + v_pk_add_f32, no fma): a numpy model
-// in float32 gives the same bits.  counters[0..3] += rows read / created / combined / dropped, ONE atomic per counter
-// and block (k_table_export above says why); the status bits likewise.
+// counters[i] += the block's total of n[i], *status |= the block's bits: per-lane values reduced over the wave by
+// shuffles and over the block through LDS, then ONE atomic per non-zero counter and block (k_table_export above says
+// why).  Every thread of the block calls it.
+template <int N>
+__device__ __forceinline__ void block_add(u64 (&n)[N], uint32_t bits, u64* counters, uint32_t* status) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) n[c] += __shfl_xor(n[c], d);
+    bits |= __shfl_xor(bits, d);
+  }
+  __shared__ u64 wn[N][kBlock / 64];
+  __shared__ uint32_t wb[kBlock / 64];
+  if ((threadIdx.x & 63u) == 0u) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) wn[c][threadIdx.x >> 6] = n[c];
+    wb[threadIdx.x >> 6] = bits;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  uint32_t sb = 0u;
+#pragma unroll
+  for (int v = 0; v < kBlock / 64; ++v) sb |= wb[v];
+#pragma unroll
+  for (int c = 0; c < N; ++c) {
+    u64 sum = 0ull;
+#pragma unroll
+    for (int v = 0; v < kBlock / 64; ++v) sum += wn[c][v];
+    if (sum) atomicAdd(&counters[c], sum);
+  }
+  if (sb && status != nullptr) atomicOr(status, sb);
+}
+
+// Growth (q2048_table_grow): every occupied row of `old_t` is inserted into `new_t` (zero-filled, larger)
+// in ONE streaming pass -- an occupied slot claims its slot in the new table with the find-or-create of the rollout
+// (the first access is the claiming compare-and-swap at the key's new home) and writes its four values.  Keys of
+// one table are distinct, so no two lanes ever insert the same key; counters[0] += rows moved,
+// counters[1] += rows that found no slot or found their key already there (expected: 0; the host
+// refuses the new table otherwise).  Not a combine_into: a key that is there is a failure, and `new_t` is never read.
+template <int WORDS>
+__global__ __launch_bounds__(kBlock) void k_table_rehash(const q2048_slot* old_t, u64 old_cap, q2048_slot* new_t,
+                                                         u64 new_mask, u64* counters) {
+  u64 rows = 0ull, failed = 0ull;
+  stream_rows(old_t, old_cap, [new_t, new_mask, &rows, &failed](u64 k0, u64 k1, const Row& q) {
+    ++rows;
+    const auto key = table_key<WORDS>(k0, k1);
+    bool inserted;
+    const int64_t slot = probe_insert(new_t, new_mask, key, key_home(key, new_mask), inserted, kMaxProbe);
+    if (slot < 0 || !inserted) { ++failed; return; }
+    store_row(&new_t[slot], q.q0, q.q1, q.q2, q.q3);
+  });
+  u64 n[] = {rows - failed, failed};                                     // moved, failed
+  block_add(n, 0u, counters, nullptr);
+}
+
+// Find-or-create-and-combine: THE way a bulk operation (merge, fold, unfold) brings one (key, row) into `dst`.  The
+// row's slot is found or claimed as the growth claims one -- the first access is the claiming compare-and-swap at the
+// key's home.  A created row takes the source's values (ADD: w * q_src, the defaultdict's zero row + w * q_src); a row
+// that was there is read (two 8-byte loads), combined and written back (two 8-byte stores).  The caller sees to it that
+// no two lanes ever bring the same key -- ONE WRITER PER DST ROW -- so the only races are the slot claims
+// `probe_insert` / `confirm` resolve, there are no float atomics, and the result depends on the two tables' rows only.
+// float32, product and sum rounded separately (no contraction: Q2048_NO_CONTRACT, checked in the ISA -- v_pk_mul_f32
+// + v_pk_add_f32, no fma): a numpy model in float32 gives the same bits.
+struct Tally { u64 created, combined, dropped; uint32_t bits; };
 template <int MODE>
 __device__ __forceinline__ float merge_value(float d, float s, float w, float one_minus_w) {
   // plain * and + under the pragma: it binds the operators written HERE (the header's __fmul_rn / __fadd_rn are
@@ -2218,66 +2259,46 @@ __device__ __forceinline__ float merge_value(float d, float s, float w, float on
     return fabsf(s) > fabsf(d) ? s : d;
   }
 }
+template <int MODE, class Key>
+__device__ __forceinline__ void combine_into(q2048_slot* dst, u64 dst_mask, const Key& key, const Row& s, float w,
+                                             float one_minus_w, Tally& t) {
+  bool inserted;
+  const int64_t slot = probe_insert(dst, dst_mask, key, key_home(key, dst_mask), inserted, kMaxProbe);
+  if (slot < 0) { ++t.dropped; t.bits |= Q2048_STATUS_TABLE_FULL; return; }
+  float r0, r1, r2, r3;
+  if (inserted) {
+    ++t.created;
+    if (deep_row(key, dst_mask, (u64)slot)) t.bits |= Q2048_STATUS_DEEP_ROW;
+    if constexpr (MODE == Q2048_MERGE_ADD) { r0 = __fmul_rn(w, s.q0); r1 = __fmul_rn(w, s.q1); r2 = __fmul_rn(w, s.q2); r3 = __fmul_rn(w, s.q3); }
+    else { r0 = s.q0; r1 = s.q1; r2 = s.q2; r3 = s.q3; }
+  } else {
+    ++t.combined;
+    const u64 lo = ld_u64(&dst[slot].q[0]), hi = ld_u64(&dst[slot].q[2]);
+    r0 = merge_value<MODE>(bits_f32((uint32_t)lo), s.q0, w, one_minus_w);
+    r1 = merge_value<MODE>(bits_f32((uint32_t)(lo >> 32)), s.q1, w, one_minus_w);
+    r2 = merge_value<MODE>(bits_f32((uint32_t)hi), s.q2, w, one_minus_w);
+    r3 = merge_value<MODE>(bits_f32((uint32_t)(hi >> 32)), s.q3, w, one_minus_w);
+  }
+  store_row(&dst[slot], r0, r1, r2, r3);
+}
+// counters += {lead..., rows written (created + combined + dropped), created, combined, dropped}, *status |= bits
+template <class... Lead>
+__device__ __forceinline__ void tally_add(const Tally& t, u64* counters, uint32_t* status, Lead... lead) {
+  u64 n[] = {lead..., t.created + t.combined + t.dropped, t.created, t.combined, t.dropped};
+  block_add(n, t.bits, counters, status);
+}
+
+// Merge (q2048_table_merge): the growth's move with a destination that may already hold the key: every occupied row
+// of `src` goes through combine_into.  Keys of one table are distinct, so no two lanes ever meet on a dst row.
+// counters[0..3] += rows read / created / combined / dropped.
 template <int WORDS, int MODE>
 __global__ __launch_bounds__(kBlock) void k_table_merge(const q2048_slot* src, u64 src_cap, q2048_slot* dst, u64 dst_mask,
                                                         float w, float one_minus_w, u64* counters, uint32_t* status) {
-  const u32x4* t16 = reinterpret_cast<const u32x4*>(src);
-  u64 created = 0ull, combined = 0ull, dropped = 0ull;
-  uint32_t bits = 0u;
-  for (u64 i = (u64)blockIdx.x * kBlock + threadIdx.x; i < src_cap; i += (u64)gridDim.x * kBlock) {
-    const u32x4 a = __builtin_nontemporal_load(&t16[2ull * i]);          // {key, q0, q1}
-    const u64 k = (u64)a.x | ((u64)a.y << 32);
-    if (k == 0ull) continue;
-    const u32x4 b = __builtin_nontemporal_load(&t16[2ull * i + 1ull]);   // {q2, q3, second key word}
-    typename Geo<WORDS == 1 ? 4 : 5>::Key key;
-    key.k0 = k;
-    if constexpr (WORDS == 2) key.k1 = (u64)b.z | ((u64)b.w << 32);
-    bool inserted;
-    const int64_t slot = probe_insert(dst, dst_mask, key, key_home(key, dst_mask), inserted, kMaxProbe);
-    if (slot < 0) { ++dropped; bits |= Q2048_STATUS_TABLE_FULL; continue; }
-    const float s0 = bits_f32(a.z), s1 = bits_f32(a.w), s2 = bits_f32(b.x), s3 = bits_f32(b.y);
-    float r0, r1, r2, r3;
-    if (inserted) {
-      ++created;
-      // beyond the learning paths' probe limit: as q2048_table_import tells its caller
-      if (seq_pos(seq_of(key_hash(key), dst_mask), (u64)slot) >= probe_limit(dst_mask, kRolloutProbe)) bits |= Q2048_STATUS_DEEP_ROW;
-      if constexpr (MODE == Q2048_MERGE_ADD) { r0 = __fmul_rn(w, s0); r1 = __fmul_rn(w, s1); r2 = __fmul_rn(w, s2); r3 = __fmul_rn(w, s3); }
-      else { r0 = s0; r1 = s1; r2 = s2; r3 = s3; }
-    } else {
-      ++combined;
-      const u64 lo = ld_u64(&dst[slot].q[0]), hi = ld_u64(&dst[slot].q[2]);
-      r0 = merge_value<MODE>(bits_f32((uint32_t)lo), s0, w, one_minus_w);
-      r1 = merge_value<MODE>(bits_f32((uint32_t)(lo >> 32)), s1, w, one_minus_w);
-      r2 = merge_value<MODE>(bits_f32((uint32_t)hi), s2, w, one_minus_w);
-      r3 = merge_value<MODE>(bits_f32((uint32_t)(hi >> 32)), s3, w, one_minus_w);
-    }
-    uint2* q = reinterpret_cast<uint2*>(dst[slot].q);                    // 8-byte aligned (offset 8 of a 32-B slot)
-    q[0] = make_uint2(f32_bits(r0), f32_bits(r1));
-    q[1] = make_uint2(f32_bits(r2), f32_bits(r3));
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    created += __shfl_xor(created, d); combined += __shfl_xor(combined, d); dropped += __shfl_xor(dropped, d);
-    bits |= __shfl_xor(bits, d);
-  }
-  __shared__ u64 wc[3][kBlock / 64];
-  __shared__ uint32_t wb[kBlock / 64];
-  if ((threadIdx.x & 63u) == 0u) {
-    const uint32_t wv = threadIdx.x >> 6;
-    wc[0][wv] = created; wc[1][wv] = combined; wc[2][wv] = dropped; wb[wv] = bits;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    u64 c = 0ull, m = 0ull, f = 0ull;
-    uint32_t sb = 0u;
-#pragma unroll
-    for (int v = 0; v < kBlock / 64; ++v) { c += wc[0][v]; m += wc[1][v]; f += wc[2][v]; sb |= wb[v]; }
-    if (c + m + f) atomicAdd(&counters[0], c + m + f);
-    if (c) atomicAdd(&counters[1], c);
-    if (m) atomicAdd(&counters[2], m);
-    if (f) atomicAdd(&counters[3], f);
-    if (sb && status != nullptr) atomicOr(status, sb);
-  }
+  Tally t{0ull, 0ull, 0ull, 0u};
+  stream_rows(src, src_cap, [&](u64 k0, u64 k1, const Row& q) {
+    combine_into<MODE>(dst, dst_mask, table_key<WORDS>(k0, k1), q, w, one_minus_w, t);
+  });
+  tally_add(t, counters, status);                                        // (rows read == rows written)
 }
 
 // Fold (q2048_table_fold): the merge's sibling for a PLAIN `src` and a symmetry-folded `dst`.  Up to eight rows of
@@ -2285,19 +2306,16 @@ __global__ __launch_bounds__(kBlock) void k_table_merge(const q2048_slot* src, u
 // be made true: a lane streams `src` as the merge does, and for an occupied slot walks its orbit's members in order
 // (fold_orbit, q2048_core.hpp), looking the others up in `src` itself (probe_find under the bulk limit; `src` is only
 // read).  A lane that finds a present member ahead of its own is not the orbit's leader and stops there; the leader
-// collects the remaining members, forms the orbit's row in the canonical frame and performs the orbit's one
-// find-or-create in `dst`, combined by MODE exactly as the merge combines a source row.  One writer per dst row, no
-// float atomics: the result depends on the two tables' rows only.  counters[0..4] += rows read / orbits / created /
-// combined / dropped, one atomic per counter and block.
+// collects the remaining members, forms the orbit's row in the canonical frame and brings it into `dst` with the
+// orbit's one combine_into.  counters[0..4] += rows read / orbits / created / combined / dropped.
 static_assert(Q2048_FOLD_MEAN == kFoldMean && Q2048_FOLD_MEAN_TRAINED == kFoldMeanTrained && Q2048_FOLD_SUM == kFoldSum &&
               Q2048_FOLD_MAXABS == kFoldMaxAbs, "q2048.h / q2048_core.hpp");
 template <int FOLD, int MODE>
 __global__ __launch_bounds__(kBlock) void k_table_fold(const q2048_slot* src, u64 src_cap, q2048_slot* dst, u64 dst_mask,
                                                        float w, float one_minus_w, u64* counters, uint32_t* status) {
-  const u32x4* t16 = reinterpret_cast<const u32x4*>(src);
   const u64 src_mask = src_cap - 1ull;
-  u64 read = 0ull, created = 0ull, combined = 0ull, dropped = 0ull;
-  uint32_t bits = 0u;
+  u64 read = 0ull;
+  Tally t{0ull, 0ull, 0ull, 0u};
   const auto find = [src, src_mask](uint64_t k, float out[4]) {
     Row row;
     bool made;
@@ -2305,147 +2323,34 @@ __global__ __launch_bounds__(kBlock) void k_table_fold(const q2048_slot* src, u6
     out[0] = row.q0; out[1] = row.q1; out[2] = row.q2; out[3] = row.q3;
     return present;
   };
-  for (u64 i = (u64)blockIdx.x * kBlock + threadIdx.x; i < src_cap; i += (u64)gridDim.x * kBlock) {
-    const u32x4 a = __builtin_nontemporal_load(&t16[2ull * i]);          // {key, q0, q1}
-    const u64 k = (u64)a.x | ((u64)a.y << 32);
-    if (k == 0ull) continue;
+  stream_rows(src, src_cap, [&](u64 k, u64, const Row& q) {
     ++read;
-    const u32x4 b = __builtin_nontemporal_load(&t16[2ull * i + 1ull]);   // {q2, q3, summary word: not looked at}
-    const float own[4] = {bits_f32(a.z), bits_f32(a.w), bits_f32(b.x), bits_f32(b.y)};
+    const float own[4] = {q.q0, q.q1, q.q2, q.q3};
     uint64_t canon;
-    float s[4];
-    if (!fold_orbit<FOLD>(k, own, find, canon, s)) continue;             // another lane leads this orbit
-    const Geo<4>::Key key{(u64)canon};
-    bool inserted;
-    const int64_t slot = probe_insert(dst, dst_mask, key, key_home(key, dst_mask), inserted, kMaxProbe);
-    if (slot < 0) { ++dropped; bits |= Q2048_STATUS_TABLE_FULL; continue; }
-    float r0, r1, r2, r3;
-    if (inserted) {
-      ++created;
-      if (seq_pos(seq_of(key_hash(key), dst_mask), (u64)slot) >= probe_limit(dst_mask, kRolloutProbe)) bits |= Q2048_STATUS_DEEP_ROW;
-      if constexpr (MODE == Q2048_MERGE_ADD) { r0 = __fmul_rn(w, s[0]); r1 = __fmul_rn(w, s[1]); r2 = __fmul_rn(w, s[2]); r3 = __fmul_rn(w, s[3]); }
-      else { r0 = s[0]; r1 = s[1]; r2 = s[2]; r3 = s[3]; }
-    } else {
-      ++combined;
-      const u64 lo = ld_u64(&dst[slot].q[0]), hi = ld_u64(&dst[slot].q[2]);
-      r0 = merge_value<MODE>(bits_f32((uint32_t)lo), s[0], w, one_minus_w);
-      r1 = merge_value<MODE>(bits_f32((uint32_t)(lo >> 32)), s[1], w, one_minus_w);
-      r2 = merge_value<MODE>(bits_f32((uint32_t)hi), s[2], w, one_minus_w);
-      r3 = merge_value<MODE>(bits_f32((uint32_t)(hi >> 32)), s[3], w, one_minus_w);
-    }
-    uint2* q = reinterpret_cast<uint2*>(dst[slot].q);                    // 8-byte aligned (offset 8 of a 32-B slot)
-    q[0] = make_uint2(f32_bits(r0), f32_bits(r1));
-    q[1] = make_uint2(f32_bits(r2), f32_bits(r3));
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    read += __shfl_xor(read, d); created += __shfl_xor(created, d); combined += __shfl_xor(combined, d);
-    dropped += __shfl_xor(dropped, d); bits |= __shfl_xor(bits, d);
-  }
-  __shared__ u64 wc[4][kBlock / 64];
-  __shared__ uint32_t wb[kBlock / 64];
-  if ((threadIdx.x & 63u) == 0u) {
-    const uint32_t wv = threadIdx.x >> 6;
-    wc[0][wv] = read; wc[1][wv] = created; wc[2][wv] = combined; wc[3][wv] = dropped; wb[wv] = bits;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    u64 n = 0ull, c = 0ull, m = 0ull, f = 0ull;
-    uint32_t sb = 0u;
-#pragma unroll
-    for (int v = 0; v < kBlock / 64; ++v) { n += wc[0][v]; c += wc[1][v]; m += wc[2][v]; f += wc[3][v]; sb |= wb[v]; }
-    if (n) atomicAdd(&counters[0], n);
-    if (c + m + f) atomicAdd(&counters[1], c + m + f);
-    if (c) atomicAdd(&counters[2], c);
-    if (m) atomicAdd(&counters[3], m);
-    if (f) atomicAdd(&counters[4], f);
-    if (sb && status != nullptr) atomicOr(status, sb);
-  }
-}
-
-template <int FOLD>
-void launch_fold(int mode, dim3 grid, hipStream_t stream, const q2048_slot* src, u64 cap, q2048_slot* dst, u64 mask, float w,
-                 float one_minus_w, u64* counters, uint32_t* status) {
-  if (mode == Q2048_MERGE_ADD)
-    hipLaunchKernelGGL((k_table_fold<FOLD, Q2048_MERGE_ADD>), grid, dim3(kBlock), 0, stream, src, cap, dst, mask, w,
-                       one_minus_w, counters, status);
-  else if (mode == Q2048_MERGE_BLEND)
-    hipLaunchKernelGGL((k_table_fold<FOLD, Q2048_MERGE_BLEND>), grid, dim3(kBlock), 0, stream, src, cap, dst, mask, w,
-                       one_minus_w, counters, status);
-  else
-    hipLaunchKernelGGL((k_table_fold<FOLD, Q2048_MERGE_MAXABS>), grid, dim3(kBlock), 0, stream, src, cap, dst, mask, w,
-                       one_minus_w, counters, status);
+    float r[4];
+    if (!fold_orbit<FOLD>(k, own, find, canon, r)) return;               // another lane leads this orbit
+    combine_into<MODE>(dst, dst_mask, Geo<4>::Key{(u64)canon}, Row{r[0], r[1], r[2], r[3]}, w, one_minus_w, t);
+  });
+  tally_add(t, counters, status, read);
 }
 
 // Unfold (q2048_table_unfold): the fold's inverse, for a symmetry-folded `src` and a PLAIN `dst`.  A lane streams
 // `src` as the merge does, and an occupied slot that holds a canonical key sends one row per member of its orbit
-// (unfold_orbit, q2048_core.hpp: the member's key, the row in the member's frame) through the merge's find-or-create
-// and its arithmetic -- up to eight of them, one after the other.  Distinct canonical keys have disjoint orbits and
-// one lane writes its whole orbit, so no two lanes ever meet on a dst row: the only races are the slot claims.  A
-// key that is not canonical is counted and skipped.  counters[0..5] += rows read / skipped / members / created /
-// combined / dropped, one atomic per counter and block.
+// (unfold_orbit, q2048_core.hpp: the member's key, the row in the member's frame) through combine_into -- up to eight
+// of them, one after the other.  Distinct canonical keys have disjoint orbits and one lane writes its whole orbit, so
+// no two lanes ever meet on a dst row.  A key that is not canonical is counted and skipped.  counters[0..5] += rows
+// read / skipped / members / created / combined / dropped.
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void k_table_unfold(const q2048_slot* src, u64 src_cap, q2048_slot* dst, u64 dst_mask,
                                                          float w, float one_minus_w, u64* counters, uint32_t* status) {
-  const u32x4* t16 = reinterpret_cast<const u32x4*>(src);
-  u64 read = 0ull, skipped = 0ull, created = 0ull, combined = 0ull, dropped = 0ull;
-  uint32_t bits = 0u;
-  const auto emit = [&](uint64_t m, const Row& s) {
-    const Geo<4>::Key key{(u64)m};
-    bool inserted;
-    const int64_t slot = probe_insert(dst, dst_mask, key, key_home(key, dst_mask), inserted, kMaxProbe);
-    if (slot < 0) { ++dropped; bits |= Q2048_STATUS_TABLE_FULL; return; }
-    float r0, r1, r2, r3;
-    if (inserted) {
-      ++created;
-      if (seq_pos(seq_of(key_hash(key), dst_mask), (u64)slot) >= probe_limit(dst_mask, kRolloutProbe)) bits |= Q2048_STATUS_DEEP_ROW;
-      if constexpr (MODE == Q2048_MERGE_ADD) { r0 = __fmul_rn(w, s.q0); r1 = __fmul_rn(w, s.q1); r2 = __fmul_rn(w, s.q2); r3 = __fmul_rn(w, s.q3); }
-      else { r0 = s.q0; r1 = s.q1; r2 = s.q2; r3 = s.q3; }
-    } else {
-      ++combined;
-      const u64 lo = ld_u64(&dst[slot].q[0]), hi = ld_u64(&dst[slot].q[2]);
-      r0 = merge_value<MODE>(bits_f32((uint32_t)lo), s.q0, w, one_minus_w);
-      r1 = merge_value<MODE>(bits_f32((uint32_t)(lo >> 32)), s.q1, w, one_minus_w);
-      r2 = merge_value<MODE>(bits_f32((uint32_t)hi), s.q2, w, one_minus_w);
-      r3 = merge_value<MODE>(bits_f32((uint32_t)(hi >> 32)), s.q3, w, one_minus_w);
-    }
-    uint2* q = reinterpret_cast<uint2*>(dst[slot].q);                    // 8-byte aligned (offset 8 of a 32-B slot)
-    q[0] = make_uint2(f32_bits(r0), f32_bits(r1));
-    q[1] = make_uint2(f32_bits(r2), f32_bits(r3));
-  };
-  for (u64 i = (u64)blockIdx.x * kBlock + threadIdx.x; i < src_cap; i += (u64)gridDim.x * kBlock) {
-    const u32x4 a = __builtin_nontemporal_load(&t16[2ull * i]);          // {key, q0, q1}
-    const u64 k = (u64)a.x | ((u64)a.y << 32);
-    if (k == 0ull) continue;
+  u64 read = 0ull, skipped = 0ull;
+  Tally t{0ull, 0ull, 0ull, 0u};
+  const auto emit = [&](uint64_t m, const Row& q) { combine_into<MODE>(dst, dst_mask, Geo<4>::Key{(u64)m}, q, w, one_minus_w, t); };
+  stream_rows(src, src_cap, [&](u64 k, u64, const Row& q) {
     ++read;
-    const u32x4 b = __builtin_nontemporal_load(&t16[2ull * i + 1ull]);   // {q2, q3, summary word: not looked at}
-    if (unfold_orbit(k, Row{bits_f32(a.z), bits_f32(a.w), bits_f32(b.x), bits_f32(b.y)}, emit) == 0u) ++skipped;
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    read += __shfl_xor(read, d); skipped += __shfl_xor(skipped, d); created += __shfl_xor(created, d);
-    combined += __shfl_xor(combined, d); dropped += __shfl_xor(dropped, d); bits |= __shfl_xor(bits, d);
-  }
-  __shared__ u64 wc[5][kBlock / 64];
-  __shared__ uint32_t wb[kBlock / 64];
-  if ((threadIdx.x & 63u) == 0u) {
-    const uint32_t wv = threadIdx.x >> 6;
-    wc[0][wv] = read; wc[1][wv] = skipped; wc[2][wv] = created; wc[3][wv] = combined; wc[4][wv] = dropped; wb[wv] = bits;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    u64 n = 0ull, k = 0ull, c = 0ull, m = 0ull, f = 0ull;
-    uint32_t sb = 0u;
-#pragma unroll
-    for (int v = 0; v < kBlock / 64; ++v) { n += wc[0][v]; k += wc[1][v]; c += wc[2][v]; m += wc[3][v]; f += wc[4][v]; sb |= wb[v]; }
-    if (n) atomicAdd(&counters[0], n);
-    if (k) atomicAdd(&counters[1], k);
-    if (c + m + f) atomicAdd(&counters[2], c + m + f);
-    if (c) atomicAdd(&counters[3], c);
-    if (m) atomicAdd(&counters[4], m);
-    if (f) atomicAdd(&counters[5], f);
-    if (sb && status != nullptr) atomicOr(status, sb);
-  }
+    if (unfold_orbit(k, q, emit) == 0u) ++skipped;
+  });
+  tally_add(t, counters, status, read, skipped);
 }
 
 // Placement probe: `steps` scattered device-scope atomic ORs of 0 per lane into key words chosen
@@ -2554,6 +2459,32 @@ inline int fused_mode(uint32_t flags, int n, const void* side) {   // play-only 
   const bool frozen = (flags & Q2048_FLAG_NO_NEW_ROWS) != 0u;
   return sym | ((flags & Q2048_FLAG_TD_CAS) ? kModeCas : kModeLearn) | (frozen ? kModeFrozen : 0) |
          ((frozen && (n == 4 || side != nullptr) && (flags & Q2048_FLAG_LINE_SUMMARY)) ? kModeSummary : 0);   // (5x5: only with a side array)
+}
+// merge, fold and unfold: `mode` / `fold` as a compile-time constant (f gets a std::integral_constant), and the one
+// launch they share -- a grid-stride pass over src in the growth's grid (8 blocks of 4 waves per CU)
+template <class F>
+void with_mode(int mode, F&& f) {
+  if (mode == Q2048_MERGE_ADD) f(std::integral_constant<int, Q2048_MERGE_ADD>{});
+  else if (mode == Q2048_MERGE_BLEND) f(std::integral_constant<int, Q2048_MERGE_BLEND>{});
+  else f(std::integral_constant<int, Q2048_MERGE_MAXABS>{});
+}
+template <class F>
+void with_fold(int fold, F&& f) {
+  if (fold == Q2048_FOLD_MEAN) f(std::integral_constant<int, Q2048_FOLD_MEAN>{});
+  else if (fold == Q2048_FOLD_MEAN_TRAINED) f(std::integral_constant<int, Q2048_FOLD_MEAN_TRAINED>{});
+  else if (fold == Q2048_FOLD_SUM) f(std::integral_constant<int, Q2048_FOLD_SUM>{});
+  else f(std::integral_constant<int, Q2048_FOLD_MAXABS>{});
+}
+using CombineKernel = void (*)(const q2048_slot*, u64, q2048_slot*, u64, float, float, u64*, uint32_t*);
+int launch_combine(CombineKernel kernel, q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, int src_cap_log2, float w,
+                   uint64_t* counters, uint32_t* status, void* stream) {
+  const u64 cap = 1ull << src_cap_log2, mask = (1ull << dst_cap_log2) - 1ull;
+  const u64 want = (cap + kBlock - 1) / kBlock;
+  const dim3 grid((unsigned)(want < 2048 ? want : 2048));
+  const float one_minus_w = 1.0f - w;
+  hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, src, cap, dst, mask, w, one_minus_w,
+                     reinterpret_cast<u64*>(counters), status);
+  return launch_status();
 }
 constexpr size_t kOptsSizeNoSide = offsetof(q2048_rollout_opts, line_summary);   // the layout before `line_summary`
 static_assert(kOptsSizeNoSide == 56 && sizeof(q2048_rollout_opts) == 64, "ABI layout");
@@ -3122,28 +3053,12 @@ int q2048_table_import(q2048_slot* table, int cap_log2, const uint64_t* keys, co
   return launch_status();
 }
 
-#define Q2048_LAUNCH_MERGE(WORDS)                                                                                     \
-  do {                                                                                                                \
-    if (mode == Q2048_MERGE_ADD)                                                                                      \
-      hipLaunchKernelGGL((k_table_merge<WORDS, Q2048_MERGE_ADD>), grid, dim3(kBlock), 0, (hipStream_t)stream, src,    \
-                         cap, dst, mask, w, one_minus_w, reinterpret_cast<u64*>(counters), status);                   \
-    else if (mode == Q2048_MERGE_BLEND)                                                                               \
-      hipLaunchKernelGGL((k_table_merge<WORDS, Q2048_MERGE_BLEND>), grid, dim3(kBlock), 0, (hipStream_t)stream, src,  \
-                         cap, dst, mask, w, one_minus_w, reinterpret_cast<u64*>(counters), status);                   \
-    else                                                                                                              \
-      hipLaunchKernelGGL((k_table_merge<WORDS, Q2048_MERGE_MAXABS>), grid, dim3(kBlock), 0, (hipStream_t)stream, src, \
-                         cap, dst, mask, w, one_minus_w, reinterpret_cast<u64*>(counters), status);                   \
-  } while (0)
 int q2048_table_merge(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, int src_cap_log2, int key_words,
                       int mode, float w, uint64_t* counters, uint32_t* status, void* stream) {
   if (int e = check_merge(dst, dst_cap_log2, src, src_cap_log2, counters, key_words == 1 || key_words == 2, true, mode, w)) return e;
-  const u64 cap = 1ull << src_cap_log2, mask = (1ull << dst_cap_log2) - 1ull;
-  const u64 want = (cap + kBlock - 1) / kBlock;
-  const dim3 grid((unsigned)(want < 2048 ? want : 2048));              // the growth's move: 8 blocks of 4 waves per CU
-  const float one_minus_w = 1.0f - w;
-  if (key_words == 1) Q2048_LAUNCH_MERGE(1);
-  else Q2048_LAUNCH_MERGE(2);
-  return launch_status();
+  CombineKernel kernel;
+  with_mode(mode, [&](auto m) { kernel = key_words == 1 ? k_table_merge<1, decltype(m)::value> : k_table_merge<2, decltype(m)::value>; });
+  return launch_combine(kernel, dst, dst_cap_log2, src, src_cap_log2, w, counters, status, stream);
 }
 
 int q2048_table_fold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, int src_cap_log2, int key_words, int fold,
@@ -3152,17 +3067,9 @@ int q2048_table_fold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, i
   if (key_words == 2) return Q2048_ERR_UNSUPPORTED;                    // (5x5 has no folded table)
   const bool fold_ok = fold == Q2048_FOLD_MEAN || fold == Q2048_FOLD_MEAN_TRAINED || fold == Q2048_FOLD_SUM || fold == Q2048_FOLD_MAXABS;
   if (int e = check_merge(dst, dst_cap_log2, src, src_cap_log2, counters, key_words == 1, fold_ok, mode, w)) return e;
-  const u64 cap = 1ull << src_cap_log2, mask = (1ull << dst_cap_log2) - 1ull;
-  const u64 want = (cap + kBlock - 1) / kBlock;
-  const dim3 grid((unsigned)(want < 2048 ? want : 2048));              // the merge's grid: a grid-stride pass over src
-  const float one_minus_w = 1.0f - w;
-  u64* ctr = reinterpret_cast<u64*>(counters);
-  const hipStream_t s = (hipStream_t)stream;
-  if (fold == Q2048_FOLD_MEAN) launch_fold<Q2048_FOLD_MEAN>(mode, grid, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
-  else if (fold == Q2048_FOLD_MEAN_TRAINED) launch_fold<Q2048_FOLD_MEAN_TRAINED>(mode, grid, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
-  else if (fold == Q2048_FOLD_SUM) launch_fold<Q2048_FOLD_SUM>(mode, grid, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
-  else launch_fold<Q2048_FOLD_MAXABS>(mode, grid, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
-  return launch_status();
+  CombineKernel kernel;
+  with_fold(fold, [&](auto f) { with_mode(mode, [&](auto m) { kernel = k_table_fold<decltype(f)::value, decltype(m)::value>; }); });
+  return launch_combine(kernel, dst, dst_cap_log2, src, src_cap_log2, w, counters, status, stream);
 }
 
 int q2048_table_unfold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src, int src_cap_log2, int key_words, int mode,
@@ -3170,19 +3077,9 @@ int q2048_table_unfold(q2048_slot* dst, int dst_cap_log2, const q2048_slot* src,
   if (!dst || !src || !counters) return Q2048_ERR_NULL;
   if (key_words == 2) return Q2048_ERR_UNSUPPORTED;                    // (5x5 has no folded table)
   if (int e = check_merge(dst, dst_cap_log2, src, src_cap_log2, counters, key_words == 1, true, mode, w)) return e;
-  const u64 cap = 1ull << src_cap_log2, mask = (1ull << dst_cap_log2) - 1ull;
-  const u64 want = (cap + kBlock - 1) / kBlock;
-  const dim3 grid((unsigned)(want < 2048 ? want : 2048));              // the merge's grid: a grid-stride pass over src
-  const float one_minus_w = 1.0f - w;
-  u64* ctr = reinterpret_cast<u64*>(counters);
-  const hipStream_t s = (hipStream_t)stream;
-  if (mode == Q2048_MERGE_ADD)
-    hipLaunchKernelGGL(k_table_unfold<Q2048_MERGE_ADD>, grid, dim3(kBlock), 0, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
-  else if (mode == Q2048_MERGE_BLEND)
-    hipLaunchKernelGGL(k_table_unfold<Q2048_MERGE_BLEND>, grid, dim3(kBlock), 0, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
-  else
-    hipLaunchKernelGGL(k_table_unfold<Q2048_MERGE_MAXABS>, grid, dim3(kBlock), 0, s, src, cap, dst, mask, w, one_minus_w, ctr, status);
-  return launch_status();
+  CombineKernel kernel;
+  with_mode(mode, [&](auto m) { kernel = k_table_unfold<decltype(m)::value>; });
+  return launch_combine(kernel, dst, dst_cap_log2, src, src_cap_log2, w, counters, status, stream);
 }
 
 int q2048_table_probe(q2048_slot* table, int cap_log2, int64_t lanes, int steps, uint64_t seed,
