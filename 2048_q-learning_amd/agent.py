@@ -1133,6 +1133,9 @@ class BatchedQLearningAgent:
         if sd.get("kind") == "row_tuple":         # (a file without "kind" is a hash table: every earlier checkpoint)
             raise ValueError("this checkpoint holds row-tuple weights (BatchedRowTupleAgent), not a hash table: the "
                              "two kinds do not load into each other")
+        if sd.get("kind") == "line_tuple":
+            raise ValueError("this checkpoint holds line-tuple weights (BatchedLineTupleAgent), not a hash table: the "
+                             "two kinds do not load into each other")
         if sd["board_size"] != self.board_size:
             raise ValueError("checkpoint was taken with another board size")
         if bool(sd.get("symmetric", False)) != self.symmetric:
@@ -1558,6 +1561,133 @@ class BatchedRowTupleAgent:
         self.stats_f.copy_(sf)
         self.ctr, self.seed, self.env_id0, self.lr, self.gamma = ctr, seed, env_id0, lr, gamma
         vars(self.schedule).update(schedule)
+
+
+class BatchedLineTupleAgent(BatchedRowTupleAgent):
+    """The row-tuple learner with the four COLUMNS as features beside the four rows (the "all lines" n-tuple layout):
+    Q(s,a) = sum over the eight lines f of W[f][idx_f(s)][a], W float32 [8, 65536, 4] (8 MiB), features 0..3 the
+    rows (the row-tuple indices), 4..7 the columns read from the top.  Same methods, checks, draws and TD target as
+    `BatchedRowTupleAgent` (the error is spread over eight weights, lr / 8 each), through the q2048_lt_* entry
+    points; a checkpoint says "kind": "line_tuple", and `load_row_tuple` promotes a row-tuple checkpoint."""
+
+    N_FEATURES = 8
+
+    def __init__(self, total_epochs, action_space=4, learning_rate=0.1, discount_factor=0.9,
+                 exploration_rate=1.0, exploration_min=0.01, device="cuda", seed: int = 0,
+                 env_id0: int = 0):
+        super().__init__(total_epochs, action_space, learning_rate, discount_factor, exploration_rate,
+                         exploration_min, device, seed, env_id0)
+        self.weights = torch.zeros((self.N_FEATURES, 65536, 4), dtype=torch.float32, device=self.device)
+
+    def choose_action(self, boards) -> torch.Tensor:
+        boards = self._boards(boards)
+        B = boards.shape[0]
+        actions = torch.empty(B, dtype=torch.uint8, device=self.device)
+        N.check(self._L.q2048_lt_choose(_ptr(self.weights), _ptr(boards), B, float(self.epsilon),
+                                        self.seed, self.env_id0, self.ctr & 0xFFFFFFFF, _ptr(actions),
+                                        _stream(self.device)), "lt_choose")
+        self.ctr += 1
+        return actions
+
+    def update_q_value(self, boards, actions, reward, next_boards, done) -> None:
+        boards, next_boards = self._boards(boards), self._boards(next_boards)
+        B = boards.shape[0]
+        vec = lambda v, dt: torch.as_tensor(v).to(device=self.device, dtype=dt).contiguous()  # noqa: E731
+        actions, reward, done = vec(actions, torch.uint8), vec(reward, torch.float32), vec(done, torch.uint8)
+        if not (actions.shape == reward.shape == done.shape == (B,)):
+            raise ValueError("actions / reward / done must have shape (B,)")
+        N.check(self._L.q2048_lt_update(_ptr(self.weights), _ptr(boards), _ptr(actions), _ptr(reward),
+                                        _ptr(next_boards), _ptr(done), B, float(self.lr),
+                                        float(self.gamma), _ptr(self.status), _stream(self.device)),
+                "lt_update")
+
+    def q_values(self, boards) -> torch.Tensor:
+        boards = self._boards(boards)
+        q = torch.empty((boards.shape[0], 4), dtype=torch.float32, device=self.device)
+        N.check(self._L.q2048_lt_lookup(_ptr(self.weights), _ptr(boards), boards.shape[0], _ptr(q),
+                                        _stream(self.device)), "lt_lookup")
+        return q
+
+    def fused_rollout(self, env: BatchedGame2048Env, steps: int) -> None:
+        if env.board_size != 4 or env.device != self.device:
+            raise ValueError("the line-tuple learner needs a 4x4 env on the same device")
+        if env.env_flags:
+            raise ValueError("env profiles are supported by the hash-table agent only")
+        if (env.seed, env.env_id0, env.ctr) != (self.seed, self.env_id0, self.ctr):
+            raise ValueError("env and agent must share seed, env_id0 and step counter")
+        N.check(self._L.q2048_lt_fused_rollout(
+            _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), env.num_envs, int(steps),
+            float(self.epsilon), float(self.lr), float(self.gamma), self.seed, self.env_id0,
+            self.ctr & 0xFFFFFFFF, _ptr(self.stats_i), _ptr(self.stats_f), _ptr(self.status),
+            _stream(self.device)), "lt_fused_rollout")
+        env.ctr += int(steps)
+        self.ctr += int(steps)
+
+    def play_rollout(self, env: BatchedGame2048Env, steps: int, epsilon: float = 0.0) -> None:
+        """The greedy player on the weights (q2048_lt_play_rollout): `BatchedRowTupleAgent.play_rollout` with this
+        learner's row.  The weights are only read; statistics go to `play_stats`."""
+        if env.device != self.device:
+            raise ValueError("env and agent live on different devices")
+        if env.board_size != 4:
+            raise ValueError("the line-tuple learner plays 4x4 boards only")
+        if self._play_stats is None:
+            self._play_stats = new_stats_vectors(self.device)
+        si, sf = self._play_stats
+        N.check(self._L.q2048_lt_play_rollout(
+            _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), env.num_envs, int(steps), float(epsilon), env.seed,
+            env.env_id0, env.ctr & 0xFFFFFFFF, env.env_flags, _ptr(si), _ptr(sf), _ptr(self.status),
+            _stream(self.device)), "lt_play_rollout")
+        env.ctr += int(steps)
+
+    # -- checkpoint / resume / promotion ------------------------------------------------------
+    def state_dict(self, compact: bool = True) -> dict:
+        """`BatchedRowTupleAgent.state_dict` with "kind": "line_tuple" and weights float32 [8, 65536, 4]."""
+        sd = super().state_dict(compact)
+        sd["kind"] = "line_tuple"
+        return sd
+
+    @staticmethod
+    def _validated(sd: dict, kind: str, features: int):
+        """The fields of a row- or line-tuple checkpoint, all checked; nothing is written."""
+        if sd.get("kind") != kind:
+            held = {"row_tuple": "row-tuple weights (BatchedRowTupleAgent; `load_row_tuple` promotes them)",
+                    "line_tuple": "line-tuple weights (BatchedLineTupleAgent)"}.get(
+                        sd.get("kind"), "a hash table (BatchedQLearningAgent)")
+            raise ValueError(f"this checkpoint holds {held}, not {kind.replace('_', '-')} weights: the kinds do not "
+                             "load into each other")
+        if int(sd["board_size"]) != 4:
+            raise ValueError(f"{kind.replace('_', '-')} weights are 4x4 only")
+        w, si, sf = sd["weights"], sd["stats_i"], sd["stats_f"]
+        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or tuple(w.shape) != (features, 65536, 4):
+            raise ValueError(f"weights must be a float32 tensor of shape ({features}, 65536, 4), got "
+                             f"{getattr(w, 'dtype', type(w).__name__)} {tuple(getattr(w, 'shape', ()))}")
+        if not isinstance(si, torch.Tensor) or si.dtype != torch.int64 or tuple(si.shape) != (N.NSTAT_I,) or \
+                not isinstance(sf, torch.Tensor) or sf.dtype != torch.float64 or tuple(sf.shape) != (N.NSTAT_F,):
+            raise ValueError(f"stats_i / stats_f must be int64 [{N.NSTAT_I}] / float64 [{N.NSTAT_F}]")
+        return (w, si, sf, dict(sd["schedule"]), int(sd["ctr"]), int(sd["seed"]), int(sd["env_id0"]),
+                float(sd["lr"]), float(sd["gamma"]))
+
+    def _take(self, si, sf, schedule, ctr, seed, env_id0, lr, gamma) -> None:
+        self.stats_i.copy_(si)
+        self.stats_f.copy_(sf)
+        self.ctr, self.seed, self.env_id0, self.lr, self.gamma = ctr, seed, env_id0, lr, gamma
+        vars(self.schedule).update(schedule)
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Everything is validated before anything of this agent, on the host or the device, is written."""
+        w, *rest = self._validated(sd, "line_tuple", self.N_FEATURES)
+        self.weights.copy_(w)
+        self._take(*rest)
+
+    def load_row_tuple(self, sd: dict) -> None:
+        """PROMOTION: takes a row-tuple checkpoint (`BatchedRowTupleAgent.state_dict`) -- its weights into features
+        0..3, features 4..7 zeroed, and its schedule, counters and statistics.  `q_values` then equals the row-tuple
+        agent's as values (the column half adds +0.0: only a -0.0 may change its sign bit), and the trained row
+        weights go on learning with columns.  Validated before anything is written, like `load_state_dict`."""
+        w, *rest = self._validated(sd, "row_tuple", 4)
+        self.weights[:4].copy_(w)
+        self.weights[4:].zero_()
+        self._take(*rest)
 
 
 def new_stats_vectors(device):

@@ -68,6 +68,40 @@ static inline int check_rt_play(const void* boards, const void* aux, const void*
   return Q2048_OK;
 }
 
+// What the four-call entry points and the fused learner of the line-tuple family check, in the order of their
+// q2048_rt_* counterparts: B, NULL, alignment, (steps,) the scalars.
+static inline int check_lt_choose(const void* weights, const void* boards, int64_t B, double eps, const void* actions) {
+  if (int e = check_batch(B, 4)) return e;
+  if (!weights || !boards || !actions) return Q2048_ERR_NULL;
+  if (!aligned16(weights) || !aligned16(boards)) return Q2048_ERR_ALIGN;
+  if (!(eps >= 0.0 && eps <= 1.0)) return Q2048_ERR_RANGE;
+  return Q2048_OK;
+}
+static inline int check_lt_lookup(const void* weights, const void* boards, int64_t B, const void* q_out) {
+  if (int e = check_batch(B, 4)) return e;
+  if (!weights || !boards || !q_out) return Q2048_ERR_NULL;
+  if (!aligned16(weights) || !aligned16(boards) || !aligned16(q_out)) return Q2048_ERR_ALIGN;
+  return Q2048_OK;
+}
+static inline int check_lt_update(const void* weights, const void* boards_s, const void* actions, const void* reward,
+                                  const void* boards_s2, const void* done, int64_t B, double lr, double gamma,
+                                  const void* status) {
+  if (int e = check_batch(B, 4)) return e;
+  if (!weights || !boards_s || !actions || !reward || !boards_s2 || !done || !status) return Q2048_ERR_NULL;
+  if (!aligned16(weights) || !aligned16(boards_s) || !aligned16(boards_s2)) return Q2048_ERR_ALIGN;
+  if (!(lr == lr) || !(gamma == gamma)) return Q2048_ERR_RANGE;
+  return Q2048_OK;
+}
+static inline int check_lt_fused(const void* boards, const void* aux, const void* weights, int64_t B, int64_t steps,
+                                 double eps, double lr, double gamma, const void* status) {
+  if (int e = check_batch(B, 4)) return e;
+  if (!boards || !aux || !weights || !status) return Q2048_ERR_NULL;
+  if (!aligned16(boards) || !aligned16(aux) || !aligned16(weights)) return Q2048_ERR_ALIGN;
+  if (steps < 0 || steps > (1 << 30)) return Q2048_ERR_SIZE;
+  if (!(eps >= 0.0 && eps <= 1.0) || !(lr == lr) || !(gamma == gamma)) return Q2048_ERR_RANGE;
+  return Q2048_OK;
+}
+
 // q2048_strerror
 static inline const char* error_text(int code) {
   switch (code) {

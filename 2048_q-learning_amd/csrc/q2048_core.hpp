@@ -965,4 +965,23 @@ Q_HD float rt_delta(float q_sa, float reward, float max_next, bool done, double 
   return (float)((lr * 0.25) * (target - (double)q_sa));
 }
 
+// line-tuple linear Q: the four rows and the four columns as features ("all lines"), W = float[8][65536][4].
+// Feature f < 4 is row f (the row-tuple index), feature 4 + c is pack_row of word c of transpose(b).  Q is the
+// row-tuple sum of the rows plus the same sum of the columns; the error is spread evenly over the eight weights.
+constexpr int kLtFeatures = 8;
+Q_HD float lt_sum(float e0, float e1, float e2, float e3, float e4, float e5, float e6, float e7) {
+  return rt_sum(e0, e1, e2, e3) + rt_sum(e4, e5, e6, e7);
+}
+Q_HD float lt_delta(float q_sa, float reward, float max_next, bool done, double lr, double gamma) {
+  const double target = (double)reward + (gamma * (double)max_next * (done ? 0.0 : 1.0));
+  return (float)((lr * 0.125) * (target - (double)q_sa));
+}
+// the eight indices of a board: ONE transpose per state serves the four column features
+struct LtIdx { uint32_t i[kLtFeatures]; };
+Q_HD LtIdx lt_indices(const Board& b) {
+  const Board t = transpose(b);
+  return LtIdx{{pack_row(b.r0), pack_row(b.r1), pack_row(b.r2), pack_row(b.r3),
+                pack_row(t.r0), pack_row(t.r1), pack_row(t.r2), pack_row(t.r3)}};
+}
+
 }  // namespace q2048

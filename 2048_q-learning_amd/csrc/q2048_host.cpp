@@ -835,6 +835,26 @@ inline void rt_scatter(float* w, const Board& b, const RtRows& e, int act, float
   for (int r = 0; r < 4; ++r) st_f32(rt_entry(w, r, idx[r]) + act, row_get(e.e[r], act) + d);
 }
 
+// ---- line-tuple linear Q (rows and columns as features): W = float[8][65536][4] ----------------------------------
+struct LtRows { Row e[kLtFeatures]; };
+inline LtRows lt_gather(const float* w, const LtIdx& x) {
+  LtRows e;
+  for (int f = 0; f < kLtFeatures; ++f) {
+    const float* p = rt_entry(const_cast<float*>(w), f, x.i[f]);
+    e.e[f] = Row{ld_f32(p), ld_f32(p + 1), ld_f32(p + 2), ld_f32(p + 3)};
+  }
+  return e;
+}
+inline Row lt_q(const LtRows& e) {
+  return Row{lt_sum(e.e[0].q0, e.e[1].q0, e.e[2].q0, e.e[3].q0, e.e[4].q0, e.e[5].q0, e.e[6].q0, e.e[7].q0),
+             lt_sum(e.e[0].q1, e.e[1].q1, e.e[2].q1, e.e[3].q1, e.e[4].q1, e.e[5].q1, e.e[6].q1, e.e[7].q1),
+             lt_sum(e.e[0].q2, e.e[1].q2, e.e[2].q2, e.e[3].q2, e.e[4].q2, e.e[5].q2, e.e[6].q2, e.e[7].q2),
+             lt_sum(e.e[0].q3, e.e[1].q3, e.e[2].q3, e.e[3].q3, e.e[4].q3, e.e[5].q3, e.e[6].q3, e.e[7].q3)};
+}
+inline void lt_scatter(float* w, const LtIdx& x, const LtRows& e, int act, float d) {
+  for (int f = 0; f < kLtFeatures; ++f) st_f32(rt_entry(w, f, x.i[f]) + act, row_get(e.e[f], act) + d);
+}
+
 // ---- bulk moves of rows into a table (import, merge, fold, unfold) ----------------------------------------------
 // the one- or two-word key of a table, as the type the probes are compiled for: f(Geo<4>::Key) or f(Geo<5>::Key)
 template <class F>
@@ -1506,6 +1526,156 @@ int q2048_rt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights,
         Draws y{0u, 0u, 0u, 0u};
         if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
         const Row q = rt_q(rt_gather(weights, b));
+        bool explored;
+        const int act = play_action(legal_mask(b), q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
+        const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+        st.i[Q2048_ST_VALID] += o.valid != 0;
+        st.i[Q2048_ST_EXPLORE] += explored;
+        reward_sum += (double)o.reward;
+        if (o.done) {
+          st.i[Q2048_ST_EPISODES] += 1;
+          st.episode(a, o.max_log2);
+          begin_episode(b, a, seed, id, (env & kEnvResetShaping) != 0);
+        }
+      }
+      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
+      st.f[Q2048_SF_REWARD] += reward_sum;
+      store_board(boards, i, b);
+      st_aux(aux, i, a);
+    }
+  });
+  stats_merge(parts, used, stats_i, stats_f);
+  return Q2048_OK;
+}
+
+// ---- the line-tuple family: the row-tuple functions above with lt_gather / lt_q / lt_scatter ----
+int q2048_lt_choose(const float* weights, const uint8_t* boards, int64_t B, double eps, uint64_t seed, uint64_t env_id0,
+                    uint32_t ctr, uint8_t* actions, void*) {
+  if (int e = check_lt_choose(weights, boards, B, eps, actions)) return e;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Board b;
+      load_board(boards, i, b);
+      const Draws x = draws(seed, env_id0 + (uint64_t)i, ctr, kStreamStep);
+      int act;
+      if (draw_uniform(x.x0) < eps) act = draw_action(x.x1);
+      else { const Row q = lt_q(lt_gather(weights, lt_indices(b))); act = argmax4(q.q0, q.q1, q.q2, q.q3); }
+      actions[i] = (uint8_t)act;
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_lt_lookup(const float* weights, const uint8_t* boards, int64_t B, float* q_out, void*) {
+  if (int e = check_lt_lookup(weights, boards, B, q_out)) return e;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Board b;
+      load_board(boards, i, b);
+      const Row q = lt_q(lt_gather(weights, lt_indices(b)));
+      q_out[4 * i] = q.q0; q_out[4 * i + 1] = q.q1; q_out[4 * i + 2] = q.q2; q_out[4 * i + 3] = q.q3;
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_lt_update(float* weights, const uint8_t* boards_s, const uint8_t* actions, const float* reward,
+                    const uint8_t* boards_s2, const uint8_t* done, int64_t B, double lr, double gamma, uint32_t* status,
+                    void*) {
+  if (int e = check_lt_update(weights, boards_s, actions, reward, boards_s2, done, B, lr, gamma, status)) return e;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      const int act = actions[i];
+      if (act > 3) { status_or(status, Q2048_STATUS_BAD_ACTION); continue; }
+      Board b_s, b_n;
+      load_board(boards_s, i, b_s);
+      load_board(boards_s2, i, b_n);
+      const Row qn = lt_q(lt_gather(weights, lt_indices(b_n)));
+      const LtIdx xs = lt_indices(b_s);
+      const LtRows es = lt_gather(weights, xs);
+      const float d = lt_delta(row_get(lt_q(es), act), reward[i], max4(qn.q0, qn.q1, qn.q2, qn.q3), done[i] != 0, lr, gamma);
+      lt_scatter(weights, xs, es, act, d);
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_lt_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, int64_t B, int64_t steps, double eps,
+                           double lr, double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i,
+                           double* stats_f, uint32_t* status, void*) {
+  if (int e = check_lt_fused(boards, aux, weights, B, steps, eps, lr, gamma, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  const int T = threads_for(B);
+  std::vector<Stats> parts((size_t)T);
+  Stats* sp = parts.data();
+  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+    Stats& st = sp[tid];
+    for (int64_t i = lo; i < hi; ++i) {
+      const uint64_t id = env_id0 + (uint64_t)i;
+      Board b;
+      load_board(boards, i, b);
+      Aux a = ld_aux(aux, i);
+      double reward_sum = 0.0;
+      LtIdx xs = lt_indices(b);
+      LtRows es = lt_gather(weights, xs);
+      for (int64_t t = 0; t < steps; ++t) {
+        const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+        const Row q = lt_q(es);
+        bool explored;
+        const int act = eps_greedy(eps, x.x0, x.x1, q.q0, q.q1, q.q2, q.q3, explored);
+        const StepOut o = env_step(b, a, act, x.x2, x.x3);
+        const LtIdx xn = lt_indices(b);
+        LtRows en = lt_gather(weights, xn);
+        const Row qn = lt_q(en);
+        const float d = lt_delta(row_get(q, act), o.reward, max4(qn.q0, qn.q1, qn.q2, qn.q3), o.done != 0, lr, gamma);
+        lt_scatter(weights, xs, es, act, d);
+        st.i[Q2048_ST_VALID] += o.valid != 0;
+        st.i[Q2048_ST_EXPLORE] += explored;
+        reward_sum += (double)o.reward;
+        if (o.done) {
+          st.i[Q2048_ST_EPISODES] += 1;
+          st.episode(a, o.max_log2);
+          begin_episode(b, a, seed, id);
+          xs = lt_indices(b);
+          es = lt_gather(weights, xs);
+        } else {
+          for (int f = 0; f < kLtFeatures; ++f)
+            if (xn.i[f] == xs.i[f]) row_set(en.e[f], act, row_get(es.e[f], act) + d);
+          es = en;
+          xs = xn;
+        }
+      }
+      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
+      st.f[Q2048_SF_REWARD] += reward_sum;
+      store_board(boards, i, b);
+      st_aux(aux, i, a);
+    }
+  });
+  stats_merge(parts, used, stats_i, stats_f);
+  return Q2048_OK;
+}
+int q2048_lt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
+                          uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                          double* stats_f, uint32_t* status, void*) {
+  if (int e = check_rt_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  const uint64_t eps_t = eps_threshold(eps);
+  const ImageLuts lut{&g_lut_image};
+  const int env = env_bits(flags);
+  const int T = threads_for(B);
+  std::vector<Stats> parts((size_t)T);
+  Stats* sp = parts.data();
+  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+    Stats& st = sp[tid];
+    for (int64_t i = lo; i < hi; ++i) {
+      const uint64_t id = env_id0 + (uint64_t)i;
+      Board b;
+      load_board(boards, i, b);
+      Aux a = ld_aux(aux, i);
+      const DrawPrep prep = draws_prepare(seed, id, kStreamStep);
+      double reward_sum = 0.0;
+      for (int64_t t = 0; t < steps; ++t) {
+        const Draws x = draws_at(prep, ctr0 + (uint32_t)t);
+        Draws y{0u, 0u, 0u, 0u};
+        if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+        const Row q = lt_q(lt_gather(weights, lt_indices(b)));
         bool explored;
         const int act = play_action(legal_mask(b), q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
         const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);

@@ -2052,6 +2052,218 @@ __global__ __launch_bounds__(kBlock) void k_rt_play_rollout(
 }
 
 // ---------------------------------------------------------------------------------------------
+// line-tuple linear Q: the row-tuple learner above with the four columns as features beside the
+// four rows, 4x4 only.  W = float[8][65536][4] (8 MiB: twice one XCD's L2, so it lives in L2 and
+// the Infinity Cache).  Everything the row-tuple comment says holds per feature: whole 16-byte
+// entries, one request each, EIGHT in flight behind one wait; agent-scope (sc1) loads in the
+// learner kernels, plain loads in the player; a write stores old + d with the value the lane
+// gathered, a plain 4-byte store, the last writer wins.  The column indices come from ONE
+// transpose per state (lt_indices): the fused loop computes the indices of s' once and uses them
+// for the gather, for the carried-entry rule and, one step later, for the scatter.
+// Kernels of their own, not the rt_ ones templated on a feature count: no existing kernel changes.
+// ---------------------------------------------------------------------------------------------
+struct LtRows { Row e[kLtFeatures]; };
+// the eight entries of a state: eight 16-byte agent-scope loads in flight together, one wait
+__device__ __forceinline__ LtRows lt_gather(const float* w, const LtIdx& x) {
+  u32x4 v0, v1, v2, v3, v4, v5, v6, v7;
+  asm volatile(
+      "global_load_dwordx4 %0, %8, off sc1\n\tglobal_load_dwordx4 %1, %9, off sc1\n\t"
+      "global_load_dwordx4 %2, %10, off sc1\n\tglobal_load_dwordx4 %3, %11, off sc1\n\t"
+      "global_load_dwordx4 %4, %12, off sc1\n\tglobal_load_dwordx4 %5, %13, off sc1\n\t"
+      "global_load_dwordx4 %6, %14, off sc1\n\tglobal_load_dwordx4 %7, %15, off sc1\n\t"
+      "s_waitcnt vmcnt(0)"
+      : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3), "=&v"(v4), "=&v"(v5), "=&v"(v6), "=&v"(v7)
+      : "v"(rt_addr(w, 0, x.i[0])), "v"(rt_addr(w, 1, x.i[1])), "v"(rt_addr(w, 2, x.i[2])),
+        "v"(rt_addr(w, 3, x.i[3])), "v"(rt_addr(w, 4, x.i[4])), "v"(rt_addr(w, 5, x.i[5])),
+        "v"(rt_addr(w, 6, x.i[6])), "v"(rt_addr(w, 7, x.i[7]))
+      : "memory");
+  return LtRows{{rt_row(v0), rt_row(v1), rt_row(v2), rt_row(v3), rt_row(v4), rt_row(v5), rt_row(v6), rt_row(v7)}};
+}
+// the same with plain loads, for the player: nothing writes W during its launch (see rt_gather_readonly)
+__device__ __forceinline__ LtRows lt_gather_readonly(const float* w, const LtIdx& x) {
+  u32x4 v0, v1, v2, v3, v4, v5, v6, v7;
+  asm volatile(
+      "global_load_dwordx4 %0, %8, off\n\tglobal_load_dwordx4 %1, %9, off\n\t"
+      "global_load_dwordx4 %2, %10, off\n\tglobal_load_dwordx4 %3, %11, off\n\t"
+      "global_load_dwordx4 %4, %12, off\n\tglobal_load_dwordx4 %5, %13, off\n\t"
+      "global_load_dwordx4 %6, %14, off\n\tglobal_load_dwordx4 %7, %15, off\n\t"
+      "s_waitcnt vmcnt(0)"
+      : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3), "=&v"(v4), "=&v"(v5), "=&v"(v6), "=&v"(v7)
+      : "v"(rt_addr(w, 0, x.i[0])), "v"(rt_addr(w, 1, x.i[1])), "v"(rt_addr(w, 2, x.i[2])),
+        "v"(rt_addr(w, 3, x.i[3])), "v"(rt_addr(w, 4, x.i[4])), "v"(rt_addr(w, 5, x.i[5])),
+        "v"(rt_addr(w, 6, x.i[6])), "v"(rt_addr(w, 7, x.i[7]))
+      : "memory");
+  return LtRows{{rt_row(v0), rt_row(v1), rt_row(v2), rt_row(v3), rt_row(v4), rt_row(v5), rt_row(v6), rt_row(v7)}};
+}
+__device__ __forceinline__ Row lt_q(const LtRows& e) {
+  return Row{lt_sum(e.e[0].q0, e.e[1].q0, e.e[2].q0, e.e[3].q0, e.e[4].q0, e.e[5].q0, e.e[6].q0, e.e[7].q0),
+             lt_sum(e.e[0].q1, e.e[1].q1, e.e[2].q1, e.e[3].q1, e.e[4].q1, e.e[5].q1, e.e[6].q1, e.e[7].q1),
+             lt_sum(e.e[0].q2, e.e[1].q2, e.e[2].q2, e.e[3].q2, e.e[4].q2, e.e[5].q2, e.e[6].q2, e.e[7].q2),
+             lt_sum(e.e[0].q3, e.e[1].q3, e.e[2].q3, e.e[3].q3, e.e[4].q3, e.e[5].q3, e.e[6].q3, e.e[7].q3)};
+}
+__device__ __forceinline__ void lt_scatter(float* w, const LtIdx& x, const LtRows& e, int act, float d) {
+  float* base = w + act;
+#pragma unroll
+  for (int f = 0; f < kLtFeatures; ++f) base[((size_t)f * kRtIdx + x.i[f]) << 2] = row_get(e.e[f], act) + d;
+}
+
+__global__ __launch_bounds__(kBlock) void k_lt_choose(const float* w, const uint8_t* boards, int64_t B,
+                                                      double eps, uint64_t seed, uint64_t env_id0,
+                                                      uint32_t ctr, uint8_t* actions) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const Board b = load_board(boards, i, B, st);
+  const Draws x = draws(seed, env_id0 + (uint64_t)i, ctr, kStreamStep);
+  int act;
+  if (draw_uniform(x.x0) < eps) act = draw_action(x.x1);
+  else { const Row q = lt_q(lt_gather(w, lt_indices(b))); act = argmax4(q.q0, q.q1, q.q2, q.q3); }
+  actions[i] = (uint8_t)act;
+}
+
+__global__ __launch_bounds__(kBlock) void k_lt_lookup(const float* w, const uint8_t* boards, int64_t B,
+                                                      float* q_out) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const Row q = lt_q(lt_gather(w, lt_indices(load_board(boards, i, B, st))));
+  reinterpret_cast<float4*>(q_out)[i] = make_float4(q.q0, q.q1, q.q2, q.q3);
+}
+
+__global__ __launch_bounds__(kBlock) void k_lt_update(float* w, const uint8_t* s, const uint8_t* actions,
+                                                      const float* reward, const uint8_t* s2,
+                                                      const uint8_t* done, int64_t B, double lr,
+                                                      double gamma, uint32_t* status) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const int act = actions[i];
+  if (act > 3) { atomicOr(status, Q2048_STATUS_BAD_ACTION); return; }
+  const Board b_s = load_board(s, i, B, st), b_n = load_board(s2, i, B, st);
+  const Row qn = lt_q(lt_gather(w, lt_indices(b_n)));
+  const LtIdx xs = lt_indices(b_s);
+  const LtRows es = lt_gather(w, xs);
+  const float d = lt_delta(row_get(lt_q(es), act), reward[i], max4(qn.q0, qn.q1, qn.q2, qn.q3),
+                           done[i] != 0, lr, gamma);
+  lt_scatter(w, xs, es, act, d);
+}
+
+__global__ __launch_bounds__(kBlock) void k_lt_fused_rollout(
+    uint8_t* boards, q2048_aux* aux, float* w, int64_t B, int steps, double eps, double lr,
+    double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f,
+    uint32_t* /*status: as on k_rt_fused_rollout, nothing data-dependent can go wrong on this path*/) {
+  __shared__ BlockStats bs;
+  stats_clear(bs);
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < B) {
+    Stage<4> st;
+    const uint64_t id = env_id0 + (uint64_t)i;
+    Board b = load_board(boards, i, B, st);
+    Aux a = ld_aux(aux, i);
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
+    double reward_sum = 0.0;
+    LtIdx xs = lt_indices(b);
+    LtRows es = lt_gather(w, xs);   // indices and entries of the current state, carried from step to step
+    for (int t = 0; t < steps; ++t) {
+      const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+      const Row q = lt_q(es);
+      bool explored;
+      const int act = eps_greedy(eps, x.x0, x.x1, q.q0, q.q1, q.q2, q.q3, explored);
+      const StepOut o = env_step(b, a, act, x.x2, x.x3);
+      const LtIdx xn = lt_indices(b);
+      LtRows en = lt_gather(w, xn);
+      const Row qn = lt_q(en);
+      const float d = lt_delta(row_get(q, act), o.reward, max4(qn.q0, qn.q1, qn.q2, qn.q3),
+                               o.done != 0, lr, gamma);
+      lt_scatter(w, xs, es, act, d);
+      n_valid += wave_count(o.valid != 0);
+      n_explore += wave_count(explored);
+      n_done += wave_count(o.done != 0);
+      reward_sum += (double)o.reward;
+      if (o.done) {
+        episode_stats(bs, a, o.max_log2);
+        begin_episode(b, a, seed, id);
+        xs = lt_indices(b);
+        es = lt_gather(w, xs);
+      } else {
+        // s' becomes s: its entries were gathered before the write above, so PER FEATURE a line that did
+        // not move (same index at the same feature) takes the value just written.  A horizontal move
+        // leaves whole columns alone more often than rows, a vertical move the other way round.
+#pragma unroll
+        for (int f = 0; f < kLtFeatures; ++f)
+          if (xn.i[f] == xs.i[f]) row_set(en.e[f], act, row_get(es.e[f], act) + d);
+        es = en;
+        xs = xn;
+      }
+    }
+    store_board(boards, i, B, b, st);
+    st_aux(aux, i, a);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+    const uint32_t n_active = wave_count(true);
+    if (wave_leader()) {
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  stats_flush(bs, stats_i, stats_f);
+}
+
+// the greedy player on line-tuple weights (q2048_lt_play_rollout): k_rt_play_rollout with q2048_lt_lookup's row
+template <int ENV>
+__global__ __launch_bounds__(kBlock) void k_lt_play_rollout(
+    uint8_t* boards, q2048_aux* aux, const float* w, int64_t B, int steps, double eps, uint64_t seed,
+    uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
+  __shared__ BlockStats bs;
+  __shared__ Stage<4> st;
+  __shared__ LutImage lut_lds;
+  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
+  if (threadIdx.x < kLutImageDoubles)
+    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
+  stats_clear(bs);                                        // (its barrier publishes the image too)
+  const ImageLuts lut{&lut_lds};
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  Board b = load_board(boards, i, B, st);
+  if (i < B) {
+    const uint64_t id = env_id0 + (uint64_t)i;
+    Aux a = ld_aux(aux, i);
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
+    double reward_sum = 0.0;
+    const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
+    const uint64_t eps_t = eps_threshold(eps);
+    for (int t = 0; t < steps; ++t) {
+      const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
+      Draws y{0u, 0u, 0u, 0u};
+      if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+      const Row q = lt_q(lt_gather_readonly(w, lt_indices(b)));
+      bool explored;
+      const int act = play_action(legal_mask(b), q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
+      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+      if (o.done) {
+        episode_stats(bs, a, o.max_log2);
+        begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
+      }
+      n_valid += wave_count(o.valid != 0);
+      n_explore += wave_count(explored);
+      n_done += wave_count(o.done != 0);
+      reward_sum += (double)o.reward;
+    }
+    st_aux(aux, i, a);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+    const uint32_t n_active = wave_count(true);
+    if (wave_leader()) {
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  store_board(boards, i, B, b, st);
+  stats_flush(bs, stats_i, stats_f);
+}
+
+// ---------------------------------------------------------------------------------------------
 // table utilities
 // ---------------------------------------------------------------------------------------------
 // Streams the whole table once, in tiles of 16 Ki slots per block: a lane reads the first 16 bytes
@@ -3033,6 +3245,60 @@ int q2048_rt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights,
     break;
   switch (env_bits(flags) & 3) { Q2048_LAUNCH_RT_PLAY(0) Q2048_LAUNCH_RT_PLAY(1) Q2048_LAUNCH_RT_PLAY(2) Q2048_LAUNCH_RT_PLAY(3) }
 #undef Q2048_LAUNCH_RT_PLAY
+  return launch_status();
+}
+
+int q2048_lt_choose(const float* weights, const uint8_t* boards, int64_t B, double eps, uint64_t seed,
+                    uint64_t env_id0, uint32_t ctr, uint8_t* actions, void* stream) {
+  if (int e = check_lt_choose(weights, boards, B, eps, actions)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_lt_choose, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights,
+                     boards, B, eps, seed, env_id0, ctr, actions);
+  return launch_status();
+}
+
+int q2048_lt_lookup(const float* weights, const uint8_t* boards, int64_t B, float* q_out, void* stream) {
+  if (int e = check_lt_lookup(weights, boards, B, q_out)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_lt_lookup, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights,
+                     boards, B, q_out);
+  return launch_status();
+}
+
+int q2048_lt_update(float* weights, const uint8_t* boards_s, const uint8_t* actions, const float* reward,
+                    const uint8_t* boards_s2, const uint8_t* done, int64_t B, double lr, double gamma,
+                    uint32_t* status, void* stream) {
+  if (int e = check_lt_update(weights, boards_s, actions, reward, boards_s2, done, B, lr, gamma, status)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_lt_update, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights,
+                     boards_s, actions, reward, boards_s2, done, B, lr, gamma, status);
+  return launch_status();
+}
+
+int q2048_lt_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, int64_t B, int64_t steps,
+                           double eps, double lr, double gamma, uint64_t seed, uint64_t env_id0,
+                           uint32_t ctr0, int64_t* stats_i, double* stats_f, uint32_t* status,
+                           void* stream) {
+  if (int e = check_lt_fused(boards, aux, weights, B, steps, eps, lr, gamma, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_lt_fused_rollout, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream,
+                     boards, aux, weights, B, (int)steps, eps, lr, gamma, seed, env_id0, ctr0, stats_i,
+                     stats_f, status);
+  return launch_status();
+}
+
+int q2048_lt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
+                          uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                          double* stats_f, uint32_t* status, void* stream) {
+  if (int e = check_rt_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+#define Q2048_LAUNCH_LT_PLAY(E)                                                                                    \
+  case E:                                                                                                          \
+    hipLaunchKernelGGL((k_lt_play_rollout<E>), dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, boards,    \
+                       aux, weights, B, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);                   \
+    break;
+  switch (env_bits(flags) & 3) { Q2048_LAUNCH_LT_PLAY(0) Q2048_LAUNCH_LT_PLAY(1) Q2048_LAUNCH_LT_PLAY(2) Q2048_LAUNCH_LT_PLAY(3) }
+#undef Q2048_LAUNCH_LT_PLAY
   return launch_status();
 }
 

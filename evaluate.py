@@ -4,7 +4,8 @@
 The reference's README lists an `evaluate.py` ("script per la valutazione e il testing",
 README.md:52) that its repository does not contain.  This is that script for the MI355X path: it
 loads a learner written by `train.py --save` (a hash table, or -- "kind": "row_tuple" -- the row-tuple learner's
-weights: the file says which, and the JSON line then carries "agent": "row-tuple"), plays `--episodes` games per env
+weights, or -- "kind": "line_tuple" -- the line-tuple learner's: the file says which, and the JSON line then carries
+"agent": "row-tuple" / "line-tuple"), plays `--episodes` games per env
 with the stored values -- rows are read, nothing is created or written -- and prints one JSON line: games, mean
 score / return, max-tile histogram.  Two policies:
 
@@ -68,7 +69,7 @@ def main(argv=None):
 
     pkg = importlib.import_module("2048_q-learning_amd")
     sd = torch.load(args.model, map_location="cpu", weights_only=False)
-    if sd.get("kind") == "row_tuple":
+    if sd.get("kind") in ("row_tuple", "line_tuple"):
         return main_row_tuple(args, torch, pkg, sd)
     n, rows = int(sd["board_size"]), len(sd["q"])
     cap = max(int(sd["capacity_log2"]), 4) if "table" in sd else max(16, (2 * max(rows, 1) - 1).bit_length())
@@ -110,9 +111,12 @@ def main(argv=None):
 
 def main_row_tuple(args, torch, pkg, sd):
     """A file of `train.py --agent row-tuple --save`: the same three policies on a `BatchedRowTupleAgent`.  There are no
-    rows to count: what must not change is the weights, all 4 MiB, bit for bit."""
-    agent = pkg.BatchedRowTupleAgent(1, learning_rate=sd["lr"], discount_factor=sd["gamma"],
-                                     exploration_rate=args.epsilon, seed=args.seed, device=args.device)
+    rows to count: what must not change is the weights, all 4 MiB, bit for bit.  A file of `--agent line-tuple` (8 MiB,
+    "kind": "line_tuple") plays the same way on a `BatchedLineTupleAgent`."""
+    line = sd.get("kind") == "line_tuple"
+    cls = pkg.BatchedLineTupleAgent if line else pkg.BatchedRowTupleAgent
+    agent = cls(1, learning_rate=sd["lr"], discount_factor=sd["gamma"], exploration_rate=args.epsilon, seed=args.seed,
+                device=args.device)
     agent.load_state_dict(sd)
     agent.seed, agent.ctr, agent.epsilon = args.seed, 0, args.epsilon     # evaluation has its own draws
     agent.stats(reset=True)
@@ -132,7 +136,8 @@ def main_row_tuple(args, torch, pkg, sd):
                 agent.fused_rollout(env, args.steps_per_launch)
             st = agent.stats()
     assert torch.equal(before.view(torch.int32), agent.weights.cpu().view(torch.int32))   # nothing was learnt
-    out = {"model": args.model, "agent": "row-tuple", "board_size": 4, "epsilon": args.epsilon, "policy": args.policy,
+    out = {"model": args.model, "agent": "line-tuple" if line else "row-tuple", "board_size": 4,
+           "epsilon": args.epsilon, "policy": args.policy,
            "envs": args.num_envs, "games": st["episodes"], "env_steps": st["steps"],
            "mean_score": st["mean_score"], "mean_return": st["mean_return"],
            "valid_move_frac": st["valid_moves"] / max(st["steps"], 1),

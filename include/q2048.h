@@ -67,7 +67,9 @@ extern "C" {
                                legal moves, one launch) and Q2048_FLAG_SYMMETRIC (one row for a board's eight mirror
                                images), detected by the symbol q2048_canonicalize; q2048_table_fold and
                                q2048_table_unfold (into and out of a folded table) likewise, each by its symbol;
-                               q2048_rt_play_rollout (the greedy player on row-tuple weights) too, by its symbol */
+                               q2048_rt_play_rollout (the greedy player on row-tuple weights) too, by its symbol;
+                               the line-tuple family q2048_lt_* (rows and columns as features) by the symbol
+                               q2048_lt_lookup */
 
 /* return codes */
 #define Q2048_OK 0
@@ -776,6 +778,39 @@ int q2048_rt_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weights, int6
  * their 16-byte alignment (boards, aux, weights), steps < 0 or > 2^30 (Q2048_ERR_SIZE), eps outside [0, 1]
  * (Q2048_ERR_RANGE).  A refused call writes nothing.  B == 0 or steps == 0: checked, then nothing happens, Q2048_OK. */
 int q2048_rt_play_rollout(uint8_t *boards, q2048_aux *aux, const float *weights, int64_t B, int64_t steps,
+                          double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
+                          int64_t *stats_i, double *stats_f, uint32_t *status, void *stream);
+
+/* ---- line-tuple linear Q: the rows AND the columns of the board as features ("all lines") ----------------------
+ * The row-tuple family above with eight features instead of four, 4x4 boards only.  weights = float[8][65536][4]
+ * (8 MiB, 16-byte aligned, zero = untrained).
+ *   features  f = 0..3 is row r = f:       idx_f = sum over k of (cell[4 r + k] & 15) << 4 k -- the row-tuple index;
+ *             f = 4..7 is column c = f-4:  idx_f = sum over k of (cell[4 k + c] & 15) << 4 k (cell k of the column,
+ *             counted from the top, in nibble k).  A cell >= 16 aliases by the mask, as above, and is not an error.
+ *   Q value   Q(s,a) = ((e0 + e1) + (e2 + e3)) + ((e4 + e5) + (e6 + e7)), e_f = weights[f][idx_f][a], in float32 with
+ *             exactly that association (the first half is the row-tuple sum of the rows).
+ *   TD step   target = (double)reward + gamma * (double)max_a' Q(s',a') * (done ? 0.0 : 1.0);
+ *             d = (float)((lr * 0.125) * (target - (double)Q(s,a))), rounded once; each of the eight
+ *             weights[f][idx_f(s)][a] is written as (the value this lane gathered) + d: a plain store, the last
+ *             writer wins (summing every lane's delta would scale the step size by the batch size, as above).
+ *   draws     the epsilon-greedy choice, the draws, the env step and the reset are exactly those of q2048_rt_choose /
+ *             q2048_rt_fused_rollout; the player's mask, its argmax over the legal moves and its draw contract are
+ *             exactly those of q2048_rt_play_rollout, Q2048_FLAG_ENV_DQN and Q2048_FLAG_RESET_SHAPING included.
+ * Each entry point has the argument list of its q2048_rt_* counterpart, checks its arguments in the same order and
+ * returns the same codes; `weights` is the 8 MiB array.  Row-tuple weights become line-tuple weights of the same Q
+ * by copying them into features 0..3 and zeroing features 4..7. */
+int q2048_lt_choose(const float *weights, const uint8_t *boards, int64_t B, double eps,
+                    uint64_t seed, uint64_t env_id0, uint32_t ctr, uint8_t *actions, void *stream);
+int q2048_lt_lookup(const float *weights, const uint8_t *boards, int64_t B, float *q_out,
+                    void *stream);
+int q2048_lt_update(float *weights, const uint8_t *boards_s, const uint8_t *actions,
+                    const float *reward, const uint8_t *boards_s2, const uint8_t *done, int64_t B,
+                    double lr, double gamma, uint32_t *status, void *stream);
+int q2048_lt_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weights, int64_t B,
+                           int64_t steps, double eps, double lr, double gamma, uint64_t seed,
+                           uint64_t env_id0, uint32_t ctr0, int64_t *stats_i, double *stats_f,
+                           uint32_t *status, void *stream);
+int q2048_lt_play_rollout(uint8_t *boards, q2048_aux *aux, const float *weights, int64_t B, int64_t steps,
                           double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
                           int64_t *stats_i, double *stats_f, uint32_t *status, void *stream);
 

@@ -83,8 +83,10 @@ def parse_args(argv=None):
                         "to 8x fewer rows for the same experience, so the table freezes that much later.  Learns a "
                         "different table than without the flag (every row is shared by its images); --save records it "
                         "and evaluate.py / --resume / merge_tables.py follow the file")
-    p.add_argument("--agent", choices=["hash", "row-tuple"], default="hash",
-                   help="hash = the reference's whole-board Q-table; row-tuple = BASELINE configs[1]")
+    p.add_argument("--agent", choices=["hash", "row-tuple", "line-tuple"], default="hash",
+                   help="hash = the reference's whole-board Q-table; row-tuple = BASELINE configs[1]; line-tuple = the "
+                        "row-tuple learner with the four columns as features beside the four rows (8 MiB of weights; "
+                        "--resume of a row-tuple file promotes it: rows kept, columns start at zero)")
     p.add_argument("--log", default="debug_log.csv", help="CSV log path (Agent/main.py:71)")
     p.add_argument("--report-every", type=int, default=10, help="launches between CSV rows (batched)")
     p.add_argument("--max-steps", type=int, default=0, help="stop after this many env steps per env (0 = off)")
@@ -99,8 +101,8 @@ def parse_args(argv=None):
                    help="shaped = QLearningBase's Game2048_env (the reference's tabular path); nopenalty = "
                         "the DQN path's env (Deep_QLearning/environment/Game2048_nopenalty_env.py: reward = "
                         "merge score or -10, done = game over)")
-    p.add_argument("--save", default="", help="write the trained learner (Q-table rows -- or, --agent row-tuple, the "
-                   "4 MiB of weights under \"kind\": \"row_tuple\" --, epsilon schedule, counters) "
+    p.add_argument("--save", default="", help="write the trained learner (Q-table rows -- or, --agent row-tuple / line-tuple, the "
+                   "4 / 8 MiB of weights under \"kind\": \"row_tuple\" / \"line_tuple\" --, epsilon schedule, counters) "
                    "to this file when training ends -- the models/ directory of the reference's README; "
                    "evaluate.py and --resume read it")
     p.add_argument("--resume", default="", help="continue from a file written by --save (same agent arguments): "
@@ -128,7 +130,7 @@ def parse_args(argv=None):
     p.add_argument("--eval-every", type=int, default=0,
                    help="batched mode, either agent: every N epochs measure the learner as a PLAYER -- greedy over the "
                         "moves that change the board (evaluate.py --policy legal --fused, q2048_play_rollout / "
-                        "q2048_rt_play_rollout) on a "
+                        "q2048_rt_play_rollout / q2048_lt_play_rollout) on a "
                         "separate env batch with its own seed, between two training launches on the training stream. "
                         "The table is only read and training's draws, counters and statistics are untouched: the run "
                         "trains what it trains without the flag.  0 (default) = off")
@@ -230,6 +232,9 @@ def train_batched(args, pkg):
     if args.agent == "row-tuple":
         agent = pkg.BatchedRowTupleAgent(args.episodes, 4, args.alpha, args.gamma, args.epsilon,
                                          args.epsilon_min, dev, args.seed, shard.env_id0)
+    elif args.agent == "line-tuple":
+        agent = pkg.BatchedLineTupleAgent(args.episodes, 4, args.alpha, args.gamma, args.epsilon,
+                                          args.epsilon_min, dev, args.seed, shard.env_id0)
     else:
         agent = pkg.BatchedQLearningAgent(args.episodes, 4, args.alpha, args.gamma, args.epsilon,
                                           args.epsilon_min, cap, dev, args.seed, shard.env_id0,
@@ -246,6 +251,10 @@ def train_batched(args, pkg):
             _fold_into(pkg, agent, sd, args, dev)
         elif args.unfold:
             _unfold_into(pkg, agent, sd, args, dev)
+        elif args.agent == "line-tuple" and sd.get("kind") == "row_tuple":
+            agent.load_row_tuple(sd)              # promotion: the trained rows go on learning with columns
+            if rank == 0:
+                print(f"promoted {args.resume}: row-tuple weights into features 0..3, columns start at zero", flush=True)
         else:
             agent.load_state_dict(sd)
         epoch0 = _resume_schedule(agent, sd, args, shard.total_envs)
@@ -498,7 +507,8 @@ def main(argv=None):
         if args.board_size != 4:
             raise SystemExit("--symmetric folds 4x4 boards only (--board-size 5 is not built)")
         if args.agent != "hash" or args.deterministic:
-            raise SystemExit("--symmetric applies to the fused hash-table path (not --agent row-tuple, not --deterministic)")
+            raise SystemExit("--symmetric applies to the fused hash-table path (not --agent " +
+                             (args.agent if args.agent != "hash" else "row-tuple") + ", not --deterministic)")
         if args.num_envs == 1 and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
             raise SystemExit("--symmetric needs the batched mode (--num-envs > 1): the one-state loop learns through "
                              "choose_action / update_q_value, which do not take the flag")
@@ -509,7 +519,7 @@ def main(argv=None):
             raise SystemExit("--fold says how the plain file of --resume is folded: it needs --resume")
     if args.unfold:
         if args.agent != "hash":
-            raise SystemExit("--unfold unfolds a hash table: not with --agent row-tuple")
+            raise SystemExit(f"--unfold unfolds a hash table: not with --agent {args.agent}")
         if args.symmetric:
             raise SystemExit("--unfold unfolds a folded file into a PLAIN table: not together with --symmetric (a "
                              "folded file resumes under --symmetric as it is)")
