@@ -1136,6 +1136,9 @@ class BatchedQLearningAgent:
         if sd.get("kind") == "line_tuple":
             raise ValueError("this checkpoint holds line-tuple weights (BatchedLineTupleAgent), not a hash table: the "
                              "two kinds do not load into each other")
+        if sd.get("kind") == "line_afterstate":
+            raise ValueError("this checkpoint holds afterstate values (BatchedAfterstateAgent), not a hash table: the "
+                             "two kinds do not load into each other")
         if sd["board_size"] != self.board_size:
             raise ValueError("checkpoint was taken with another board size")
         if bool(sd.get("symmetric", False)) != self.symmetric:
@@ -1651,7 +1654,8 @@ class BatchedLineTupleAgent(BatchedRowTupleAgent):
         """The fields of a row- or line-tuple checkpoint, all checked; nothing is written."""
         if sd.get("kind") != kind:
             held = {"row_tuple": "row-tuple weights (BatchedRowTupleAgent; `load_row_tuple` promotes them)",
-                    "line_tuple": "line-tuple weights (BatchedLineTupleAgent)"}.get(
+                    "line_tuple": "line-tuple weights (BatchedLineTupleAgent)",
+                    "line_afterstate": "afterstate values (BatchedAfterstateAgent)"}.get(
                         sd.get("kind"), "a hash table (BatchedQLearningAgent)")
             raise ValueError(f"this checkpoint holds {held}, not {kind.replace('_', '-')} weights: the kinds do not "
                              "load into each other")
@@ -1688,6 +1692,127 @@ class BatchedLineTupleAgent(BatchedRowTupleAgent):
         self.weights[:4].copy_(w)
         self.weights[4:].zero_()
         self._take(*rest)
+
+
+class BatchedAfterstateAgent(BatchedLineTupleAgent):
+    """The AFTERSTATE VALUE learner on the line features: V float32 [8, 65536] (2 MiB), one value per line entry.  A
+    state is judged by the four boards its moves lead to before the spawn: q_a = merge score of move a + v(moved
+    board), v = the sum of the moved board's eight entries; the choice is the player's in every method (greedy or
+    exploring over the moves that change the board), and the TD step moves v(afterstate of the move played) towards
+    gamma * (q of the greedy legal move of the next state), 0 at the end of a game.  The surface of
+    `BatchedLineTupleAgent` through the q2048_av_* entry points; a checkpoint says "kind": "line_afterstate", and
+    every other kind is refused in both directions -- Q entries are not afterstate values, so nothing is promoted."""
+
+    def __init__(self, total_epochs, action_space=4, learning_rate=0.1, discount_factor=0.9,
+                 exploration_rate=1.0, exploration_min=0.01, device="cuda", seed: int = 0,
+                 env_id0: int = 0):
+        super().__init__(total_epochs, action_space, learning_rate, discount_factor, exploration_rate,
+                         exploration_min, device, seed, env_id0)
+        self.weights = torch.zeros((self.N_FEATURES, 65536), dtype=torch.float32, device=self.device)
+
+    def choose_action(self, boards) -> torch.Tensor:
+        boards = self._boards(boards)
+        B = boards.shape[0]
+        actions = torch.empty(B, dtype=torch.uint8, device=self.device)
+        N.check(self._L.q2048_av_choose(_ptr(self.weights), _ptr(boards), B, float(self.epsilon),
+                                        self.seed, self.env_id0, self.ctr & 0xFFFFFFFF, _ptr(actions),
+                                        _stream(self.device)), "av_choose")
+        self.ctr += 1
+        return actions
+
+    def update_q_value(self, boards, actions, reward, next_boards, done) -> None:
+        """The reference's signature; `reward` is IGNORED (only its shape is checked): the value of an afterstate
+        estimates what comes after the move, and the learner's reward is the merge score of the next move, which
+        the step reads off `next_boards`.  A lane whose action does not change its board writes nothing."""
+        boards, next_boards = self._boards(boards), self._boards(next_boards)
+        B = boards.shape[0]
+        vec = lambda v, dt: torch.as_tensor(v).to(device=self.device, dtype=dt).contiguous()  # noqa: E731
+        actions, done = vec(actions, torch.uint8), vec(done, torch.uint8)
+        if not (actions.shape == tuple(torch.as_tensor(reward).shape) == done.shape == (B,)):
+            raise ValueError("actions / reward / done must have shape (B,)")
+        N.check(self._L.q2048_av_update(_ptr(self.weights), _ptr(boards), _ptr(actions), _ptr(next_boards),
+                                        _ptr(done), B, float(self.lr), float(self.gamma), _ptr(self.status),
+                                        _stream(self.device)), "av_update")
+
+    def q_values(self, boards) -> torch.Tensor:
+        """q_a for the four actions (q2048_av_lookup): merge score + value of the moved board."""
+        boards = self._boards(boards)
+        q = torch.empty((boards.shape[0], 4), dtype=torch.float32, device=self.device)
+        N.check(self._L.q2048_av_lookup(_ptr(self.weights), _ptr(boards), boards.shape[0], _ptr(q),
+                                        _stream(self.device)), "av_lookup")
+        return q
+
+    def values(self, boards) -> torch.Tensor:
+        """v of each board as given (q2048_av_value)."""
+        boards = self._boards(boards)
+        v = torch.empty((boards.shape[0],), dtype=torch.float32, device=self.device)
+        N.check(self._L.q2048_av_value(_ptr(self.weights), _ptr(boards), boards.shape[0], _ptr(v),
+                                       _stream(self.device)), "av_value")
+        return v
+
+    def fused_rollout(self, env: BatchedGame2048Env, steps: int) -> None:
+        if env.board_size != 4 or env.device != self.device:
+            raise ValueError("the afterstate learner needs a 4x4 env on the same device")
+        if env.env_flags:
+            raise ValueError("env profiles are supported by the hash-table agent only")
+        if (env.seed, env.env_id0, env.ctr) != (self.seed, self.env_id0, self.ctr):
+            raise ValueError("env and agent must share seed, env_id0 and step counter")
+        N.check(self._L.q2048_av_fused_rollout(
+            _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), env.num_envs, int(steps),
+            float(self.epsilon), float(self.lr), float(self.gamma), self.seed, self.env_id0,
+            self.ctr & 0xFFFFFFFF, _ptr(self.stats_i), _ptr(self.stats_f), _ptr(self.status),
+            _stream(self.device)), "av_fused_rollout")
+        env.ctr += int(steps)
+        self.ctr += int(steps)
+
+    def play_rollout(self, env: BatchedGame2048Env, steps: int, epsilon: float = 0.0) -> None:
+        """The greedy player on the values (q2048_av_play_rollout).  The weights are only read; statistics go to
+        `play_stats`."""
+        if env.device != self.device:
+            raise ValueError("env and agent live on different devices")
+        if env.board_size != 4:
+            raise ValueError("the afterstate learner plays 4x4 boards only")
+        if self._play_stats is None:
+            self._play_stats = new_stats_vectors(self.device)
+        si, sf = self._play_stats
+        N.check(self._L.q2048_av_play_rollout(
+            _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), env.num_envs, int(steps), float(epsilon), env.seed,
+            env.env_id0, env.ctr & 0xFFFFFFFF, env.env_flags, _ptr(si), _ptr(sf), _ptr(self.status),
+            _stream(self.device)), "av_play_rollout")
+        env.ctr += int(steps)
+
+    def state_dict(self, compact: bool = True) -> dict:
+        """`BatchedRowTupleAgent.state_dict` with "kind": "line_afterstate" and weights float32 [8, 65536]."""
+        sd = BatchedRowTupleAgent.state_dict(self, compact)
+        sd["kind"] = "line_afterstate"
+        return sd
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Everything is validated before anything of this agent, on the host or the device, is written."""
+        if sd.get("kind") != "line_afterstate":
+            held = {"row_tuple": "row-tuple weights (BatchedRowTupleAgent)",
+                    "line_tuple": "line-tuple weights (BatchedLineTupleAgent)"}.get(
+                        sd.get("kind"), "a hash table (BatchedQLearningAgent)")
+            raise ValueError(f"this checkpoint holds {held}, not afterstate values: the kinds do not load into each "
+                             "other (Q entries are not afterstate values: nothing is promoted)")
+        if int(sd["board_size"]) != 4:
+            raise ValueError("afterstate values are 4x4 only")
+        w, si, sf = sd["weights"], sd["stats_i"], sd["stats_f"]
+        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or tuple(w.shape) != (self.N_FEATURES, 65536):
+            raise ValueError(f"weights must be a float32 tensor of shape ({self.N_FEATURES}, 65536), got "
+                             f"{getattr(w, 'dtype', type(w).__name__)} {tuple(getattr(w, 'shape', ()))}")
+        if not isinstance(si, torch.Tensor) or si.dtype != torch.int64 or tuple(si.shape) != (N.NSTAT_I,) or \
+                not isinstance(sf, torch.Tensor) or sf.dtype != torch.float64 or tuple(sf.shape) != (N.NSTAT_F,):
+            raise ValueError(f"stats_i / stats_f must be int64 [{N.NSTAT_I}] / float64 [{N.NSTAT_F}]")
+        rest = (si, sf, dict(sd["schedule"]), int(sd["ctr"]), int(sd["seed"]), int(sd["env_id0"]),
+                float(sd["lr"]), float(sd["gamma"]))
+        self.weights.copy_(w)
+        self._take(*rest)
+
+    def load_row_tuple(self, sd: dict) -> None:
+        """Refused: a row- or line-tuple file holds Q entries per action, which are not afterstate values."""
+        raise ValueError("Q entries are not afterstate values: a row-tuple or line-tuple checkpoint cannot be promoted "
+                         "into a BatchedAfterstateAgent")
 
 
 def new_stats_vectors(device):

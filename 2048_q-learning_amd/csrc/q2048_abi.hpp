@@ -102,6 +102,34 @@ static inline int check_lt_fused(const void* boards, const void* aux, const void
   return Q2048_OK;
 }
 
+// The afterstate value family (q2048_av_*): order and codes of the lt_ counterparts.  q2048_av_value checks as the
+// lookup does; the update has no reward argument; the player checks as q2048_rt_play_rollout does.
+static inline int check_av_value(const void* weights, const void* boards, int64_t B, const void* v_out) {
+  return check_lt_lookup(weights, boards, B, v_out);
+}
+static inline int check_av_lookup(const void* weights, const void* boards, int64_t B, const void* q_out) {
+  return check_lt_lookup(weights, boards, B, q_out);
+}
+static inline int check_av_choose(const void* weights, const void* boards, int64_t B, double eps, const void* actions) {
+  return check_lt_choose(weights, boards, B, eps, actions);
+}
+static inline int check_av_update(const void* weights, const void* boards_s, const void* actions, const void* boards_s2,
+                                  const void* done, int64_t B, double lr, double gamma, const void* status) {
+  if (int e = check_batch(B, 4)) return e;
+  if (!weights || !boards_s || !actions || !boards_s2 || !done || !status) return Q2048_ERR_NULL;
+  if (!aligned16(weights) || !aligned16(boards_s) || !aligned16(boards_s2)) return Q2048_ERR_ALIGN;
+  if (!(lr == lr) || !(gamma == gamma)) return Q2048_ERR_RANGE;
+  return Q2048_OK;
+}
+static inline int check_av_fused(const void* boards, const void* aux, const void* weights, int64_t B, int64_t steps,
+                                 double eps, double lr, double gamma, const void* status) {
+  return check_lt_fused(boards, aux, weights, B, steps, eps, lr, gamma, status);
+}
+static inline int check_av_play(const void* boards, const void* aux, const void* weights, int64_t B, int64_t steps,
+                                double eps, uint32_t flags, const void* status) {
+  return check_rt_play(boards, aux, weights, B, steps, eps, flags, status);
+}
+
 // q2048_strerror
 static inline const char* error_text(int code) {
   switch (code) {

@@ -984,4 +984,103 @@ Q_HD LtIdx lt_indices(const Board& b) {
                 pack_row(t.r0), pack_row(t.r1), pack_row(t.r2), pack_row(t.r3)}};
 }
 
+// ------------------------------------------------------------------------------------------
+// afterstate value learner on the line features: V = float[8][65536], one value per line entry, indexed by
+// lt_indices.  A state is judged by the four boards its moves lead to BEFORE the spawn (the afterstates):
+//   c_a = s moved by a (move(), its score and its "changed" flag), q_a = (float)score_a + v(c_a),
+//   v(x) = lt_sum of the eight entries of x.
+// The choice is the player's (play_action over the moves that change the board), the TD step moves v(c_a) of the
+// move played towards gamma * best(s'), best(s') = q at the greedy legal move of the next state (0 if it has none).
+// ------------------------------------------------------------------------------------------
+// move() that also hands out the transpose of the moved board: both exist inside it (the slide works on "cell j of
+// every line" words, which are the board for a vertical move and its transpose for a horizontal one), so the eight
+// indices of an afterstate need no transpose of their own.  Same answers as move(), bit for bit.
+Q_HD bool move_with_transpose(Board& b, Board& bt, int action, uint32_t& score) {
+  const bool horiz = (action & 1) == 0;
+  const bool rev = (action & 2) != 0;
+  const Board t = transpose(b);
+  const uint32_t p0 = horiz ? t.r0 : b.r0, p1 = horiz ? t.r1 : b.r1;
+  const uint32_t p2 = horiz ? t.r2 : b.r2, p3 = horiz ? t.r3 : b.r3;
+  uint32_t c0 = rev ? p3 : p0, c1 = rev ? p2 : p1, c2 = rev ? p1 : p2, c3 = rev ? p0 : p3;
+  const uint32_t o0 = c0, o1 = c1, o2 = c2, o3 = c3;
+  score = slide_lines(c0, c1, c2, c3);
+  const bool moved = ((c0 ^ o0) | (c1 ^ o1) | (c2 ^ o2) | (c3 ^ o3)) != 0;
+  const Board q{rev ? c3 : c0, rev ? c2 : c1, rev ? c1 : c2, rev ? c0 : c3};
+  const Board qt = transpose(q);
+  b = horiz ? qt : q;
+  bt = horiz ? q : qt;
+  return moved;
+}
+// the eight indices of a board whose transpose is at hand
+Q_HD LtIdx lt_indices_of(const Board& b, const Board& t) {
+  return LtIdx{{pack_row(b.r0), pack_row(b.r1), pack_row(b.r2), pack_row(b.r3),
+                pack_row(t.r0), pack_row(t.r1), pack_row(t.r2), pack_row(t.r3)}};
+}
+// the four candidates of a state: indices of c_a, merge score, and the mask of the moves that change the board
+struct AvCands { LtIdx x[4]; uint32_t score[4]; uint32_t legal; };
+Q_HD AvCands av_candidates(const Board& s) {
+  AvCands c;
+  c.legal = 0u;
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    Board m = s, mt;
+    c.legal |= (uint32_t)move_with_transpose(m, mt, a, c.score[a]) << a;
+    c.x[a] = lt_indices_of(m, mt);
+  }
+  return c;
+}
+Q_HD float av_v(const float e[kLtFeatures]) { return lt_sum(e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7]); }
+Q_HD float av_q(uint32_t score, float v) { return (float)score + v; }
+// best(s): q at the action play_action picks with threshold 0 (first maximum over the legal moves, strict >);
+// 0 without a legal move
+Q_HD float av_best(uint32_t legal, const Row& q) {
+  bool explored;
+  const int a = play_action(legal, q.q0, q.q1, q.q2, q.q3, 0ull, 0u, 0u, explored);
+  return (legal & 15u) ? row_get(q, a) : 0.0f;
+}
+// One evaluation of a state: the candidates and their 32 gathered entries (each library gathers in its own way).
+struct AvEval { AvCands c; float e[4][kLtFeatures]; };
+Q_HD Row av_row(const AvEval& ev) {
+  return Row{av_q(ev.c.score[0], av_v(ev.e[0])), av_q(ev.c.score[1], av_v(ev.e[1])),
+             av_q(ev.c.score[2], av_v(ev.e[2])), av_q(ev.c.score[3], av_v(ev.e[3]))};
+}
+// the afterstate of the move played, out of an evaluation: its indices and the entries gathered for it (selects,
+// not an address: an evaluation stays in registers)
+struct AvTaken { LtIdx x; float e[kLtFeatures]; };
+// (the four values are passed BY VALUE: all four are read, then selected.  A ternary over the array elements
+// themselves becomes one load at an address computed from `a`, and the evaluation then lives in scratch memory.
+// Two bit tests, a = 0..3: a chain of a == k becomes a switch, which hipcc lowers to a tree of branches per value.)
+Q_HD uint32_t av_sel(int a, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3) {
+  const uint32_t lo = (a & 1) ? v1 : v0, hi = (a & 1) ? v3 : v2;
+  return (a & 2) ? hi : lo;
+}
+Q_HD float av_sel(int a, float v0, float v1, float v2, float v3) {
+  const float lo = (a & 1) ? v1 : v0, hi = (a & 1) ? v3 : v2;
+  return (a & 2) ? hi : lo;
+}
+Q_HD AvTaken av_taken(const AvEval& ev, int act) {
+  AvTaken t;
+#pragma unroll
+  for (int f = 0; f < kLtFeatures; ++f) {
+    t.x.i[f] = av_sel(act, ev.c.x[0].i[f], ev.c.x[1].i[f], ev.c.x[2].i[f], ev.c.x[3].i[f]);
+    t.e[f] = av_sel(act, ev.e[0][f], ev.e[1][f], ev.e[2][f], ev.e[3][f]);
+  }
+  return t;
+}
+// THE CARRIED-ENTRY RULE of the fused learner: `ev` was gathered before the TD write of `t` (+ d), so every entry
+// of it at a written (feature, index) takes the written value.
+Q_HD void av_carry(AvEval& ev, const AvTaken& t, float d) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int f = 0; f < kLtFeatures; ++f)
+      if (ev.c.x[a].i[f] == t.x.i[f]) ev.e[a][f] = t.e[f] + d;
+}
+// d of the TD step: `live` = the next state is not terminal (not done, and it has a move)
+Q_HD float av_delta(float v_x, float best_next, bool live, double lr, double gamma) {
+  Q2048_NO_CONTRACT
+  const double target = (gamma * (double)best_next) * (live ? 1.0 : 0.0);
+  return (float)((lr * 0.125) * (target - (double)v_x));
+}
+
 }  // namespace q2048

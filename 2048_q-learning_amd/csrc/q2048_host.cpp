@@ -855,6 +855,22 @@ inline void lt_scatter(float* w, const LtIdx& x, const LtRows& e, int act, float
   for (int f = 0; f < kLtFeatures; ++f) st_f32(rt_entry(w, f, x.i[f]) + act, row_get(e.e[f], act) + d);
 }
 
+// ---- afterstate value learner on the line features: V = float[8][65536] -------------------------------------------
+inline float* av_entry(float* v, int f, uint32_t idx) { return v + ((size_t)f * kRtIdx + idx); }
+inline AvEval av_eval(const float* v, const Board& s) {
+  AvEval ev;
+  ev.c = av_candidates(s);
+  for (int a = 0; a < 4; ++a)
+    for (int f = 0; f < kLtFeatures; ++f) ev.e[a][f] = ld_f32(av_entry(const_cast<float*>(v), f, ev.c.x[a].i[f]));
+  return ev;
+}
+inline void av_gather8(const float* v, AvTaken& t) {
+  for (int f = 0; f < kLtFeatures; ++f) t.e[f] = ld_f32(av_entry(const_cast<float*>(v), f, t.x.i[f]));
+}
+inline void av_scatter(float* v, const AvTaken& t, float d) {
+  for (int f = 0; f < kLtFeatures; ++f) st_f32(av_entry(v, f, t.x.i[f]), t.e[f] + d);
+}
+
 // ---- bulk moves of rows into a table (import, merge, fold, unfold) ----------------------------------------------
 // the one- or two-word key of a table, as the type the probes are compiled for: f(Geo<4>::Key) or f(Geo<5>::Key)
 template <class F>
@@ -1678,6 +1694,175 @@ int q2048_lt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights,
         const Row q = lt_q(lt_gather(weights, lt_indices(b)));
         bool explored;
         const int act = play_action(legal_mask(b), q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
+        const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+        st.i[Q2048_ST_VALID] += o.valid != 0;
+        st.i[Q2048_ST_EXPLORE] += explored;
+        reward_sum += (double)o.reward;
+        if (o.done) {
+          st.i[Q2048_ST_EPISODES] += 1;
+          st.episode(a, o.max_log2);
+          begin_episode(b, a, seed, id, (env & kEnvResetShaping) != 0);
+        }
+      }
+      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
+      st.f[Q2048_SF_REWARD] += reward_sum;
+      store_board(boards, i, b);
+      st_aux(aux, i, a);
+    }
+  });
+  stats_merge(parts, used, stats_i, stats_f);
+  return Q2048_OK;
+}
+
+// ---- the afterstate value family: one evaluation = the four moved boards and their 32 entries ----
+int q2048_av_value(const float* weights, const uint8_t* boards, int64_t B, float* v_out, void*) {
+  if (int e = check_av_value(weights, boards, B, v_out)) return e;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Board b;
+      load_board(boards, i, b);
+      AvTaken t;
+      t.x = lt_indices(b);
+      av_gather8(weights, t);
+      v_out[i] = av_v(t.e);
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_av_lookup(const float* weights, const uint8_t* boards, int64_t B, float* q_out, void*) {
+  if (int e = check_av_lookup(weights, boards, B, q_out)) return e;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Board b;
+      load_board(boards, i, b);
+      const Row q = av_row(av_eval(weights, b));
+      q_out[4 * i] = q.q0; q_out[4 * i + 1] = q.q1; q_out[4 * i + 2] = q.q2; q_out[4 * i + 3] = q.q3;
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_av_choose(const float* weights, const uint8_t* boards, int64_t B, double eps, uint64_t seed, uint64_t env_id0,
+                    uint32_t ctr, uint8_t* actions, void*) {
+  if (int e = check_av_choose(weights, boards, B, eps, actions)) return e;
+  const uint64_t eps_t = eps_threshold(eps);
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Board b;
+      load_board(boards, i, b);
+      const Draws x = draws(seed, env_id0 + (uint64_t)i, ctr, kStreamStep);
+      const AvEval ev = av_eval(weights, b);
+      const Row q = av_row(ev);
+      bool explored;
+      actions[i] = (uint8_t)play_action(ev.c.legal, q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_av_update(float* weights, const uint8_t* boards_s, const uint8_t* actions, const uint8_t* boards_s2,
+                    const uint8_t* done, int64_t B, double lr, double gamma, uint32_t* status, void*) {
+  if (int e = check_av_update(weights, boards_s, actions, boards_s2, done, B, lr, gamma, status)) return e;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      const int act = actions[i];
+      if (act > 3) { status_or(status, Q2048_STATUS_BAD_ACTION); continue; }
+      Board b_s, b_st, b_n;
+      load_board(boards_s, i, b_s);
+      load_board(boards_s2, i, b_n);
+      uint32_t score;
+      if (!move_with_transpose(b_s, b_st, act, score)) continue;   // the step on which the env reports the end
+      const AvEval en = av_eval(weights, b_n);
+      AvTaken t;
+      t.x = lt_indices_of(b_s, b_st);
+      av_gather8(weights, t);
+      const bool live = done[i] == 0 && en.c.legal != 0u;
+      av_scatter(weights, t, av_delta(av_v(t.e), av_best(en.c.legal, av_row(en)), live, lr, gamma));
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_av_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, int64_t B, int64_t steps, double eps,
+                           double lr, double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i,
+                           double* stats_f, uint32_t* status, void*) {
+  if (int e = check_av_fused(boards, aux, weights, B, steps, eps, lr, gamma, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  const uint64_t eps_t = eps_threshold(eps);
+  const int T = threads_for(B);
+  std::vector<Stats> parts((size_t)T);
+  Stats* sp = parts.data();
+  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+    Stats& st = sp[tid];
+    for (int64_t i = lo; i < hi; ++i) {
+      const uint64_t id = env_id0 + (uint64_t)i;
+      Board b;
+      load_board(boards, i, b);
+      Aux a = ld_aux(aux, i);
+      double reward_sum = 0.0;
+      AvEval ev = av_eval(weights, b);
+      for (int64_t t = 0; t < steps; ++t) {
+        const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+        const Row q = av_row(ev);
+        bool explored;
+        const int act = play_action(ev.c.legal, q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
+        const bool legal = ((ev.c.legal >> act) & 1u) != 0u;
+        const AvTaken tk = av_taken(ev, act);
+        const StepOut o = env_step(b, a, act, x.x2, x.x3);
+        AvEval en = av_eval(weights, b);
+        float d = 0.0f;
+        if (legal) {
+          const bool live = o.done == 0 && en.c.legal != 0u;
+          d = av_delta(av_v(tk.e), av_best(en.c.legal, av_row(en)), live, lr, gamma);
+          av_scatter(weights, tk, d);
+        }
+        st.i[Q2048_ST_VALID] += o.valid != 0;
+        st.i[Q2048_ST_EXPLORE] += explored;
+        reward_sum += (double)o.reward;
+        if (o.done) {
+          st.i[Q2048_ST_EPISODES] += 1;
+          st.episode(a, o.max_log2);
+          begin_episode(b, a, seed, id);
+          ev = av_eval(weights, b);
+        } else {
+          if (legal) av_carry(en, tk, d);
+          ev = en;
+        }
+      }
+      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
+      st.f[Q2048_SF_REWARD] += reward_sum;
+      store_board(boards, i, b);
+      st_aux(aux, i, a);
+    }
+  });
+  stats_merge(parts, used, stats_i, stats_f);
+  return Q2048_OK;
+}
+int q2048_av_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
+                          uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                          double* stats_f, uint32_t* status, void*) {
+  if (int e = check_av_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  const uint64_t eps_t = eps_threshold(eps);
+  const ImageLuts lut{&g_lut_image};
+  const int env = env_bits(flags);
+  const int T = threads_for(B);
+  std::vector<Stats> parts((size_t)T);
+  Stats* sp = parts.data();
+  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+    Stats& st = sp[tid];
+    for (int64_t i = lo; i < hi; ++i) {
+      const uint64_t id = env_id0 + (uint64_t)i;
+      Board b;
+      load_board(boards, i, b);
+      Aux a = ld_aux(aux, i);
+      const DrawPrep prep = draws_prepare(seed, id, kStreamStep);
+      double reward_sum = 0.0;
+      for (int64_t t = 0; t < steps; ++t) {
+        const Draws x = draws_at(prep, ctr0 + (uint32_t)t);
+        Draws y{0u, 0u, 0u, 0u};
+        if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+        const AvEval ev = av_eval(weights, b);
+        const Row q = av_row(ev);
+        bool explored;
+        const int act = play_action(ev.c.legal, q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
         const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
         st.i[Q2048_ST_VALID] += o.valid != 0;
         st.i[Q2048_ST_EXPLORE] += explored;

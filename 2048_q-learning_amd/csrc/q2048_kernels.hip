@@ -2264,6 +2264,204 @@ __global__ __launch_bounds__(kBlock) void k_lt_play_rollout(
 }
 
 // ---------------------------------------------------------------------------------------------
+// afterstate value learner on the line features (q2048_av_*): V = float[8][65536], 2 MiB, inside
+// one XCD's L2.  One evaluation of a state = the four moved boards (move_with_transpose: the
+// moved board and its transpose both come out of the slide, so the 32 indices cost no transpose
+// beyond the one of s) and 32 four-byte loads, issued back to back and waited for once.  The
+// loads are written in plain C++ -- relaxed agent-scope atomic loads in the learner kernels
+// (another CU's stores must be seen: the compiler emits sc1 loads), ordinary loads in the player
+// -- because one asm block would need 64 operands.  No load is predicated on its move being
+// legal: all 32 are always issued.  A write stores gathered + d with a plain 4-byte store, the
+// last writer wins.  Kernels of their own; no existing kernel changes.
+// ---------------------------------------------------------------------------------------------
+template <bool AGENT>
+__device__ __forceinline__ float av_ld(const float* v, int f, uint32_t idx) {
+  const float* p = v + ((uint32_t)f * kRtIdx + idx);
+  if constexpr (AGENT) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else return *p;
+}
+template <bool AGENT>
+__device__ __forceinline__ AvEval av_eval(const float* v, const Board& s) {
+  AvEval ev;
+  ev.c = av_candidates(s);
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int f = 0; f < kLtFeatures; ++f) ev.e[a][f] = av_ld<AGENT>(v, f, ev.c.x[a].i[f]);
+  return ev;
+}
+__device__ __forceinline__ void av_gather8(const float* v, AvTaken& t) {
+#pragma unroll
+  for (int f = 0; f < kLtFeatures; ++f) t.e[f] = av_ld<true>(v, f, t.x.i[f]);
+}
+__device__ __forceinline__ void av_scatter(float* v, const AvTaken& t, float d) {
+#pragma unroll
+  for (int f = 0; f < kLtFeatures; ++f) v[(uint32_t)f * kRtIdx + t.x.i[f]] = t.e[f] + d;
+}
+
+__global__ __launch_bounds__(kBlock) void k_av_value(const float* w, const uint8_t* boards, int64_t B, float* v_out) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  AvTaken t;
+  t.x = lt_indices(load_board(boards, i, B, st));
+  av_gather8(w, t);
+  v_out[i] = av_v(t.e);
+}
+
+__global__ __launch_bounds__(kBlock) void k_av_lookup(const float* w, const uint8_t* boards, int64_t B, float* q_out) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const Row q = av_row(av_eval<true>(w, load_board(boards, i, B, st)));
+  reinterpret_cast<float4*>(q_out)[i] = make_float4(q.q0, q.q1, q.q2, q.q3);
+}
+
+__global__ __launch_bounds__(kBlock) void k_av_choose(const float* w, const uint8_t* boards, int64_t B, double eps,
+                                                      uint64_t seed, uint64_t env_id0, uint32_t ctr, uint8_t* actions) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const Board b = load_board(boards, i, B, st);
+  const Draws x = draws(seed, env_id0 + (uint64_t)i, ctr, kStreamStep);
+  const AvEval ev = av_eval<true>(w, b);
+  const Row q = av_row(ev);
+  bool explored;
+  actions[i] = (uint8_t)play_action(ev.c.legal, q.q0, q.q1, q.q2, q.q3, eps_threshold(eps), x.x0, x.x1, explored);
+}
+
+__global__ __launch_bounds__(kBlock) void k_av_update(float* w, const uint8_t* s, const uint8_t* actions, const uint8_t* s2,
+                                                      const uint8_t* done, int64_t B, double lr, double gamma,
+                                                      uint32_t* status) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const int act = actions[i];
+  if (act > 3) { atomicOr(status, Q2048_STATUS_BAD_ACTION); return; }
+  Board b_s = load_board(s, i, B, st), b_st;
+  const Board b_n = load_board(s2, i, B, st);
+  uint32_t score;
+  if (!move_with_transpose(b_s, b_st, act, score)) return;   // the step on which the env reports the end
+  const AvEval en = av_eval<true>(w, b_n);
+  AvTaken t;
+  t.x = lt_indices_of(b_s, b_st);
+  av_gather8(w, t);
+  const bool live = done[i] == 0 && en.c.legal != 0u;
+  av_scatter(w, t, av_delta(av_v(t.e), av_best(en.c.legal, av_row(en)), live, lr, gamma));
+}
+
+__global__ __launch_bounds__(kBlock) void k_av_fused_rollout(
+    uint8_t* boards, q2048_aux* aux, float* w, int64_t B, int steps, double eps, double lr,
+    double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f,
+    uint32_t* /*status: as on k_rt_fused_rollout, nothing data-dependent can go wrong on this path*/) {
+  __shared__ BlockStats bs;
+  stats_clear(bs);
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < B) {
+    Stage<4> st;
+    const uint64_t id = env_id0 + (uint64_t)i;
+    Board b = load_board(boards, i, B, st);
+    Aux a = ld_aux(aux, i);
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
+    double reward_sum = 0.0;
+    const uint64_t eps_t = eps_threshold(eps);
+    AvEval ev = av_eval<true>(w, b);   // the evaluation of the current state, carried from step to step
+    for (int t = 0; t < steps; ++t) {
+      const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+      const Row q = av_row(ev);
+      bool explored;
+      const int act = play_action(ev.c.legal, q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
+      const bool legal = ((ev.c.legal >> act) & 1u) != 0u;
+      const AvTaken tk = av_taken(ev, act);
+      const StepOut o = env_step(b, a, act, x.x2, x.x3);
+      AvEval en = av_eval<true>(w, b);
+      const bool live = o.done == 0 && en.c.legal != 0u;
+      const float d = av_delta(av_v(tk.e), av_best(en.c.legal, av_row(en)), live, lr, gamma);
+      if (legal) av_scatter(w, tk, d);
+      n_valid += wave_count(o.valid != 0);
+      n_explore += wave_count(explored);
+      n_done += wave_count(o.done != 0);
+      reward_sum += (double)o.reward;
+      if (o.done) {
+        episode_stats(bs, a, o.max_log2);
+        begin_episode(b, a, seed, id);
+        ev = av_eval<true>(w, b);
+      } else {
+        // s' becomes s: its 32 entries were gathered before the write above, so each of them at a written
+        // (feature, index) takes the written value (av_carry)
+        if (legal) av_carry(en, tk, d);
+        ev = en;
+      }
+    }
+    store_board(boards, i, B, b, st);
+    st_aux(aux, i, a);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+    const uint32_t n_active = wave_count(true);
+    if (wave_leader()) {
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  stats_flush(bs, stats_i, stats_f);
+}
+
+// the greedy player on afterstate values (q2048_av_play_rollout): k_lt_play_rollout with q2048_av_lookup's row
+template <int ENV>
+__global__ __launch_bounds__(kBlock) void k_av_play_rollout(
+    uint8_t* boards, q2048_aux* aux, const float* w, int64_t B, int steps, double eps, uint64_t seed,
+    uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
+  __shared__ BlockStats bs;
+  __shared__ Stage<4> st;
+  __shared__ LutImage lut_lds;
+  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
+  if (threadIdx.x < kLutImageDoubles)
+    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
+  stats_clear(bs);                                        // (its barrier publishes the image too)
+  const ImageLuts lut{&lut_lds};
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  Board b = load_board(boards, i, B, st);
+  if (i < B) {
+    const uint64_t id = env_id0 + (uint64_t)i;
+    Aux a = ld_aux(aux, i);
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
+    double reward_sum = 0.0;
+    const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
+    const uint64_t eps_t = eps_threshold(eps);
+    for (int t = 0; t < steps; ++t) {
+      const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
+      Draws y{0u, 0u, 0u, 0u};
+      if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+      const AvEval ev = av_eval<false>(w, b);
+      const Row q = av_row(ev);
+      bool explored;
+      const int act = play_action(ev.c.legal, q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
+      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+      if (o.done) {
+        episode_stats(bs, a, o.max_log2);
+        begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
+      }
+      n_valid += wave_count(o.valid != 0);
+      n_explore += wave_count(explored);
+      n_done += wave_count(o.done != 0);
+      reward_sum += (double)o.reward;
+    }
+    st_aux(aux, i, a);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+    const uint32_t n_active = wave_count(true);
+    if (wave_leader()) {
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  store_board(boards, i, B, b, st);
+  stats_flush(bs, stats_i, stats_f);
+}
+
+// ---------------------------------------------------------------------------------------------
 // table utilities
 // ---------------------------------------------------------------------------------------------
 // Streams the whole table once, in tiles of 16 Ki slots per block: a lane reads the first 16 bytes
@@ -3299,6 +3497,65 @@ int q2048_lt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights,
     break;
   switch (env_bits(flags) & 3) { Q2048_LAUNCH_LT_PLAY(0) Q2048_LAUNCH_LT_PLAY(1) Q2048_LAUNCH_LT_PLAY(2) Q2048_LAUNCH_LT_PLAY(3) }
 #undef Q2048_LAUNCH_LT_PLAY
+  return launch_status();
+}
+
+int q2048_av_value(const float* weights, const uint8_t* boards, int64_t B, float* v_out, void* stream) {
+  if (int e = check_av_value(weights, boards, B, v_out)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_av_value, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights, boards, B, v_out);
+  return launch_status();
+}
+
+int q2048_av_lookup(const float* weights, const uint8_t* boards, int64_t B, float* q_out, void* stream) {
+  if (int e = check_av_lookup(weights, boards, B, q_out)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_av_lookup, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights, boards, B, q_out);
+  return launch_status();
+}
+
+int q2048_av_choose(const float* weights, const uint8_t* boards, int64_t B, double eps, uint64_t seed,
+                    uint64_t env_id0, uint32_t ctr, uint8_t* actions, void* stream) {
+  if (int e = check_av_choose(weights, boards, B, eps, actions)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_av_choose, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights,
+                     boards, B, eps, seed, env_id0, ctr, actions);
+  return launch_status();
+}
+
+int q2048_av_update(float* weights, const uint8_t* boards_s, const uint8_t* actions, const uint8_t* boards_s2,
+                    const uint8_t* done, int64_t B, double lr, double gamma, uint32_t* status, void* stream) {
+  if (int e = check_av_update(weights, boards_s, actions, boards_s2, done, B, lr, gamma, status)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_av_update, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights,
+                     boards_s, actions, boards_s2, done, B, lr, gamma, status);
+  return launch_status();
+}
+
+int q2048_av_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, int64_t B, int64_t steps,
+                           double eps, double lr, double gamma, uint64_t seed, uint64_t env_id0,
+                           uint32_t ctr0, int64_t* stats_i, double* stats_f, uint32_t* status,
+                           void* stream) {
+  if (int e = check_av_fused(boards, aux, weights, B, steps, eps, lr, gamma, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_av_fused_rollout, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream,
+                     boards, aux, weights, B, (int)steps, eps, lr, gamma, seed, env_id0, ctr0, stats_i,
+                     stats_f, status);
+  return launch_status();
+}
+
+int q2048_av_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
+                          uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                          double* stats_f, uint32_t* status, void* stream) {
+  if (int e = check_av_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+#define Q2048_LAUNCH_AV_PLAY(E)                                                                                    \
+  case E:                                                                                                          \
+    hipLaunchKernelGGL((k_av_play_rollout<E>), dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, boards,    \
+                       aux, weights, B, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);                   \
+    break;
+  switch (env_bits(flags) & 3) { Q2048_LAUNCH_AV_PLAY(0) Q2048_LAUNCH_AV_PLAY(1) Q2048_LAUNCH_AV_PLAY(2) Q2048_LAUNCH_AV_PLAY(3) }
+#undef Q2048_LAUNCH_AV_PLAY
   return launch_status();
 }
 

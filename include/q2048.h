@@ -69,7 +69,8 @@ extern "C" {
                                q2048_table_unfold (into and out of a folded table) likewise, each by its symbol;
                                q2048_rt_play_rollout (the greedy player on row-tuple weights) too, by its symbol;
                                the line-tuple family q2048_lt_* (rows and columns as features) by the symbol
-                               q2048_lt_lookup */
+                               q2048_lt_lookup; the afterstate value family q2048_av_* by the symbol
+                               q2048_av_lookup */
 
 /* return codes */
 #define Q2048_OK 0
@@ -811,6 +812,56 @@ int q2048_lt_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weights, int6
                            uint64_t env_id0, uint32_t ctr0, int64_t *stats_i, double *stats_f,
                            uint32_t *status, void *stream);
 int q2048_lt_play_rollout(uint8_t *boards, q2048_aux *aux, const float *weights, int64_t B, int64_t steps,
+                          double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
+                          int64_t *stats_i, double *stats_f, uint32_t *status, void *stream);
+
+/* ---- afterstate value learner on the line features ---------------------------------------------------------------
+ * A third weights family, 4x4 boards only: one VALUE per line entry instead of a Q value per (entry, action), and a
+ * state is judged by the four boards its moves lead to before the spawn (the afterstates).
+ *   weights   V = float[8][65536] (2 MiB, 16-byte aligned, zero = untrained); feature f is indexed exactly as in the
+ *             line-tuple family above (rows 0..3, columns 0..3 from the top, low nibbles; a cell >= 16 aliases).
+ *   value     v(x) = ((V[0][i0] + V[1][i1]) + (V[2][i2] + V[3][i3])) + ((V[4][i4] + V[5][i5]) + (V[6][i6] + V[7][i7])),
+ *             float32 with exactly that association.
+ *   evaluation of a state s, for a = 0..3 (0 left, 1 up, 2 right, 3 down): c_a = s moved by a WITHOUT the spawn,
+ *             score_a its merge score, legal_a = the move changes the board; q_a = (float)score_a + v(c_a), one
+ *             float32 addition.  A move that does not change the board gives 0 + v(s); there is no special case.
+ *   has_move(s) = any legal_a.  best(s) = q_a at the first maximum over the legal moves (strict >, ascending a);
+ *             0.0f if there is no legal move.
+ *   choice    in EVERY entry point of the family the player's draw contract: greedy = that first maximum over the
+ *             legal moves; exploring (x0 below epsilon's threshold, and a legal move exists) = the k-th legal move,
+ *             k = (x1 * n_legal) >> 32; no legal move = action 0, not counted as explored.  (Not the unmasked
+ *             epsilon-greedy of q2048_lt_choose: an afterstate learner can only learn from moves that change the board.)
+ *   TD step   for a transition (s, a, s2, done): x = c_a(s).  If a is not legal in s nothing is written (no error:
+ *             it is the step on which the env reports the end of the game).  Otherwise
+ *             live = (!done && has_move(s2)) ? 1.0 : 0.0;  target = (gamma * (double)best(s2)) * live;
+ *             d = (float)((lr * 0.125) * (target - (double)v(x))), rounded once; each V[f][idx_f(x)] is written as
+ *             (the value this lane gathered) + d: a plain 4-byte store, the last writer wins.  The reward of (s, a)
+ *             does not enter: v(x) estimates what comes AFTER the move, and the learner's reward is the merge score
+ *             of the next move, inside best(s2).  The env's shaped reward still goes into aux and the statistics.
+ *   fused     q2048_av_fused_rollout, per lane and step: evaluate s (carried from the previous step), choose with
+ *             x0, x1, env step with x2, x3 (default profile, no flags), evaluate s', TD step on c_act with best(s'),
+ *             on done statistics + reset + evaluate the new board; otherwise the evaluation of s' is carried, and
+ *             every entry of it at a (feature, index) the TD step wrote takes the written value -- so B = 1 is
+ *             exactly the four-call loop.  Q2048_ST_EXPLORE counts the steps the choice reports as explored.
+ *   player    q2048_av_play_rollout: q2048_lt_play_rollout with the row q_a; weights are only read;
+ *             Q2048_FLAG_ENV_DQN and Q2048_FLAG_RESET_SHAPING as there.
+ * Argument lists: q2048_av_lookup / _choose / _fused_rollout / _play_rollout have those of their q2048_lt_*
+ * counterparts, q2048_av_value that of the lookup with v_out[B], q2048_av_update that of q2048_lt_update without
+ * `reward`.  Checks, their order and the codes are the counterparts'; a refused call writes nothing; B == 0 or
+ * steps == 0 is Q2048_OK.  q2048_av_update: an action > 3 sets Q2048_STATUS_BAD_ACTION and skips the lane. */
+int q2048_av_value(const float *weights, const uint8_t *boards, int64_t B, float *v_out, void *stream);
+int q2048_av_lookup(const float *weights, const uint8_t *boards, int64_t B, float *q_out,
+                    void *stream);
+int q2048_av_choose(const float *weights, const uint8_t *boards, int64_t B, double eps,
+                    uint64_t seed, uint64_t env_id0, uint32_t ctr, uint8_t *actions, void *stream);
+int q2048_av_update(float *weights, const uint8_t *boards_s, const uint8_t *actions,
+                    const uint8_t *boards_s2, const uint8_t *done, int64_t B,
+                    double lr, double gamma, uint32_t *status, void *stream);
+int q2048_av_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weights, int64_t B,
+                           int64_t steps, double eps, double lr, double gamma, uint64_t seed,
+                           uint64_t env_id0, uint32_t ctr0, int64_t *stats_i, double *stats_f,
+                           uint32_t *status, void *stream);
+int q2048_av_play_rollout(uint8_t *boards, q2048_aux *aux, const float *weights, int64_t B, int64_t steps,
                           double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
                           int64_t *stats_i, double *stats_f, uint32_t *status, void *stream);
 
