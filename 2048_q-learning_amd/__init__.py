@@ -13,7 +13,7 @@ per-lane arithmetic -- exists only for callers that ask for it by name.
 """
 from . import _native
 from ._native import NativeError, build
-from .agent import (EPISODE_DTYPE, BatchedAfterstateAgent, BatchedLineTupleAgent, BatchedQLearningAgent, BatchedRowTupleAgent, EpisodeLog,
+from .agent import (EPISODE_DTYPE, BatchedAfterstateAgent, BatchedLineTupleAgent, BatchedNTupleAgent, BatchedQLearningAgent, BatchedRowTupleAgent, EpisodeLog,
                     EpsilonSchedule, QLearningAgent, auto_capacity_log2, place_table,
                     stats_dict)
 from . import launch
@@ -22,7 +22,7 @@ from .summary import SUMMARY_HEADER, summarize_csv, summarize_episodes, summariz
 from .env import (AUX_DTYPE, BatchedGame2048Env, Game2048_env, boards_to_raw, raw_to_boards)
 
 __all__ = [
-    "BatchedGame2048Env", "Game2048_env", "BatchedQLearningAgent", "BatchedRowTupleAgent", "BatchedLineTupleAgent", "BatchedAfterstateAgent",
+    "BatchedGame2048Env", "Game2048_env", "BatchedQLearningAgent", "BatchedRowTupleAgent", "BatchedLineTupleAgent", "BatchedAfterstateAgent", "BatchedNTupleAgent",
     "QLearningAgent",
     "EpsilonSchedule", "EpisodeLog", "EPISODE_DTYPE", "stats_dict", "Shard", "shard_plan", "weak_shard", "allreduce_stats", "StatsAllReduce", "launch",
     "boards_to_raw", "raw_to_boards", "AUX_DTYPE", "build", "NativeError", "place_table", "auto_capacity_log2",

@@ -1139,6 +1139,9 @@ class BatchedQLearningAgent:
         if sd.get("kind") == "line_afterstate":
             raise ValueError("this checkpoint holds afterstate values (BatchedAfterstateAgent), not a hash table: the "
                              "two kinds do not load into each other")
+        if sd.get("kind") == "ntuple6_afterstate":
+            raise ValueError("this checkpoint holds a 6-tuple afterstate network (BatchedNTupleAgent), not a hash "
+                             "table: the two kinds do not load into each other")
         if sd["board_size"] != self.board_size:
             raise ValueError("checkpoint was taken with another board size")
         if bool(sd.get("symmetric", False)) != self.symmetric:
@@ -1655,7 +1658,8 @@ class BatchedLineTupleAgent(BatchedRowTupleAgent):
         if sd.get("kind") != kind:
             held = {"row_tuple": "row-tuple weights (BatchedRowTupleAgent; `load_row_tuple` promotes them)",
                     "line_tuple": "line-tuple weights (BatchedLineTupleAgent)",
-                    "line_afterstate": "afterstate values (BatchedAfterstateAgent)"}.get(
+                    "line_afterstate": "afterstate values (BatchedAfterstateAgent)",
+                    "ntuple6_afterstate": "a 6-tuple afterstate network (BatchedNTupleAgent)"}.get(
                         sd.get("kind"), "a hash table (BatchedQLearningAgent)")
             raise ValueError(f"this checkpoint holds {held}, not {kind.replace('_', '-')} weights: the kinds do not "
                              "load into each other")
@@ -1708,15 +1712,22 @@ class BatchedAfterstateAgent(BatchedLineTupleAgent):
                  env_id0: int = 0):
         super().__init__(total_epochs, action_space, learning_rate, discount_factor, exploration_rate,
                          exploration_min, device, seed, env_id0)
-        self.weights = torch.zeros((self.N_FEATURES, 65536), dtype=torch.float32, device=self.device)
+        self.weights = torch.zeros(self._SHAPE, dtype=torch.float32, device=self.device)
+
+    # what tells this family from the one that inherits its surface (BatchedNTupleAgent): the entry points' prefix,
+    # the weights' shape, the checkpoint's kind and the words of a refusal
+    _FAMILY, _SHAPE, _KIND, _WHAT = "av", (8, 65536), "line_afterstate", "afterstate values"
+
+    def _fn(self, name: str):
+        return getattr(self._L, f"q2048_{self._FAMILY}_{name}")
 
     def choose_action(self, boards) -> torch.Tensor:
         boards = self._boards(boards)
         B = boards.shape[0]
         actions = torch.empty(B, dtype=torch.uint8, device=self.device)
-        N.check(self._L.q2048_av_choose(_ptr(self.weights), _ptr(boards), B, float(self.epsilon),
+        N.check(self._fn("choose")(_ptr(self.weights), _ptr(boards), B, float(self.epsilon),
                                         self.seed, self.env_id0, self.ctr & 0xFFFFFFFF, _ptr(actions),
-                                        _stream(self.device)), "av_choose")
+                                        _stream(self.device)), self._FAMILY + "_choose")
         self.ctr += 1
         return actions
 
@@ -1730,24 +1741,24 @@ class BatchedAfterstateAgent(BatchedLineTupleAgent):
         actions, done = vec(actions, torch.uint8), vec(done, torch.uint8)
         if not (actions.shape == tuple(torch.as_tensor(reward).shape) == done.shape == (B,)):
             raise ValueError("actions / reward / done must have shape (B,)")
-        N.check(self._L.q2048_av_update(_ptr(self.weights), _ptr(boards), _ptr(actions), _ptr(next_boards),
+        N.check(self._fn("update")(_ptr(self.weights), _ptr(boards), _ptr(actions), _ptr(next_boards),
                                         _ptr(done), B, float(self.lr), float(self.gamma), _ptr(self.status),
-                                        _stream(self.device)), "av_update")
+                                        _stream(self.device)), self._FAMILY + "_update")
 
     def q_values(self, boards) -> torch.Tensor:
         """q_a for the four actions (q2048_av_lookup): merge score + value of the moved board."""
         boards = self._boards(boards)
         q = torch.empty((boards.shape[0], 4), dtype=torch.float32, device=self.device)
-        N.check(self._L.q2048_av_lookup(_ptr(self.weights), _ptr(boards), boards.shape[0], _ptr(q),
-                                        _stream(self.device)), "av_lookup")
+        N.check(self._fn("lookup")(_ptr(self.weights), _ptr(boards), boards.shape[0], _ptr(q),
+                                        _stream(self.device)), self._FAMILY + "_lookup")
         return q
 
     def values(self, boards) -> torch.Tensor:
         """v of each board as given (q2048_av_value)."""
         boards = self._boards(boards)
         v = torch.empty((boards.shape[0],), dtype=torch.float32, device=self.device)
-        N.check(self._L.q2048_av_value(_ptr(self.weights), _ptr(boards), boards.shape[0], _ptr(v),
-                                       _stream(self.device)), "av_value")
+        N.check(self._fn("value")(_ptr(self.weights), _ptr(boards), boards.shape[0], _ptr(v),
+                                       _stream(self.device)), self._FAMILY + "_value")
         return v
 
     def fused_rollout(self, env: BatchedGame2048Env, steps: int) -> None:
@@ -1757,11 +1768,11 @@ class BatchedAfterstateAgent(BatchedLineTupleAgent):
             raise ValueError("env profiles are supported by the hash-table agent only")
         if (env.seed, env.env_id0, env.ctr) != (self.seed, self.env_id0, self.ctr):
             raise ValueError("env and agent must share seed, env_id0 and step counter")
-        N.check(self._L.q2048_av_fused_rollout(
+        N.check(self._fn("fused_rollout")(
             _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), env.num_envs, int(steps),
             float(self.epsilon), float(self.lr), float(self.gamma), self.seed, self.env_id0,
             self.ctr & 0xFFFFFFFF, _ptr(self.stats_i), _ptr(self.stats_f), _ptr(self.status),
-            _stream(self.device)), "av_fused_rollout")
+            _stream(self.device)), self._FAMILY + "_fused_rollout")
         env.ctr += int(steps)
         self.ctr += int(steps)
 
@@ -1775,31 +1786,34 @@ class BatchedAfterstateAgent(BatchedLineTupleAgent):
         if self._play_stats is None:
             self._play_stats = new_stats_vectors(self.device)
         si, sf = self._play_stats
-        N.check(self._L.q2048_av_play_rollout(
+        N.check(self._fn("play_rollout")(
             _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), env.num_envs, int(steps), float(epsilon), env.seed,
             env.env_id0, env.ctr & 0xFFFFFFFF, env.env_flags, _ptr(si), _ptr(sf), _ptr(self.status),
-            _stream(self.device)), "av_play_rollout")
+            _stream(self.device)), self._FAMILY + "_play_rollout")
         env.ctr += int(steps)
 
     def state_dict(self, compact: bool = True) -> dict:
         """`BatchedRowTupleAgent.state_dict` with "kind": "line_afterstate" and weights float32 [8, 65536]."""
         sd = BatchedRowTupleAgent.state_dict(self, compact)
-        sd["kind"] = "line_afterstate"
+        sd["kind"] = self._KIND
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
         """Everything is validated before anything of this agent, on the host or the device, is written."""
-        if sd.get("kind") != "line_afterstate":
+        if sd.get("kind") != self._KIND:
             held = {"row_tuple": "row-tuple weights (BatchedRowTupleAgent)",
-                    "line_tuple": "line-tuple weights (BatchedLineTupleAgent)"}.get(
+                    "line_tuple": "line-tuple weights (BatchedLineTupleAgent)",
+                    "line_afterstate": "afterstate values (BatchedAfterstateAgent)",
+                    "ntuple6_afterstate": "a 6-tuple afterstate network (BatchedNTupleAgent)"}.get(
                         sd.get("kind"), "a hash table (BatchedQLearningAgent)")
-            raise ValueError(f"this checkpoint holds {held}, not afterstate values: the kinds do not load into each "
-                             "other (Q entries are not afterstate values: nothing is promoted)")
+            raise ValueError(f"this checkpoint holds {held}, not {self._WHAT}: the kinds do not load into each "
+                             "other (Q entries are not afterstate values, and the two afterstate families index "
+                             "other features: nothing is promoted)")
         if int(sd["board_size"]) != 4:
-            raise ValueError("afterstate values are 4x4 only")
+            raise ValueError(f"{self._WHAT} are 4x4 only")
         w, si, sf = sd["weights"], sd["stats_i"], sd["stats_f"]
-        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or tuple(w.shape) != (self.N_FEATURES, 65536):
-            raise ValueError(f"weights must be a float32 tensor of shape ({self.N_FEATURES}, 65536), got "
+        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or tuple(w.shape) != self._SHAPE:
+            raise ValueError(f"weights must be a float32 tensor of shape {self._SHAPE}, got "
                              f"{getattr(w, 'dtype', type(w).__name__)} {tuple(getattr(w, 'shape', ()))}")
         if not isinstance(si, torch.Tensor) or si.dtype != torch.int64 or tuple(si.shape) != (N.NSTAT_I,) or \
                 not isinstance(sf, torch.Tensor) or sf.dtype != torch.float64 or tuple(sf.shape) != (N.NSTAT_F,):
@@ -1812,7 +1826,19 @@ class BatchedAfterstateAgent(BatchedLineTupleAgent):
     def load_row_tuple(self, sd: dict) -> None:
         """Refused: a row- or line-tuple file holds Q entries per action, which are not afterstate values."""
         raise ValueError("Q entries are not afterstate values: a row-tuple or line-tuple checkpoint cannot be promoted "
-                         "into a BatchedAfterstateAgent")
+                         f"into a {type(self).__name__}")
+
+
+class BatchedNTupleAgent(BatchedAfterstateAgent):
+    """The 6-TUPLE AFTERSTATE NETWORK with shared symmetric weights: V float32 [4, 16777216] (256 MiB).  Four 6-cell
+    patterns, each read on the eight images of the board (the numbering of `symmetric=True`), one table per pattern
+    shared by the eight images; v(board) = the sum of its 32 entries.  Everything else is `BatchedAfterstateAgent`
+    -- q_a = merge score + v(moved board), the player's choice in every method, the TD step (the error spread over 32
+    entries, lr / 32 each; a weight that a symmetric board reads several times moves once), `values`, the fused
+    learner and the player -- through the q2048_nt_* entry points.  A checkpoint says "kind": "ntuple6_afterstate";
+    every other kind is refused in both directions, and nothing is promoted."""
+
+    _FAMILY, _SHAPE, _KIND, _WHAT = "nt", (4, 1 << 24), "ntuple6_afterstate", "a 6-tuple afterstate network"
 
 
 def new_stats_vectors(device):

@@ -130,6 +130,29 @@ static inline int check_av_play(const void* boards, const void* aux, const void*
   return check_rt_play(boards, aux, weights, B, steps, eps, flags, status);
 }
 
+// The 6-tuple afterstate network (q2048_nt_*): the checks of the q2048_av_* counterparts, in their order, with their codes.
+static inline int check_nt_value(const void* weights, const void* boards, int64_t B, const void* v_out) {
+  return check_av_value(weights, boards, B, v_out);
+}
+static inline int check_nt_lookup(const void* weights, const void* boards, int64_t B, const void* q_out) {
+  return check_av_lookup(weights, boards, B, q_out);
+}
+static inline int check_nt_choose(const void* weights, const void* boards, int64_t B, double eps, const void* actions) {
+  return check_av_choose(weights, boards, B, eps, actions);
+}
+static inline int check_nt_update(const void* weights, const void* boards_s, const void* actions, const void* boards_s2,
+                                  const void* done, int64_t B, double lr, double gamma, const void* status) {
+  return check_av_update(weights, boards_s, actions, boards_s2, done, B, lr, gamma, status);
+}
+static inline int check_nt_fused(const void* boards, const void* aux, const void* weights, int64_t B, int64_t steps,
+                                 double eps, double lr, double gamma, const void* status) {
+  return check_av_fused(boards, aux, weights, B, steps, eps, lr, gamma, status);
+}
+static inline int check_nt_play(const void* boards, const void* aux, const void* weights, int64_t B, int64_t steps,
+                                double eps, uint32_t flags, const void* status) {
+  return check_av_play(boards, aux, weights, B, steps, eps, flags, status);
+}
+
 // q2048_strerror
 static inline const char* error_text(int code) {
   switch (code) {

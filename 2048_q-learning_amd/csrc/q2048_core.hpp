@@ -1083,4 +1083,97 @@ Q_HD float av_delta(float v_x, float best_next, bool live, double lr, double gam
   return (float)((lr * 0.125) * (target - (double)v_x));
 }
 
+// ------------------------------------------------------------------------------------------
+// 6-tuple afterstate network with shared symmetric weights (q2048_nt_*): V = float[4][2^24], 256 MiB.  Four 6-cell
+// patterns (cell index 4r + c), each read on the eight images of the board (key_images: the numbering of
+// Q2048_FLAG_SYMMETRIC), one table per pattern shared by the eight images:
+//   P0 = {0,1,2,3,4,5}   P1 = {4,5,6,7,8,9}   P2 = {0,1,2,4,5,6}   P3 = {4,5,6,8,9,10}
+//   idx[p][g](x) = sum_k (img_g(x).flat[P_p[k]] & 15) << 4k;  e[p][g] = V[p][idx[p][g](x)];
+//   v(x) = rt_sum(s_0, s_1, s_2, s_3), s_p = lt_sum(e[p][0..7]).
+// Everything else -- candidates, q_a, best, the choice, live and target of the TD step -- is the afterstate
+// family's, by calling it.  The two libraries hand in how an entry is loaded and stored (`ld(p, idx)`,
+// `st(p, idx, value)`); what is loaded, in which order it is summed and what is stored is written here once.
+// ------------------------------------------------------------------------------------------
+constexpr uint32_t kNtIdx = 1u << 24;   // entries per pattern table
+constexpr int kNtPatterns = 4, kNtImages = 8;
+// The four indices of an image from its packed key (cell 4r + c in nibble 4r + c): P0 is the low six nibbles, P1
+// the same one row down, P2 three nibbles of row 0 and three of row 1, P3 the same one row down.
+Q_HD uint32_t nt_index(uint64_t key, int p) {
+  const uint32_t k = (uint32_t)((p & 1) ? (key >> 16) : key), k1 = (uint32_t)(key >> ((p & 1) ? 32 : 16));
+  return (p & 2) ? ((k & 0xfffu) | ((k1 & 0xfffu) << 12)) : (k & 0xffffffu);
+}
+struct NtIdx { uint32_t i[kNtPatterns][kNtImages]; };
+Q_HD NtIdx nt_indices(const Board& x) {
+  bool overflow;                                  // a cell >= 16 aliases by its low nibble, as in the other families
+  uint64_t img[kNtImages];
+  key_images(pack_key(x, overflow), img);
+  NtIdx ix;
+#pragma unroll
+  for (int p = 0; p < kNtPatterns; ++p)
+#pragma unroll
+    for (int g = 0; g < kNtImages; ++g) ix.i[p][g] = nt_index(img[g], p);
+  return ix;
+}
+struct NtEntries { float e[kNtPatterns][kNtImages]; };
+// all 32 entries of a board, loaded back to back: nothing between two loads but the next address
+template <class Ld>
+Q_HD NtEntries nt_gather(const NtIdx& ix, Ld ld) {
+  NtEntries n;
+#pragma unroll
+  for (int p = 0; p < kNtPatterns; ++p)
+#pragma unroll
+    for (int g = 0; g < kNtImages; ++g) n.e[p][g] = ld(p, ix.i[p][g]);
+  return n;
+}
+Q_HD float nt_v(const NtEntries& n) {
+  float s[kNtPatterns];
+#pragma unroll
+  for (int p = 0; p < kNtPatterns; ++p)
+    s[p] = lt_sum(n.e[p][0], n.e[p][1], n.e[p][2], n.e[p][3], n.e[p][4], n.e[p][5], n.e[p][6], n.e[p][7]);
+  return rt_sum(s[0], s[1], s[2], s[3]);
+}
+// One evaluation of a state: each candidate's 32 entries are reduced to its q as they arrive, so what is held is a
+// Row and the mask of the moves that change the board -- nothing is carried from step to step.  The four candidates
+// are a LOOP, not four copies: unrolled, hipcc keeps the 128 entries of an evaluation and their addresses alive
+// together (it sinks the sums below the last load), which takes every VGPR there is and spills; as a loop a lane has
+// 32 loads in flight, the other waves of the SIMD fill the wait, and the code is a quarter as long.  (The selects:
+// an array indexed by the loop counter would live in scratch memory.)
+struct NtEval { Row q; uint32_t legal; };
+template <class Ld>
+Q_HD NtEval nt_eval(const Board& s, Ld ld) {
+  NtEval ev{Row{0.0f, 0.0f, 0.0f, 0.0f}, 0u};
+#pragma unroll 1
+  for (int a = 0; a < 4; ++a) {
+    Board m = s;
+    uint32_t score;
+    ev.legal |= (uint32_t)move(m, a, score) << a;
+    const float q = av_q(score, nt_v(nt_gather(nt_indices(m), ld)));
+    ev.q.q0 = a == 0 ? q : ev.q.q0;
+    ev.q.q1 = a == 1 ? q : ev.q.q1;
+    ev.q.q2 = a == 2 ? q : ev.q.q2;
+    ev.q.q3 = a == 3 ? q : ev.q.q3;
+  }
+  return ev;
+}
+// d of the TD step: av_delta's live and target, the error spread over the 32 entries
+Q_HD float nt_delta(float v_x, float best_next, bool live, double lr, double gamma) {
+  Q2048_NO_CONTRACT
+  const double target = (gamma * (double)best_next) * (live ? 1.0 : 0.0);
+  return (float)((lr * 0.03125) * (target - (double)v_x));
+}
+// The TD step on the afterstate x, given the evaluation of the next state: all 32 entries of x are gathered, then
+// each is written as gathered + d.  Entries of x that are the same weight (a board with a symmetry) gathered the
+// same value and store the same value, so that weight moves by d ONCE: this family's rule, not the literature's.
+template <class Ld, class St>
+Q_HD void nt_td(const Board& x, const NtEval& en, bool done, double lr, double gamma, Ld ld, St st) {
+  const NtIdx ix = nt_indices(x);
+  const NtEntries n = nt_gather(ix, ld);
+  const bool live = !done && en.legal != 0u;
+  const float d = nt_delta(nt_v(n), av_best(en.legal, en.q), live, lr, gamma);
+#pragma unroll
+  for (int p = 0; p < kNtPatterns; ++p)
+#pragma unroll
+    for (int g = 0; g < kNtImages; ++g) st(p, ix.i[p][g], n.e[p][g] + d);
+}
+
 }  // namespace q2048

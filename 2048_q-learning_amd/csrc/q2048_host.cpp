@@ -871,6 +871,16 @@ inline void av_scatter(float* v, const AvTaken& t, float d) {
   for (int f = 0; f < kLtFeatures; ++f) st_f32(av_entry(v, f, t.x.i[f]), t.e[f] + d);
 }
 
+// ---- 6-tuple afterstate network: V = float[4][2^24]; how nt_gather / nt_eval / nt_td reach an entry here ----------
+struct NtLd {
+  const float* v;
+  float operator()(int p, uint32_t idx) const { return ld_f32(v + ((size_t)p * kNtIdx + idx)); }
+};
+struct NtSt {
+  float* v;
+  void operator()(int p, uint32_t idx, float x) const { st_f32(v + ((size_t)p * kNtIdx + idx), x); }
+};
+
 // ---- bulk moves of rows into a table (import, merge, fold, unfold) ----------------------------------------------
 // the one- or two-word key of a table, as the type the probes are compiled for: f(Geo<4>::Key) or f(Geo<5>::Key)
 template <class F>
@@ -1863,6 +1873,158 @@ int q2048_av_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights,
         const Row q = av_row(ev);
         bool explored;
         const int act = play_action(ev.c.legal, q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
+        const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+        st.i[Q2048_ST_VALID] += o.valid != 0;
+        st.i[Q2048_ST_EXPLORE] += explored;
+        reward_sum += (double)o.reward;
+        if (o.done) {
+          st.i[Q2048_ST_EPISODES] += 1;
+          st.episode(a, o.max_log2);
+          begin_episode(b, a, seed, id, (env & kEnvResetShaping) != 0);
+        }
+      }
+      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
+      st.f[Q2048_SF_REWARD] += reward_sum;
+      store_board(boards, i, b);
+      st_aux(aux, i, a);
+    }
+  });
+  stats_merge(parts, used, stats_i, stats_f);
+  return Q2048_OK;
+}
+
+// ---- the 6-tuple afterstate network: one evaluation = the four moved boards and their 4 x 32 entries; nothing is
+// carried from step to step, the fused learner evaluates s from memory on every step ----
+int q2048_nt_value(const float* weights, const uint8_t* boards, int64_t B, float* v_out, void*) {
+  if (int e = check_nt_value(weights, boards, B, v_out)) return e;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Board b;
+      load_board(boards, i, b);
+      v_out[i] = nt_v(nt_gather(nt_indices(b), NtLd{weights}));
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_nt_lookup(const float* weights, const uint8_t* boards, int64_t B, float* q_out, void*) {
+  if (int e = check_nt_lookup(weights, boards, B, q_out)) return e;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Board b;
+      load_board(boards, i, b);
+      const Row q = nt_eval(b, NtLd{weights}).q;
+      q_out[4 * i] = q.q0; q_out[4 * i + 1] = q.q1; q_out[4 * i + 2] = q.q2; q_out[4 * i + 3] = q.q3;
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_nt_choose(const float* weights, const uint8_t* boards, int64_t B, double eps, uint64_t seed, uint64_t env_id0,
+                    uint32_t ctr, uint8_t* actions, void*) {
+  if (int e = check_nt_choose(weights, boards, B, eps, actions)) return e;
+  const uint64_t eps_t = eps_threshold(eps);
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Board b;
+      load_board(boards, i, b);
+      const Draws x = draws(seed, env_id0 + (uint64_t)i, ctr, kStreamStep);
+      const NtEval ev = nt_eval(b, NtLd{weights});
+      bool explored;
+      actions[i] = (uint8_t)play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_nt_update(float* weights, const uint8_t* boards_s, const uint8_t* actions, const uint8_t* boards_s2,
+                    const uint8_t* done, int64_t B, double lr, double gamma, uint32_t* status, void*) {
+  if (int e = check_nt_update(weights, boards_s, actions, boards_s2, done, B, lr, gamma, status)) return e;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      const int act = actions[i];
+      if (act > 3) { status_or(status, Q2048_STATUS_BAD_ACTION); continue; }
+      Board x, b_n;
+      load_board(boards_s, i, x);
+      load_board(boards_s2, i, b_n);
+      uint32_t score;
+      if (!move(x, act, score)) continue;   // the step on which the env reports the end
+      const NtEval en = nt_eval(b_n, NtLd{weights});
+      nt_td(x, en, done[i] != 0, lr, gamma, NtLd{weights}, NtSt{weights});
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_nt_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, int64_t B, int64_t steps, double eps,
+                           double lr, double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i,
+                           double* stats_f, uint32_t* status, void*) {
+  if (int e = check_nt_fused(boards, aux, weights, B, steps, eps, lr, gamma, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  const uint64_t eps_t = eps_threshold(eps);
+  const int T = threads_for(B);
+  std::vector<Stats> parts((size_t)T);
+  Stats* sp = parts.data();
+  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+    Stats& st = sp[tid];
+    for (int64_t i = lo; i < hi; ++i) {
+      const uint64_t id = env_id0 + (uint64_t)i;
+      Board b;
+      load_board(boards, i, b);
+      Aux a = ld_aux(aux, i);
+      double reward_sum = 0.0;
+      for (int64_t t = 0; t < steps; ++t) {
+        const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+        const NtEval ev = nt_eval(b, NtLd{weights});
+        bool explored;
+        const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+        Board c = b;                    // the afterstate of the move played
+        uint32_t score;
+        const bool legal = move(c, act, score);
+        const StepOut o = env_step(b, a, act, x.x2, x.x3);
+        const NtEval en = nt_eval(b, NtLd{weights});
+        if (legal) nt_td(c, en, o.done != 0, lr, gamma, NtLd{weights}, NtSt{weights});
+        st.i[Q2048_ST_VALID] += o.valid != 0;
+        st.i[Q2048_ST_EXPLORE] += explored;
+        reward_sum += (double)o.reward;
+        if (o.done) {
+          st.i[Q2048_ST_EPISODES] += 1;
+          st.episode(a, o.max_log2);
+          begin_episode(b, a, seed, id);
+        }
+      }
+      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
+      st.f[Q2048_SF_REWARD] += reward_sum;
+      store_board(boards, i, b);
+      st_aux(aux, i, a);
+    }
+  });
+  stats_merge(parts, used, stats_i, stats_f);
+  return Q2048_OK;
+}
+int q2048_nt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
+                          uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                          double* stats_f, uint32_t* status, void*) {
+  if (int e = check_nt_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  const uint64_t eps_t = eps_threshold(eps);
+  const ImageLuts lut{&g_lut_image};
+  const int env = env_bits(flags);
+  const int T = threads_for(B);
+  std::vector<Stats> parts((size_t)T);
+  Stats* sp = parts.data();
+  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+    Stats& st = sp[tid];
+    for (int64_t i = lo; i < hi; ++i) {
+      const uint64_t id = env_id0 + (uint64_t)i;
+      Board b;
+      load_board(boards, i, b);
+      Aux a = ld_aux(aux, i);
+      const DrawPrep prep = draws_prepare(seed, id, kStreamStep);
+      double reward_sum = 0.0;
+      for (int64_t t = 0; t < steps; ++t) {
+        const Draws x = draws_at(prep, ctr0 + (uint32_t)t);
+        Draws y{0u, 0u, 0u, 0u};
+        if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+        const NtEval ev = nt_eval(b, NtLd{weights});
+        bool explored;
+        const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
         const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
         st.i[Q2048_ST_VALID] += o.valid != 0;
         st.i[Q2048_ST_EXPLORE] += explored;

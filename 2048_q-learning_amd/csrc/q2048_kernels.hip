@@ -2462,6 +2462,179 @@ __global__ __launch_bounds__(kBlock) void k_av_play_rollout(
 }
 
 // ---------------------------------------------------------------------------------------------
+// 6-tuple afterstate network with shared symmetric weights (q2048_nt_*): V = float[4][2^24],
+// 256 MiB -- 64 times an XCD's L2.  One evaluation = the four moved boards, for each its packed
+// key, the eight image keys (key_images) and 32 indices by shifts and masks, and 32 four-byte
+// loads issued back to back; the 32 entries of a candidate are reduced to its q as they arrive,
+// so an evaluation leaves a Row and a legality mask in registers and NOTHING is carried from step
+// to step: the fused learner evaluates s from memory at the top of every step (it sees the lane's
+// own writes, which is what makes B = 1 the four-call loop) and gathers the 32 entries of the
+// afterstate again for the TD step.  Loads in plain C++, relaxed agent-scope atomic loads in the
+// learner kernels, ordinary loads in the player; none is predicated on its move being legal.
+// Kernels of their own; no existing kernel changes.
+// ---------------------------------------------------------------------------------------------
+template <bool AGENT>
+struct NtLd {
+  const float* v;
+  __device__ __forceinline__ float operator()(int p, uint32_t idx) const {
+    const float* e = v + ((size_t)p * kNtIdx + idx);
+    if constexpr (AGENT) return __hip_atomic_load(e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else return *e;
+  }
+};
+struct NtSt {
+  float* v;
+  __device__ __forceinline__ void operator()(int p, uint32_t idx, float x) const { v[(size_t)p * kNtIdx + idx] = x; }
+};
+
+__global__ __launch_bounds__(kBlock) void k_nt_value(const float* w, const uint8_t* boards, int64_t B, float* v_out) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  v_out[i] = nt_v(nt_gather(nt_indices(load_board(boards, i, B, st)), NtLd<true>{w}));
+}
+
+__global__ __launch_bounds__(kBlock) void k_nt_lookup(const float* w, const uint8_t* boards, int64_t B, float* q_out) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const Row q = nt_eval(load_board(boards, i, B, st), NtLd<true>{w}).q;
+  reinterpret_cast<float4*>(q_out)[i] = make_float4(q.q0, q.q1, q.q2, q.q3);
+}
+
+__global__ __launch_bounds__(kBlock) void k_nt_choose(const float* w, const uint8_t* boards, int64_t B, double eps,
+                                                      uint64_t seed, uint64_t env_id0, uint32_t ctr, uint8_t* actions) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const Board b = load_board(boards, i, B, st);
+  const Draws x = draws(seed, env_id0 + (uint64_t)i, ctr, kStreamStep);
+  const NtEval ev = nt_eval(b, NtLd<true>{w});
+  bool explored;
+  actions[i] = (uint8_t)play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_threshold(eps), x.x0, x.x1, explored);
+}
+
+__global__ __launch_bounds__(kBlock) void k_nt_update(float* w, const uint8_t* s, const uint8_t* actions, const uint8_t* s2,
+                                                      const uint8_t* done, int64_t B, double lr, double gamma,
+                                                      uint32_t* status) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const int act = actions[i];
+  if (act > 3) { atomicOr(status, Q2048_STATUS_BAD_ACTION); return; }
+  Board x = load_board(s, i, B, st);
+  const Board b_n = load_board(s2, i, B, st);
+  uint32_t score;
+  if (!move(x, act, score)) return;   // the step on which the env reports the end
+  const NtEval en = nt_eval(b_n, NtLd<true>{w});
+  nt_td(x, en, done[i] != 0, lr, gamma, NtLd<true>{w}, NtSt{w});
+}
+
+__global__ __launch_bounds__(kBlock) void k_nt_fused_rollout(
+    uint8_t* boards, q2048_aux* aux, float* w, int64_t B, int steps, double eps, double lr,
+    double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f,
+    uint32_t* /*status: as on k_av_fused_rollout, nothing data-dependent can go wrong on this path*/) {
+  __shared__ BlockStats bs;
+  stats_clear(bs);
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < B) {
+    Stage<4> st;
+    const uint64_t id = env_id0 + (uint64_t)i;
+    Board b = load_board(boards, i, B, st);
+    Aux a = ld_aux(aux, i);
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
+    double reward_sum = 0.0;
+    const uint64_t eps_t = eps_threshold(eps);
+    for (int t = 0; t < steps; ++t) {
+      const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+      // s is evaluated from memory on every step: whatever this lane wrote before is read back (its entries
+      // were read one step earlier as s', so they are close by), and no written index has to be remembered
+      const NtEval ev = nt_eval(b, NtLd<true>{w});
+      bool explored;
+      const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+      Board c = b;                    // the afterstate of the move played
+      uint32_t score;
+      const bool legal = move(c, act, score);
+      const StepOut o = env_step(b, a, act, x.x2, x.x3);
+      const NtEval en = nt_eval(b, NtLd<true>{w});
+      if (legal) nt_td(c, en, o.done != 0, lr, gamma, NtLd<true>{w}, NtSt{w});
+      n_valid += wave_count(o.valid != 0);
+      n_explore += wave_count(explored);
+      n_done += wave_count(o.done != 0);
+      reward_sum += (double)o.reward;
+      if (o.done) {
+        episode_stats(bs, a, o.max_log2);
+        begin_episode(b, a, seed, id);
+      }
+    }
+    store_board(boards, i, B, b, st);
+    st_aux(aux, i, a);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+    const uint32_t n_active = wave_count(true);
+    if (wave_leader()) {
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  stats_flush(bs, stats_i, stats_f);
+}
+
+// the greedy player on the network (q2048_nt_play_rollout): k_av_play_rollout with q2048_nt_lookup's row
+template <int ENV>
+__global__ __launch_bounds__(kBlock) void k_nt_play_rollout(
+    uint8_t* boards, q2048_aux* aux, const float* w, int64_t B, int steps, double eps, uint64_t seed,
+    uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
+  __shared__ BlockStats bs;
+  __shared__ Stage<4> st;
+  __shared__ LutImage lut_lds;
+  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
+  if (threadIdx.x < kLutImageDoubles)
+    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
+  stats_clear(bs);                                        // (its barrier publishes the image too)
+  const ImageLuts lut{&lut_lds};
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  Board b = load_board(boards, i, B, st);
+  if (i < B) {
+    const uint64_t id = env_id0 + (uint64_t)i;
+    Aux a = ld_aux(aux, i);
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
+    double reward_sum = 0.0;
+    const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
+    const uint64_t eps_t = eps_threshold(eps);
+    for (int t = 0; t < steps; ++t) {
+      const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
+      Draws y{0u, 0u, 0u, 0u};
+      if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+      const NtEval ev = nt_eval(b, NtLd<false>{w});
+      bool explored;
+      const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+      if (o.done) {
+        episode_stats(bs, a, o.max_log2);
+        begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
+      }
+      n_valid += wave_count(o.valid != 0);
+      n_explore += wave_count(explored);
+      n_done += wave_count(o.done != 0);
+      reward_sum += (double)o.reward;
+    }
+    st_aux(aux, i, a);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+    const uint32_t n_active = wave_count(true);
+    if (wave_leader()) {
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  store_board(boards, i, B, b, st);
+  stats_flush(bs, stats_i, stats_f);
+}
+
+// ---------------------------------------------------------------------------------------------
 // table utilities
 // ---------------------------------------------------------------------------------------------
 // Streams the whole table once, in tiles of 16 Ki slots per block: a lane reads the first 16 bytes
@@ -3556,6 +3729,65 @@ int q2048_av_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights,
     break;
   switch (env_bits(flags) & 3) { Q2048_LAUNCH_AV_PLAY(0) Q2048_LAUNCH_AV_PLAY(1) Q2048_LAUNCH_AV_PLAY(2) Q2048_LAUNCH_AV_PLAY(3) }
 #undef Q2048_LAUNCH_AV_PLAY
+  return launch_status();
+}
+
+int q2048_nt_value(const float* weights, const uint8_t* boards, int64_t B, float* v_out, void* stream) {
+  if (int e = check_nt_value(weights, boards, B, v_out)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_nt_value, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights, boards, B, v_out);
+  return launch_status();
+}
+
+int q2048_nt_lookup(const float* weights, const uint8_t* boards, int64_t B, float* q_out, void* stream) {
+  if (int e = check_nt_lookup(weights, boards, B, q_out)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_nt_lookup, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights, boards, B, q_out);
+  return launch_status();
+}
+
+int q2048_nt_choose(const float* weights, const uint8_t* boards, int64_t B, double eps, uint64_t seed,
+                    uint64_t env_id0, uint32_t ctr, uint8_t* actions, void* stream) {
+  if (int e = check_nt_choose(weights, boards, B, eps, actions)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_nt_choose, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights,
+                     boards, B, eps, seed, env_id0, ctr, actions);
+  return launch_status();
+}
+
+int q2048_nt_update(float* weights, const uint8_t* boards_s, const uint8_t* actions, const uint8_t* boards_s2,
+                    const uint8_t* done, int64_t B, double lr, double gamma, uint32_t* status, void* stream) {
+  if (int e = check_nt_update(weights, boards_s, actions, boards_s2, done, B, lr, gamma, status)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_nt_update, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights,
+                     boards_s, actions, boards_s2, done, B, lr, gamma, status);
+  return launch_status();
+}
+
+int q2048_nt_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, int64_t B, int64_t steps,
+                           double eps, double lr, double gamma, uint64_t seed, uint64_t env_id0,
+                           uint32_t ctr0, int64_t* stats_i, double* stats_f, uint32_t* status,
+                           void* stream) {
+  if (int e = check_nt_fused(boards, aux, weights, B, steps, eps, lr, gamma, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_nt_fused_rollout, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream,
+                     boards, aux, weights, B, (int)steps, eps, lr, gamma, seed, env_id0, ctr0, stats_i,
+                     stats_f, status);
+  return launch_status();
+}
+
+int q2048_nt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
+                          uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                          double* stats_f, uint32_t* status, void* stream) {
+  if (int e = check_nt_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+#define Q2048_LAUNCH_NT_PLAY(E)                                                                                    \
+  case E:                                                                                                          \
+    hipLaunchKernelGGL((k_nt_play_rollout<E>), dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, boards,    \
+                       aux, weights, B, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);                   \
+    break;
+  switch (env_bits(flags) & 3) { Q2048_LAUNCH_NT_PLAY(0) Q2048_LAUNCH_NT_PLAY(1) Q2048_LAUNCH_NT_PLAY(2) Q2048_LAUNCH_NT_PLAY(3) }
+#undef Q2048_LAUNCH_NT_PLAY
   return launch_status();
 }
 

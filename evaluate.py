@@ -5,8 +5,8 @@ The reference's README lists an `evaluate.py` ("script per la valutazione e il t
 README.md:52) that its repository does not contain.  This is that script for the MI355X path: it
 loads a learner written by `train.py --save` (a hash table, or -- "kind": "row_tuple" -- the row-tuple learner's
 weights, or -- "kind": "line_tuple" -- the line-tuple learner's, or -- "kind": "line_afterstate" -- the afterstate
-learner's values: the file says which, and the JSON line then carries
-"agent": "row-tuple" / "line-tuple" / "afterstate"), plays `--episodes` games per env
+learner's values, or -- "kind": "ntuple6_afterstate" -- the 6-tuple afterstate network: the file says which, and the
+JSON line then carries "agent": "row-tuple" / "line-tuple" / "afterstate" / "ntuple"), plays `--episodes` games per env
 with the stored values -- rows are read, nothing is created or written -- and prints one JSON line: games, mean
 score / return, max-tile histogram.  Two policies:
 
@@ -70,7 +70,7 @@ def main(argv=None):
 
     pkg = importlib.import_module("2048_q-learning_amd")
     sd = torch.load(args.model, map_location="cpu", weights_only=False)
-    if sd.get("kind") in ("row_tuple", "line_tuple", "line_afterstate"):
+    if sd.get("kind") in ("row_tuple", "line_tuple", "line_afterstate", "ntuple6_afterstate"):
         return main_row_tuple(args, torch, pkg, sd)
     n, rows = int(sd["board_size"]), len(sd["q"])
     cap = max(int(sd["capacity_log2"]), 4) if "table" in sd else max(16, (2 * max(rows, 1) - 1).bit_length())
@@ -114,10 +114,12 @@ def main_row_tuple(args, torch, pkg, sd):
     """A file of `train.py --agent row-tuple --save`: the same three policies on a `BatchedRowTupleAgent`.  There are no
     rows to count: what must not change is the weights, all 4 MiB, bit for bit.  A file of `--agent line-tuple` (8 MiB,
     "kind": "line_tuple") plays the same way on a `BatchedLineTupleAgent`, a file of `--agent afterstate` (2 MiB,
-    "kind": "line_afterstate") on a `BatchedAfterstateAgent` ("agent": "afterstate")."""
+    "kind": "line_afterstate") on a `BatchedAfterstateAgent` ("agent": "afterstate"), a file of `--agent ntuple`
+    (256 MiB, "kind": "ntuple6_afterstate") on a `BatchedNTupleAgent` ("agent": "ntuple")."""
     kind = sd.get("kind")
     cls, name = {"row_tuple": (pkg.BatchedRowTupleAgent, "row-tuple"), "line_tuple": (pkg.BatchedLineTupleAgent, "line-tuple"),
-                 "line_afterstate": (pkg.BatchedAfterstateAgent, "afterstate")}[kind]
+                 "line_afterstate": (pkg.BatchedAfterstateAgent, "afterstate"),
+                 "ntuple6_afterstate": (pkg.BatchedNTupleAgent, "ntuple")}[kind]
     agent = cls(1, learning_rate=sd["lr"], discount_factor=sd["gamma"], exploration_rate=args.epsilon, seed=args.seed,
                 device=args.device)
     agent.load_state_dict(sd)

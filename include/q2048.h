@@ -70,7 +70,8 @@ extern "C" {
                                q2048_rt_play_rollout (the greedy player on row-tuple weights) too, by its symbol;
                                the line-tuple family q2048_lt_* (rows and columns as features) by the symbol
                                q2048_lt_lookup; the afterstate value family q2048_av_* by the symbol
-                               q2048_av_lookup */
+                               q2048_av_lookup; the 6-tuple afterstate network q2048_nt_* by the symbol
+                               q2048_nt_lookup */
 
 /* return codes */
 #define Q2048_OK 0
@@ -862,6 +863,54 @@ int q2048_av_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weights, int6
                            uint64_t env_id0, uint32_t ctr0, int64_t *stats_i, double *stats_f,
                            uint32_t *status, void *stream);
 int q2048_av_play_rollout(uint8_t *boards, q2048_aux *aux, const float *weights, int64_t B, int64_t steps,
+                          double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
+                          int64_t *stats_i, double *stats_f, uint32_t *status, void *stream);
+
+/* ---- 6-tuple afterstate network with shared symmetric weights ---------------------------------------------------
+ * A fourth weights family, 4x4 boards only: the afterstate family above with another feature set -- four 6-cell
+ * patterns, each read on the eight images of the board, one weight table per pattern shared by the eight images.
+ *   weights   V = float[4][16777216] (256 MiB, 16-byte aligned, zero = untrained).  Pattern p has the cells P_p, with
+ *             cell index 4r + c:  P0 = {0,1,2,3,4,5}  P1 = {4,5,6,7,8,9}  P2 = {0,1,2,4,5,6}  P3 = {4,5,6,8,9,10}.
+ *   images    the eight images of Q2048_FLAG_SYMMETRIC, with the same numbering: img_g(b) = np.rot90(b, g) for
+ *             g = 0..3, img_g(b) = np.rot90(np.fliplr(b), g - 4) for g = 4..7.
+ *   index     idx[p][g](b) = sum over k = 0..5 of (img_g(b).flat[P_p[k]] & 15) << 4k.  A cell >= 16 aliases by the
+ *             mask, as in the other weight families, and is not an error.  Every index is below 2^24 by
+ *             construction, so no board can address outside the array.
+ *   value     e[p][g] = V[p][idx[p][g](x)];  s_p = ((e[p][0] + e[p][1]) + (e[p][2] + e[p][3])) + ((e[p][4] + e[p][5])
+ *             + (e[p][6] + e[p][7]));  v(x) = (s_0 + s_1) + (s_2 + s_3); float32 with exactly that association.
+ *   evaluation, has_move, best, choice: word for word those of the afterstate family: q_a = (float)score_a + v(c_a),
+ *             no special case for a move that does not change the board, and every entry point uses the player's
+ *             draw contract.
+ *   TD step   for (s, a, s2, done), x = c_a(s): nothing is written if a is not legal in s; an action > 3 sets
+ *             Q2048_STATUS_BAD_ACTION and skips the lane.  live and target are those of the afterstate family;
+ *             d = (float)((lr * 0.03125) * (target - (double)v(x))), rounded once.  The lane gathers all 32 entries
+ *             of x, then writes each V[p][idx[p][g](x)] as (the value gathered at that entry) + d: plain 4-byte
+ *             stores, the last writer wins.  Where several of a lane's 32 entries are the same weight (a board with
+ *             a symmetry: the empty board has 4 distinct entries among its 32) they gathered the same value and
+ *             store the same value, so that weight moves by d ONCE, not once per occurrence.  This is this family's
+ *             rule; it is not the literature's, which adds the error once per occurrence.
+ *   fused     q2048_nt_fused_rollout, per lane and step: evaluate s, choose with x0, x1, env step with x2, x3
+ *             (default profile, no flags), evaluate s', TD step on c_act, on done statistics + reset.  Nothing is
+ *             carried from step to step: s is evaluated from memory on every step and the 32 entries of c_act are
+ *             gathered again for the TD step, so every evaluation a lane makes sees the lane's own earlier writes
+ *             and B = 1 is exactly the four-call loop, all 256 MiB bit for bit.
+ *   player    q2048_nt_play_rollout: q2048_av_play_rollout with this row; weights are only read;
+ *             Q2048_FLAG_ENV_DQN and Q2048_FLAG_RESET_SHAPING as there.
+ * Each entry point has the argument list of its q2048_av_* counterpart, the same checks in the same order and the
+ * same codes; a refused call writes nothing; B == 0 or steps == 0 is Q2048_OK. */
+int q2048_nt_value(const float *weights, const uint8_t *boards, int64_t B, float *v_out, void *stream);
+int q2048_nt_lookup(const float *weights, const uint8_t *boards, int64_t B, float *q_out,
+                    void *stream);
+int q2048_nt_choose(const float *weights, const uint8_t *boards, int64_t B, double eps,
+                    uint64_t seed, uint64_t env_id0, uint32_t ctr, uint8_t *actions, void *stream);
+int q2048_nt_update(float *weights, const uint8_t *boards_s, const uint8_t *actions,
+                    const uint8_t *boards_s2, const uint8_t *done, int64_t B,
+                    double lr, double gamma, uint32_t *status, void *stream);
+int q2048_nt_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weights, int64_t B,
+                           int64_t steps, double eps, double lr, double gamma, uint64_t seed,
+                           uint64_t env_id0, uint32_t ctr0, int64_t *stats_i, double *stats_f,
+                           uint32_t *status, void *stream);
+int q2048_nt_play_rollout(uint8_t *boards, q2048_aux *aux, const float *weights, int64_t B, int64_t steps,
                           double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
                           int64_t *stats_i, double *stats_f, uint32_t *status, void *stream);
 

@@ -98,6 +98,9 @@ def main(argv=None):
         if sd.get("kind") == "line_afterstate":
             raise SystemExit(f"{path} holds afterstate values, not a hash table: the two kinds do not mix, and averaging "
                              "weight replicas is not built")
+        if sd.get("kind") == "ntuple6_afterstate":
+            raise SystemExit(f"{path} holds a 6-tuple afterstate network, not a hash table: the two kinds do not mix, and "
+                             "averaging weight replicas is not built")
         if first is None:
             first = {k: v for k, v in sd.items() if k not in ("keys", "q", "table", "env", "visit_rows")}
         if int(sd["board_size"]) != int(first["board_size"]):

@@ -1,0 +1,1036 @@
+"""The 6-tuple afterstate network with shared symmetric weights (V = float32 [4, 2^24], 256 MiB): the six entry points
+q2048_nt_value, q2048_nt_lookup, q2048_nt_choose, q2048_nt_update, q2048_nt_fused_rollout and q2048_nt_play_rollout
+against a numpy model, and BatchedNTupleAgent's checkpoint.  (The scripts: test_ntuple_scripts.py.)
+
+Which test executes which kernel (device) / function (CPU twin):
+  k_nt_value          test_index_definition (through v), test_value_and_lookup_at_the_edges, test_symmetric_boards,
+                      test_65536_boards
+  k_nt_lookup         test_index_definition, test_value_and_lookup_at_the_edges,
+                      test_lookup_on_boards_with_one_move_none_and_merges, test_65536_boards
+  k_nt_choose         test_choose_greedy_ties_and_illegal_maxima, test_choose_at_the_edges, test_65536_boards
+  k_nt_update         test_symmetric_boards, test_update_where_lanes_cannot_race
+  k_nt_fused_rollout  test_fused_rollout_with_frozen_weights, test_fused_rollout_one_lane_many_steps (re-reading),
+                      test_fused_rollout_one_learning_step, test_racing_learning_at_65536_boards_properties
+  k_nt_play_rollout   test_player_equals_the_four_call_loop, test_player_exploration_against_a_model
+  the argument checks test_abi, test_argument_errors_need_no_device, test_refused_calls_write_nothing
+
+The model (model_images, model_idx, model_v, model_eval, model_update) is plain numpy: the images come from np.rot90 /
+np.flip, the moves from the oracle (`oracle.move` through test_afterstate.model_moves), and it shares no code with
+csrc/.  Every comparison is exact: integers, bytes, and float32 values as bit patterns; a whole 256 MiB array is
+compared with one np.array_equal, and a per-entry difference is worked out only when that fails.  There is no
+tolerance: v is a fixed tree of float32 additions, q_a one more float32 addition of an integer below 2^24, the TD step
+one float64 expression rounded once (lr * 0.03125 is exact: a power of two), and a contraction of
+(gamma * best) * live - v into an fma cannot change it because live is 0.0 or 1.0.  Every case runs on the CPU twin
+("cpu") and on the GPU."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import test_afterstate as AV
+import test_line_tuple as LT
+import test_row_tuple_kernels as K
+import test_row_tuple_player as P
+
+REPO = P.REPO
+DEVICES = LT.DEVICES
+EDGES = sorted(set(LT.EDGES) | {63, 64, 65, 255, 256, 257})
+ROOM, Q_CANARY, A_CANARY, BAD_ACTION = K.ROOM, K.Q_CANARY, K.A_CANARY, K.BAD_ACTION
+ERR_NULL, ERR_SIZE, ERR_ALIGN, ERR_RANGE, ERR_FLAGS = -1, -2, -3, -6, -7
+F32 = np.float32
+NIDX = 1 << 24
+PATTERNS = ((0, 1, 2, 3, 4, 5), (4, 5, 6, 7, 8, 9), (0, 1, 2, 4, 5, 6), (4, 5, 6, 8, 9, 10))
+NAMES = ("q2048_nt_value", "q2048_nt_lookup", "q2048_nt_choose", "q2048_nt_update", "q2048_nt_fused_rollout",
+         "q2048_nt_play_rollout")
+lib, t8, t32, bits = K.lib, K.t8, K.t32, K.bits
+model_moves, model_greedy, model_best, mask_of, conflicts = AV.model_moves, AV.model_greedy, AV.model_best, AV.mask_of, AV.conflicts
+
+
+def assert_same_bits(got, want, what):
+    """One comparison of the whole array; where it differs is worked out only on failure."""
+    got, want = bits(got), bits(want)
+    assert got.shape == want.shape, what
+    if not np.array_equal(got, want):
+        bad = np.argwhere(got != want)
+        raise AssertionError(f"{what}: {len(bad)} values differ, first at {bad[0].tolist()}: "
+                             f"{got[tuple(bad[0])]:#x} != {want[tuple(bad[0])]:#x}")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the model
+# ---------------------------------------------------------------------------------------------------------------
+def model_images(boards):
+    """img_g(b) = np.rot90(b, g), g = 0..3; np.rot90(np.fliplr(b), g - 4), g = 4..7 -> uint8 [B, 8, 16]"""
+    b = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 4, 4)
+    flipped = np.flip(b, axis=2)                                                      # np.fliplr of every board
+    imgs = [np.rot90(b, g, axes=(1, 2)) for g in range(4)] + [np.rot90(flipped, g, axes=(1, 2)) for g in range(4)]
+    return np.stack([i.reshape(-1, 16) for i in imgs], axis=1)
+
+
+def model_idx(boards):
+    """idx[p][g] = sum_k (img_g.flat[P_p[k]] & 15) << 4k -> int64 [B, 4, 8]"""
+    img = (model_images(boards) & 15).astype(np.int64)
+    out = np.zeros((len(img), 4, 8), np.int64)
+    for p, cells in enumerate(PATTERNS):
+        for k, c in enumerate(cells):
+            out[:, p, :] += img[:, :, c] << (4 * k)
+    assert out.max(initial=0) < NIDX
+    return out
+
+
+def model_v(V, boards):
+    """s_p = ((e0 + e1) + (e2 + e3)) + ((e4 + e5) + (e6 + e7)) over the images, v = (s0 + s1) + (s2 + s3) -> float32 [B]"""
+    idx = model_idx(boards)
+    s = []
+    for p in range(4):
+        e = [V[p, idx[:, p, g]] for g in range(8)]
+        assert all(x.dtype == F32 for x in e)
+        s.append(((e[0] + e[1]) + (e[2] + e[3])) + ((e[4] + e[5]) + (e[6] + e[7])))
+    return (s[0] + s[1]) + (s[2] + s[3])
+
+
+def model_eval(O, V, boards, moves=None):
+    """q_a = float32(score_a) + v(c_a) -> (q float32 [B, 4], legal bool [B, 4], moved boards)"""
+    moved, score, legal = moves if moves is not None else model_moves(O, boards)
+    assert score.max(initial=0) < 1 << 24
+    q = np.stack([score[:, a].astype(F32) + model_v(V, moved[:, a]) for a in range(4)], axis=1)
+    assert q.dtype == F32
+    return q, legal, moved
+
+
+def model_update(O, V, s, actions, s2, done, lr, gamma, inplace=False):
+    """The TD step, lane after lane on one array: all 32 entries gathered, then each written as gathered + d (an entry
+    that occurs several times is written several times with the same value).
+    -> (values afterwards, status word, int [B, 4, 8] written indices or -1)"""
+    V, status = (V if inplace else V.copy()), 0
+    written = np.full((len(s), 4, 8), -1, np.int64)
+    pp = np.arange(4)[:, None]
+    for i in range(len(s)):
+        a = int(actions[i])
+        if a > 3:
+            status |= BAD_ACTION
+            continue
+        x, _, legal = O.move(s[i], a)
+        if not legal:
+            continue
+        q2, legal2, _ = model_eval(O, V, s2[i:i + 1])
+        live = 1.0 if (not done[i]) and legal2.any() else 0.0
+        target = (gamma * float(model_best(q2, legal2)[0])) * live                    # float64
+        d = F32((lr * 0.03125) * (target - float(model_v(V, x[None])[0])))           # rounded once
+        idx = model_idx(x[None])[0]
+        gathered = V[pp, idx]
+        V[pp, idx] = gathered + d
+        written[i] = idx
+    return V, status, written
+
+
+def entry_ids(boards):
+    """p * 2^24 + idx of the 32 entries of each board -> int64 [B, 32]"""
+    return (model_idx(boards) + (np.arange(4) * NIDX)[None, :, None]).reshape(len(boards), 32)
+
+
+def entry_sets_many(O, s, a, s2, fused=False):
+    """(read set, write set) of every lane of the TD step, entry ids p * 2^24 + idx.  `fused`: the step of the fused
+    learner, which also evaluates s itself (all four candidates)."""
+    n = len(s)
+    moved_s, _, legal_s = model_moves(O, s)
+    at = lambda boards: entry_ids(boards.reshape(-1, 16)).reshape(n, -1)      # noqa: E731
+    reads = np.concatenate([at(model_moves(O, s2)[0])] + ([at(moved_s)] if fused else []), axis=1)
+    ok = a <= 3
+    act = np.where(ok, a, 0)
+    wrote = ok & legal_s[np.arange(n), act]
+    writes = at(moved_s[np.arange(n), act])
+    out = []
+    for i in range(n):
+        w = set(writes[i].tolist()) if wrote[i] else set()
+        out.append((set(reads[i].tolist()) | w, w))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the entry points, through ctypes alone
+# ---------------------------------------------------------------------------------------------------------------
+def nt_value(L, dev, weights, boards):
+    B = len(boards)
+    out = torch.full((B + ROOM,), Q_CANARY - (1 << 32), dtype=torch.int32, device=dev)
+    tb = t8(dev, boards)
+    assert L.q2048_nt_value(weights.data_ptr(), tb.data_ptr(), B, out.data_ptr(), None) == 0
+    out = out.cpu().numpy().view(np.uint32)
+    return out[:B], out[B:]
+
+
+def nt_lookup(L, dev, weights, boards):
+    B = len(boards)
+    out = torch.full((B + ROOM, 4), Q_CANARY - (1 << 32), dtype=torch.int32, device=dev)
+    tb = t8(dev, boards)
+    assert L.q2048_nt_lookup(weights.data_ptr(), tb.data_ptr(), B, out.data_ptr(), None) == 0
+    out = out.cpu().numpy().view(np.uint32)
+    return out[:B], out[B:]
+
+
+def nt_choose(L, dev, weights, boards, eps, seed=0, env_id0=0, ctr=0):
+    B = len(boards)
+    out = torch.full((B + ROOM,), A_CANARY, dtype=torch.uint8, device=dev)
+    tb = t8(dev, boards)
+    assert L.q2048_nt_choose(weights.data_ptr(), tb.data_ptr(), B, float(eps), seed, env_id0, ctr, out.data_ptr(),
+                             None) == 0
+    out = out.cpu().numpy()
+    return out[:B], out[B:]
+
+
+_SHARED = {}
+
+
+def base_values():
+    """Random normal float32 [4, 2^24] (scale 4: it outweighs most merge scores), built once per module; nobody writes it."""
+    if "v" not in _SHARED:
+        v = np.random.default_rng(24).standard_normal((4, NIDX), dtype=F32)
+        v *= F32(4.0)
+        v.setflags(write=False)
+        _SHARED["v"] = v
+    return _SHARED["v"]
+
+
+def base_on(dev):
+    """The base values as a tensor on `dev`, uploaded once per device for the tests that only READ them (each asserts
+    afterwards that it left them bit-identical)."""
+    key = ("t", str(dev))
+    if key not in _SHARED:
+        _SHARED[key] = t32(dev, base_values())
+    return _SHARED[key]
+
+
+def assert_base_unwritten(dev, what):
+    assert np.array_equal(bits(base_on(dev)), bits(base_values())), what
+
+
+def make_agent(pkg, dev, eps=0.3, lr=0.1, gamma=0.95, seed=P.SEED, id0=P.ID0, epochs=100):
+    return pkg.BatchedNTupleAgent(epochs, learning_rate=lr, discount_factor=gamma, exploration_rate=eps, seed=seed,
+                                  env_id0=id0, device=dev)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 1. ABI and argument errors
+# ---------------------------------------------------------------------------------------------------------------
+def test_abi(pkg):
+    N = pkg._native
+    with open(os.path.join(REPO, "include", "q2048.h")) as fh:
+        header = fh.read()
+    for name in NAMES:
+        assert name in N._SIGNATURES, name
+        assert hasattr(N.host_lib(), name) and hasattr(N.lib(), name), name
+        assert f"int {name}(" in header, name
+        assert N._SIGNATURES[name] == N._SIGNATURES[name.replace("_nt_", "_av_")], name
+    assert N.host_lib().q2048_abi_version() == 7 == N.lib().q2048_abi_version() == N.ABI_VERSION
+    assert "#define Q2048_ABI_VERSION 7 " in header
+    assert pkg.BatchedNTupleAgent is __import__("q2048_amd").BatchedNTupleAgent
+    assert issubclass(pkg.BatchedNTupleAgent, pkg.BatchedAfterstateAgent)
+
+
+def entry_points(L):
+    a = [0x1000 * (k + 1) for k in range(8)]
+    nan = float("nan")
+    # name: (function, good arguments, required pointers, 16-byte aligned pointers, position of B, {scalar position: refused})
+    return {
+        "nt_value": (L.q2048_nt_value, [a[0], a[1], 64, a[2], None], (0, 1, 3), (0, 1, 3), 2, {}),
+        "nt_lookup": (L.q2048_nt_lookup, [a[0], a[1], 64, a[2], None], (0, 1, 3), (0, 1, 3), 2, {}),
+        "nt_choose": (L.q2048_nt_choose, [a[0], a[1], 64, 0.3, 7, 50, 3, a[2], None], (0, 1, 7), (0, 1), 2,
+                      {3: (-0.1, 1.5, nan)}),
+        "nt_update": (L.q2048_nt_update, [a[0], a[1], a[2], a[3], a[4], 64, 0.1, 0.97, a[5], None],
+                      (0, 1, 2, 3, 4, 8), (0, 1, 3), 5, {6: (nan,), 7: (nan,)}),
+        "nt_fused_rollout": (L.q2048_nt_fused_rollout, [a[0], a[1], a[2], 64, 2, 0.3, 0.1, 0.97, 3, 50, 0, None, None,
+                                                        a[3], None],
+                             (0, 1, 2, 13), (0, 1, 2), 3, {5: (-0.1, 1.5, nan), 6: (nan,), 7: (nan,)}),
+    }
+
+
+@pytest.mark.parametrize("which", ["hip", "host"])
+def test_argument_errors_need_no_device(pkg, which):
+    """The order of the q2048_av_* counterparts -- B, (flags,) NULL, alignment, (steps,) the scalars -- on both
+    libraries, with made-up aligned addresses: every refused call also carries the errors that come later in the
+    order, and nothing behind the addresses is touched (B == 0 and steps == 0 are no-ops)."""
+    N = pkg._native
+    L = N.lib() if which == "hip" else N.host_lib()
+    nan, big = float("nan"), (2 ** 31 - 1) * 256 + 1
+    table = entry_points(L)
+    for name, (fn, good, pointers, aligned, b_pos, scalars) in table.items():
+        def call(**kw):
+            args = list(good)
+            for pos, value in kw.items():
+                args[int(pos[1:])] = value
+            return fn(*args)
+
+        bad_scalar = {f"p{pos}": values[-1] for pos, values in scalars.items()}
+        bad_align = {f"p{pos}": good[pos] + 8 for pos in aligned}
+        for value in (-1, big):                                         # B before everything
+            assert call(**{f"p{b_pos}": value, f"p{pointers[0]}": None}, **bad_scalar) == ERR_SIZE, name
+        for pos in pointers:                                            # NULL before the alignment and the scalars
+            kw = {**bad_align, **bad_scalar, f"p{pos}": None}
+            assert call(**kw) == ERR_NULL, f"{name}: NULL in position {pos}"
+        for pos in aligned:                                             # the alignment before the scalars
+            assert call(**{f"p{pos}": good[pos] + 8}, **bad_scalar) == ERR_ALIGN, f"{name}: position {pos} off by 8 bytes"
+        for pos, values in scalars.items():
+            for value in values:
+                assert call(**{f"p{pos}": value}) == ERR_RANGE, f"{name}: {value} in position {pos}"
+        assert call(**{f"p{b_pos}": 0}) == 0, f"{name}: B = 0"
+        assert call(**{f"p{b_pos}": 0, f"p{pointers[0]}": None}) == ERR_NULL, f"{name}: B = 0 is checked first"
+    fn, good = table["nt_fused_rollout"][:2]
+    for steps, eps, code in ((-1, nan, ERR_SIZE), ((1 << 30) + 1, nan, ERR_SIZE), (0, 0.3, 0), (0, nan, ERR_RANGE)):
+        args = list(good)
+        args[4], args[5] = steps, eps                                   # steps before epsilon
+        assert fn(*args) == code, f"nt_fused_rollout: steps = {steps}"
+    ok = P.argument_errors(L.q2048_nt_play_rollout, 0x1000, 0x2000, 0x3000, 0x4000)
+    for bit in (N.FLAG_INDEPENDENT, N.FLAG_SYMMETRIC, N.FLAG_SINGLE_ENV, N.FLAG_TD_CAS, N.FLAG_PLAY_ONLY, N.FLAG_NO_LEARN,
+                N.FLAG_NO_NEW_ROWS, N.FLAG_LINE_SUMMARY, 1 << 8, 1 << 23, 1 << 30, 1 << 31):
+        assert ok(flags=bit) == ERR_FLAGS and ok(flags=bit | N.FLAG_ENV_DQN | N.FLAG_RESET_SHAPING) == ERR_FLAGS, bit
+    assert ok(B=0) == 0 and ok(steps=0) == 0
+    assert ok(B=0, boards=None) == ERR_NULL and ok(steps=0, weights=0x3008) == ERR_ALIGN
+    assert ok(B=0, flags=N.FLAG_INDEPENDENT) == ERR_FLAGS
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+def test_refused_calls_write_nothing(pkg, dev):
+    """Each entry point refused for its LAST check (a scalar out of range; a misaligned output where it has no scalar)
+    on real buffers: weights, boards, aux, outputs, statistics and status keep every byte."""
+    L, B = lib(pkg, dev), 64
+    nan = float("nan")
+    V = base_on(dev)
+    boards = t8(dev, K.random_boards(np.random.default_rng(1), B))
+    aux = torch.full((B, 4), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    out = torch.full((B * 4 + 8,), 0x6B6B6B6B, dtype=torch.int32, device=dev)
+    acts = torch.full((B,), 2, dtype=torch.uint8, device=dev)
+    done = torch.zeros(B, dtype=torch.uint8, device=dev)
+    si, sf = torch.full((64,), 7, dtype=torch.int64, device=dev), torch.full((16,), 7.0, dtype=torch.float64, device=dev)
+    status = torch.full((1,), 0x777, dtype=torch.int32, device=dev)
+    everything = (boards, aux, out, acts, done, si, sf, status)
+    before = [t.clone() for t in everything]
+    p = lambda t: t.data_ptr()      # noqa: E731
+    calls = [
+        L.q2048_nt_value(p(V), p(boards), B, p(out) + 8, None),
+        L.q2048_nt_lookup(p(V), p(boards), B, p(out) + 8, None),
+        L.q2048_nt_choose(p(V), p(boards), B, 1.5, 1, 0, 0, p(acts), None),
+        L.q2048_nt_update(p(V), p(boards), p(acts), p(boards), p(done), B, 0.1, nan, p(status), None),
+        L.q2048_nt_fused_rollout(p(boards), p(aux), p(V), B, 3, 0.3, nan, 0.9, 1, 0, 0, p(si), p(sf), p(status), None),
+        L.q2048_nt_play_rollout(p(boards), p(aux), p(V), B, 3, nan, 1, 0, 0, 0, p(si), p(sf), p(status), None),
+        L.q2048_nt_play_rollout(p(boards), p(aux), p(V), B, 3, 0.0, 1, 0, 0, 1 << 8, p(si), p(sf), p(status), None),
+    ]
+    P.sync(dev)
+    assert calls == [ERR_ALIGN, ERR_ALIGN, ERR_RANGE, ERR_RANGE, ERR_RANGE, ERR_RANGE, ERR_FLAGS]
+    for t, b in zip(everything, before):
+        assert torch.equal(t.view(torch.uint8), b.view(torch.uint8)), "a refused call wrote"
+    assert_base_unwritten(dev, "a refused call wrote the weights")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 2. the index definition
+# ---------------------------------------------------------------------------------------------------------------
+ASYM = np.array([1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 1], np.uint8)     # no two images are equal
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+def test_index_definition(pkg, O, dev):
+    """One non-zero entry (p, idx[p][g](ASYM)) in 256 MiB of zeros, for every pattern p and every image g: nt_value of
+    ASYM is exactly that entry's value (every other entry of ASYM reads 0), and it is 0 for the seven other images'
+    entries of every OTHER board in the batch that does not read it.  The batch: ASYM, its transpose, its left-right
+    mirror, and ASYM with the nibbles of pattern p read in reverse order.  This pins the image numbering, the nibble
+    order and which pattern reads which cells: with a transposed or mirrored pattern, another image numbering or a
+    reversed nibble order the entry is read by another board of the batch, or by none.  The same through nt_lookup on
+    a board whose move left gives ASYM."""
+    L = lib(pkg, dev)
+    g4 = ASYM.reshape(4, 4)
+    batch = np.stack([ASYM, g4.T.reshape(16), g4[:, ::-1].reshape(16), g4[::-1].reshape(16)]).astype(np.uint8)
+    idx = model_idx(batch)                                              # [4 boards, 4, 8]
+    assert len({tuple(model_images(ASYM[None])[0, g]) for g in range(8)}) == 8
+    for p in range(4):
+        assert len(set(idx[0, p].tolist())) == 8, "ASYM's eight images read eight entries"
+    src = ASYM.copy()                       # a board whose move left is legal and gives ASYM: no two neighbours merge
+    moved, score, legal = O.move(src, 0)
+    assert not legal
+    src = np.array([1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 0, 13, 14, 15], np.uint8)
+    want_x = np.array([1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 0], np.uint8)
+    moved, score, legal = O.move(src, 0)
+    assert legal and score == 0 and np.array_equal(moved, want_x)
+    idx_x = model_idx(want_x[None])[0]
+    weights = torch.zeros((4, NIDX), dtype=torch.float32, device=dev)
+    seen_by_others = 0
+    for p in range(4):
+        for g in range(8):
+            V = {(p, int(idx[0, p, g])): F32(3.0 + p + 0.125 * g)}
+            (pp, ii), val = next(iter(V.items()))
+            weights[pp, ii] = float(val)
+            got, _ = nt_value(L, dev, weights, batch)
+            want = np.array([sum(val for q in range(4) for h in range(8) if (q, int(idx[b, q, h])) == (pp, ii))
+                             for b in range(4)], F32)
+            assert want[0] == val, "the model reads the entry once on ASYM"
+            seen_by_others += int((want[1:] != 0).sum())
+            assert np.array_equal(got.view(F32), want), f"pattern {p}, image {g}: {got.view(F32).tolist()} != {want.tolist()}"
+            weights[pp, ii] = 0.0
+            # the same entry definition through the lookup: q_0 of `src` is 0 + v(want_x)
+            pp, ii = p, int(idx_x[p, g])
+            weights[pp, ii] = float(val)
+            got, _ = nt_lookup(L, dev, weights, src[None])
+            assert got.view(F32)[0, 0] == val, f"lookup: pattern {p}, image {g}"
+            weights[pp, ii] = 0.0
+    assert seen_by_others > 0, "the transposed and mirrored boards never read ASYM's entries: no teeth"
+    assert not bool(weights.any())
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 3. values, rows and choices
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dev", DEVICES)
+@pytest.mark.parametrize("B", EDGES)
+def test_value_and_lookup_at_the_edges(pkg, O, dev, B):
+    """Random values over all 256 MiB.  nt_value on random cells 0..31: a cell of 16..31 reads the entry of its low
+    nibble.  nt_lookup on random cells 0..15 (two 15s merge into a 16, which aliases to 0 -- the model masks too).
+    The records beyond B keep their canary; the weights are not written."""
+    L, V = lib(pkg, dev), base_values()
+    rng = np.random.default_rng(100 + B)
+    wide = rng.integers(0, 32, size=(B, 16), dtype=np.uint8)
+    wide[0, 6] = 16 + 5
+    want_v = model_v(V, wide)
+    assert_same_bits(want_v, model_v(V, wide & 15), "the model's own mask")
+    weights = base_on(dev)
+    got, tail = nt_value(L, dev, weights, wide)
+    assert_same_bits(got.view(F32), want_v, f"values, B = {B}")
+    assert (tail == np.uint32(Q_CANARY)).all(), "values written beyond B"
+
+    boards = K.random_boards(rng, B)
+    q, legal, moved = model_eval(O, V, boards)
+    got, tail = nt_lookup(L, dev, weights, boards)
+    assert_same_bits(got.view(F32), q, f"rows, B = {B}")
+    assert (tail == np.uint32(Q_CANARY)).all(), "rows written beyond B"
+    if B >= 63:      # teeth: the row is neither v(s) four times nor v(c_a) without the score
+        v_s = model_v(V, boards)
+        assert (bits(q) != bits(v_s)[:, None]).all(axis=1).any() and model_moves(O, boards)[1].max() > 0
+    if B == EDGES[-1]:
+        assert_base_unwritten(dev, "a lookup wrote the weights")
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+def test_lookup_on_boards_with_one_move_none_and_merges(pkg, O, dev):
+    """Exactly one legal move (the three others give 0 + v(s) bit for bit), no legal move (four times v(s)), and moves
+    that merge: score_a is added and v is read at the moved board, not at s.  The same boards through nt_choose at
+    epsilon 0 and 1: the one legal move, or action 0 where there is none."""
+    L, V = lib(pkg, dev), base_values()
+    boards = AV.special_boards()
+    moved, score, legal = model_moves(O, boards)
+    assert [int(x.sum()) for x in legal[:5]] == [1, 1, 1, 1, 0] and [int(np.argmax(x)) for x in legal[:4]] == [0, 1, 2, 3]
+    assert score[5].tolist() == [16, 16, 16, 16] and score[6, 0] == 64 + 128 + 256
+    q, _, _ = model_eval(O, V, boards)
+    v_s = model_v(V, boards)
+    assert (bits(q)[~legal] == np.broadcast_to(bits(v_s)[:, None], q.shape)[~legal]).all()
+    assert (bits(q[5]) != bits(F32(16.0) + v_s[5])).all(), "the merging moves do not tell c_a from s"
+    weights = base_on(dev)
+    got, _ = nt_lookup(L, dev, weights, boards)
+    assert_same_bits(got.view(F32), q, "special boards")
+    want = model_greedy(q, legal)
+    for eps in (0.0, 1.0):
+        got, tail = nt_choose(L, dev, weights, boards[:5], eps, 3, 9, 1)
+        assert got.tolist() == want[:5].tolist() == [0, 1, 2, 3, 0], f"epsilon = {eps}"
+        assert (tail == A_CANARY).all()
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+def test_65536_boards(pkg, O, dev):
+    """256 full blocks of mid-game boards (hot entries shared by most of the batch, as in a rollout): values and rows bit
+    for bit, greedy actions equal, and the read-only pass leaves V bit-identical."""
+    L, V = lib(pkg, dev), base_values()
+    boards, moves = AV.midgame(O)
+    q, legal, _ = model_eval(O, V, boards, moves)
+    weights = base_on(dev)
+    got, tail = nt_value(L, dev, weights, boards)
+    assert_same_bits(got.view(F32), model_v(V, boards), "65,536 values")
+    assert (tail == np.uint32(Q_CANARY)).all()
+    got, tail = nt_lookup(L, dev, weights, boards)
+    assert_same_bits(got.view(F32), q, "65,536 rows")
+    assert (tail == np.uint32(Q_CANARY)).all(), "rows written beyond B"
+    greedy = model_greedy(q, legal).astype(np.uint8)
+    assert np.bincount(greedy, minlength=4).min() > 0 and (~legal).any()
+    got, tail = nt_choose(L, dev, weights, boards, 0.0, 41, 0, 40)
+    assert np.array_equal(got, greedy), f"{int((got != greedy).sum())} greedy actions differ"
+    assert (tail == A_CANARY).all(), "actions written beyond B"
+    assert_base_unwritten(dev, "a read-only pass wrote the weights")
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+def test_choose_greedy_ties_and_illegal_maxima(pkg, O, dev):
+    """(a) Zero values: q_a = score_a exactly, so legal moves tie two, three and four ways at the maximum (counted from
+    the model); the first legal maximum wins.  (b) Random values with +50 planted on the 32 entries of s on lanes that
+    have an illegal move: the illegal moves read 0 + v(s) = the largest q of the row, and must not be played."""
+    L, B = lib(pkg, dev), 1000
+    boards = AV.midgame(O)[0][:B]
+    moves = tuple(m[:B] for m in AV.midgame(O)[1])
+    score, legal = moves[1], moves[2]
+    q = score.astype(F32)                                               # the model on zero values: 0 + score
+    top = np.where(legal, q, -np.inf)
+    ties = ((top == top.max(axis=1, keepdims=True)) & legal).sum(axis=1)
+    assert (ties == 2).sum() > 10 and (ties == 3).sum() > 10 and (ties == 4).sum() > 10     # (a unique maximum: part (b))
+    want = model_greedy(q, legal)
+    assert (want[ties == 2] > 0).any(), "every two-way tie is won by action 0"
+    weights = torch.zeros((4, NIDX), dtype=torch.float32, device=dev)
+    got, tail = nt_choose(L, dev, weights, boards, 0.0)
+    assert np.array_equal(got, want) and (tail == A_CANARY).all()
+
+    lanes = np.flatnonzero(~legal.all(axis=1) & legal.any(axis=1))[:40]
+    idx = model_idx(boards)
+    planted = {}                            # zeros elsewhere: the model below reads a sparse V through a dense twin
+    for i in lanes:
+        for p in range(4):
+            for g in range(8):
+                planted[(p, int(idx[i, p, g]))] = F32(50.0)
+    V = np.zeros((4, NIDX), F32)
+    for (p, ii), val in planted.items():
+        V[p, ii] = val
+        weights[p, ii] = float(val)
+    q, legal, _ = model_eval(O, V, boards, moves)
+    want = model_greedy(q, legal)
+    held = [i for i in lanes if not legal[i, int(np.argmax(q[i]))]]
+    assert len(held) > 10, "too few lanes whose largest q belongs to an illegal move"
+    got, _ = nt_choose(L, dev, weights, boards, 0.0)
+    assert np.array_equal(got, want)
+    assert all(legal[i, got[i]] for i in held)
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+@pytest.mark.parametrize("B", EDGES)
+def test_choose_at_the_edges(pkg, O, dev, B):
+    """epsilon = 0: the model's first legal maximum.  epsilon = 0.3 with (seed, env_id0, ctr) = (7, 2^33 + 5, 3): the
+    player's draw contract (`model_actions` of the row-tuple player's test) on this learner's rows."""
+    L, V = lib(pkg, dev), base_values()
+    boards = AV.midgame(O)[0][1000:1000 + B]
+    moves = tuple(m[1000:1000 + B] for m in AV.midgame(O)[1])
+    q, legal, _ = model_eval(O, V, boards, moves)
+    weights = base_on(dev)
+    greedy = model_greedy(q, legal).astype(np.uint8)
+    got, tail = nt_choose(L, dev, weights, boards, 0.0)
+    assert np.array_equal(got, greedy), f"greedy actions differ on lanes {np.flatnonzero(got != greedy)[:8].tolist()}"
+    assert (tail == A_CANARY).all(), "actions written beyond B"
+    eps, seed, id0, ctr = 0.3, 7, (1 << 33) + 5, 3
+    want, explored = P.model_actions(O, q, mask_of(legal), seed, id0, ctr, eps)
+    if B >= 63:
+        assert 0 < explored < B and (want != greedy).any()
+    got, tail = nt_choose(L, dev, weights, boards, eps, seed, id0, ctr)
+    assert np.array_equal(got, want), f"actions differ on lanes {np.flatnonzero(got != want)[:8].tolist()}"
+    assert (tail == A_CANARY).all(), "actions written beyond B"
+    if B == EDGES[-1]:
+        assert_base_unwritten(dev, "choosing wrote the weights")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 4. boards with a symmetry: several of the 32 entries are the same weight
+# ---------------------------------------------------------------------------------------------------------------
+def symmetric_cases():
+    """(name, board, distinct entries among its 32).  The count follows from the definition: a board that g images map
+    onto itself has 8 / g distinct images, so at most 4 * 8 / g distinct entries -- 4 for the empty board and for any
+    board invariant under all eight images, 8 under a four-element subgroup, 16 under one mirror."""
+    full = np.array([1, 2, 2, 1, 2, 3, 3, 2, 2, 3, 3, 2, 1, 2, 2, 1], np.uint8)      # all eight images
+    four = np.array([1, 2, 2, 1, 3, 4, 4, 3, 3, 4, 4, 3, 1, 2, 2, 1], np.uint8)      # both mirrors and the half turn
+    lr = np.array([5, 6, 6, 5, 7, 8, 8, 7, 9, 10, 10, 9, 0, 0, 0, 0], np.uint8)      # the left-right mirror only
+    diag = np.array([11, 12, 13, 14, 12, 15, 11, 0, 13, 11, 0, 0, 14, 0, 0, 0], np.uint8)   # the transpose only
+    return [("empty", np.zeros(16, np.uint8), 4), ("all eight images", full, 4), ("four images", four, 8),
+            ("one mirror", lr, 16), ("the transpose", diag, 16)]
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+def test_symmetric_boards(pkg, O, dev):
+    """nt_value on boards with a symmetry: the model's sum counts an entry once per occurrence, and so must the kernel.
+    The distinct entries among the 32 are counted from the model: 4 for the empty board, 4 for a board that all eight
+    images map onto itself (its images are one board, so each pattern reads one entry: the count cannot be 8), 8 for
+    one invariant under four images, 16 under one mirror.
+    nt_update: only a board with ONE mirror can be the afterstate of a legal move (a board that its half turn maps
+    onto itself is full or empty once it is packed towards an edge, and a full row does not move), so the TD step is
+    checked on three such afterstates -- mirrored left-right, mirrored top-bottom (the move left of the board
+    invariant under all eight images) and transposed -- one lane per call, and the empty and the eight-fold boards go
+    through it as s: no write for the empty board.  After the update exactly as many weights differ from the base as the afterstate
+    has distinct entries, each by d ONCE, and everything else of the 256 MiB is unchanged."""
+    L, V = lib(pkg, dev), base_values()
+    cases = symmetric_cases()
+    boards = np.stack([b for _, b, _ in cases])
+    ids = entry_ids(boards)
+    for (name, b, n), row in zip(cases, ids):
+        assert len(set(row.tolist())) == n, f"{name}: {len(set(row.tolist()))} distinct entries"
+        n_img = len({tuple(i) for i in model_images(b[None])[0]})
+        assert n_img * 4 >= n
+    got, _ = nt_value(L, dev, base_on(dev), boards)
+    assert_same_bits(got.view(F32), model_v(V, boards), "values of symmetric boards")
+    got, _ = nt_lookup(L, dev, base_on(dev), boards)
+    assert_same_bits(got.view(F32), model_eval(O, V, boards)[0], "rows of symmetric boards")
+
+    # transitions: (s, a) and the afterstate's symmetry
+    s = np.stack([
+        np.array([5, 6, 6, 5, 7, 8, 8, 7, 0, 0, 0, 0, 9, 10, 10, 9], np.uint8),      # up -> mirrored left-right
+        cases[1][1],                                                                  # left: 2,2 and 3,3 merge -> mirrored top-bottom
+        np.array([11, 12, 13, 14, 0, 12, 15, 11, 0, 13, 0, 11, 0, 0, 14, 0], np.uint8),   # left -> its own transpose
+        np.zeros(16, np.uint8),                                                       # the empty board: nothing moves
+    ])
+    actions = np.array([1, 0, 0, 2], np.uint8)
+    x = [O.move(s[i], int(actions[i])) for i in range(4)]
+    assert [bool(r[2]) for r in x] == [True, True, True, False]
+    assert np.array_equal(x[0][0], cases[3][1]) and np.array_equal(x[2][0], cases[4][1])
+    g1 = x[1][0].reshape(4, 4)
+    assert np.array_equal(g1, g1[::-1]) and not np.array_equal(g1, g1[:, ::-1]) and x[1][1] > 0
+    rng = np.random.default_rng(41)
+    s2 = np.stack([AV.spawned(rng, x[i][0]) for i in range(4)])
+    done = np.zeros(4, np.uint8)
+    lr, gamma = 0.1, 0.97
+    want, _, written = model_update(O, V, s, actions, s2, done, lr, gamma)
+    entries = [{(p, int(i)) for p in range(4) for i in written[k, p]} for k in range(3)]
+    distinct = [len(e) for e in entries]
+    assert distinct == [16, 16, 16] and (written[3] == -1).all()
+    assert len(entries[0] | entries[1] | entries[2]) == sum(distinct), "the three afterstates share no entry"
+    changed = np.argwhere(bits(want) != bits(V))
+    assert len(changed) == sum(distinct), "each distinct weight moves, once"
+    for k in range(3):                                                   # ... by d, not by a multiple of it
+        d = F32((lr * 0.03125) * ((gamma * float(model_best(*model_eval(O, V, s2[k:k + 1])[:2])[0]))
+                                  - float(model_v(V, x[k][0][None])[0])))
+        pp = np.arange(4)[:, None]
+        assert np.array_equal(bits(want[pp, written[k]]), bits(V[pp, written[k]] + d)) and d != 0
+
+    weights, status = t32(dev, V), torch.zeros(1, dtype=torch.int32, device=dev)
+    for k in range(4):       # one lane per call, in the model's order: sparse boards share entries (index 0 of every pattern)
+        ts, ts2, ta, td = t8(dev, s[k:k + 1]), t8(dev, s2[k:k + 1]), t8(dev, actions[k:k + 1]), t8(dev, done[k:k + 1])
+        assert L.q2048_nt_update(weights.data_ptr(), ts.data_ptr(), ta.data_ptr(), ts2.data_ptr(), td.data_ptr(), 1, lr,
+                                 gamma, status.data_ptr(), None) == 0
+    assert int(status.item()) == 0
+    assert_same_bits(weights, want, "the TD step on symmetric afterstates")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 5. nt_update where lanes cannot race
+# ---------------------------------------------------------------------------------------------------------------
+MAX_CANDIDATES = 3000
+
+
+def nonracing_transitions(O, rng, B):
+    """At most 3,000 candidate transitions from test_afterstate's `crowded` boards, built as there -- s a board, a
+    uniform (every 7th candidate 7, a bad action; every 11th a board with one legal move and another action), s' = the
+    moved board with a spawn (s itself for an illegal move; every 5th candidate the dead board) -- accepted lane by
+    lane under its rule: the write set is disjoint from every earlier read and write set and the read set from every
+    earlier write set.  Entry ids are p * 2^24 + idx."""
+    boards = AV.crowded()
+    order = rng.permutation(len(boards))[:MAX_CANDIDATES]
+    s, a, s2 = [], [], []
+    for n, c in enumerate(order):
+        board = boards[c]
+        act = 7 if n % 7 == 3 else int(rng.integers(0, 4))
+        if n % 11 == 5:
+            board, act = P.one_move_board(n % 4), (n + 1) % 4
+        x = O.move(board, act)[0] if act <= 3 else board
+        s.append(board); a.append(act)      # noqa: E702
+        s2.append(P.DEAD.numpy().copy() if n % 5 == 2 else AV.spawned(rng, x))
+    s, a, s2 = np.stack(s), np.array(a, np.uint8), np.stack(s2)
+    keep, seen_r, seen_w = [], set(), set()
+    for i, (r, w) in enumerate(entry_sets_many(O, s, a.astype(np.int64), s2)):
+        if (w & seen_r) or (r & seen_w):
+            continue
+        seen_r |= r
+        seen_w |= w
+        keep.append(i)
+        if len(keep) == B:
+            break
+    return s[keep], a[keep], s2[keep]
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+@pytest.mark.parametrize("B", [65, 257, 1000])
+def test_update_where_lanes_cannot_race(pkg, O, dev, B):
+    """No lane reads or writes an entry another lane writes (by construction, asserted), so the result does not depend
+    on the order of the lanes and the sequential model is the specification.  All 256 MiB are compared: the distinct
+    entries of each lane with a legal action moved, none for an illegal or a bad action (both present); done = 1 and a
+    dead s' both give target 0 (both present, and both told from the live target by the model).  The B lanes are found
+    among at most 3,000 candidates."""
+    L, V = lib(pkg, dev), base_values()
+    rng = np.random.default_rng(300 + B)
+    s, actions, s2 = nonracing_transitions(O, rng, B)
+    assert len(s) == B, f"only {len(s)} lanes that cannot race among {MAX_CANDIDATES} candidates"
+    assert not conflicts(entry_sets_many(O, s, actions.astype(np.int64), s2))
+    done = (rng.random(B) < 0.3).astype(np.uint8)
+    lr, gamma = 0.1, 0.97
+    want, want_status, written = model_update(O, V, s, actions, s2, done, lr, gamma)
+    wrote = written[:, 0, 0] >= 0
+    bad = actions > 3
+    illegal = ~wrote & ~bad
+    dead = (s2 == P.DEAD.numpy()).all(axis=1)
+    assert bad.any() and illegal.any() and want_status == BAD_ACTION
+    assert (wrote & (done == 1)).any() and (wrote & dead & (done == 0)).any() and (wrote & ~dead & (done == 0)).any()
+    n_entries = sum(len(set((written[i] + (np.arange(4) * NIDX)[:, None]).ravel().tolist())) for i in np.flatnonzero(wrote))
+    n_changed = int(np.count_nonzero(bits(want) != bits(V)))
+    assert n_changed == n_entries
+    alive, _, _ = model_update(O, V, s, actions, s2, np.zeros(B, np.uint8), lr, gamma)
+    assert not np.array_equal(bits(alive), bits(want)), "done does not show"
+    del alive
+
+    weights, status = t32(dev, V), torch.zeros(1, dtype=torch.int32, device=dev)
+    ts, ts2, ta, td = t8(dev, s), t8(dev, s2), t8(dev, actions), t8(dev, done)
+    assert L.q2048_nt_update(weights.data_ptr(), ts.data_ptr(), ta.data_ptr(), ts2.data_ptr(), td.data_ptr(), B, lr, gamma,
+                             status.data_ptr(), None) == 0
+    assert int(status.item()) == want_status
+    assert_same_bits(weights, want, f"B = {B}")
+    for t, a in ((ts, s), (ts2, s2), (ta, actions), (td, done)):
+        assert np.array_equal(t.cpu().numpy(), a), "an input was written"
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 6. the fused learner against the four-call loop of the same agent class
+# ---------------------------------------------------------------------------------------------------------------
+def fused_run(pkg, dev, V, B, launches, seed, id0, eps, lr, gamma, boards=None):
+    env = pkg.BatchedGame2048Env(B, seed=seed, env_id0=id0, device=dev)
+    agent = make_agent(pkg, dev, eps, lr, gamma, seed, id0)
+    agent.weights.copy_(t32("cpu", V))
+    if boards is not None:
+        env.boards.copy_(torch.from_numpy(boards))
+    for k in launches:
+        agent.fused_rollout(env, k)
+    assert agent.check_status() == 0
+    return env, agent
+
+
+def four_call_run(pkg, O, dev, V, B, steps, seed, id0, eps, lr, gamma, boards=None, learn=False, keep=False):
+    """choose_action -> env.step -> (model_update on V, its written entries mirrored into the agent) -> env.reset(done),
+    `steps` times: the loop the fused learner replaces, on entry points the tests above have pinned to the model.  V is
+    updated IN PLACE when `learn` (the caller hands in a copy).
+    -> (env, the statistics the fused learner counts, the transitions)"""
+    env = pkg.BatchedGame2048Env(B, seed=seed, env_id0=id0, device=dev)
+    agent = make_agent(pkg, dev, eps, lr, gamma, seed, id0)
+    agent.weights.copy_(t32("cpu", V))
+    if boards is not None:
+        env.boards.copy_(torch.from_numpy(boards))
+    thr = 0 if eps <= 0.0 else int(np.ceil(eps * 4294967296.0))
+    st = {"steps": 0, "episodes": 0, "valid_moves": 0, "explored": 0, "score_sum": 0}
+    trans = []
+    pp = np.arange(4)[:, None]
+    for t in range(steps):
+        s = env.boards.cpu().numpy().copy()
+        has_move = env.legal_moves().cpu().numpy() != 0
+        actions = agent.choose_action(env.boards)
+        s2, _, done, _ = env.step(actions)
+        s2, a, d = s2.cpu().numpy().copy(), actions.cpu().numpy(), done.cpu().numpy().copy()
+        st["steps"] += B
+        st["episodes"] += int(d.sum())
+        st["valid_moves"] += int((s != s2).any(axis=1).sum())            # a move that changes the board, spawn included
+        st["score_sum"] += int(env.score.cpu().numpy()[d].sum())
+        if eps > 0.0 and not keep:                                       # explored: the draw is below, and a move exists
+            st["explored"] += sum(int(O.draws(seed, id0 + i, t)[0]) < thr and bool(has_move[i]) for i in range(B))
+        if learn:
+            _, _, written = model_update(O, V, s, a, s2, d, lr, gamma, inplace=True)
+            for i in np.flatnonzero(written[:, 0, 0] >= 0):
+                agent.weights[torch.from_numpy(pp), torch.from_numpy(written[i])] = torch.from_numpy(V[pp, written[i]]).to(dev)
+            trans.append((s, a, s2, d, written))
+        elif keep:
+            trans.append((s, a, s2, d, None))
+        env.reset(done)
+    return env, st, trans
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+@pytest.mark.parametrize("B,steps,eps", [(257, 100, 0.3), (1000, 100, 0.0)])
+def test_fused_rollout_with_frozen_weights(pkg, O, dev, B, steps, eps):
+    """learning_rate = 0: every lane is a function of V alone, so the four-call loop is the specification at any batch
+    size.  Launches of 1 and steps - 1 steps.  Boards, aux records and statistics equal the loop's; the values are bit
+    for bit what was loaded (a write of gathered + 0.0 stores the gathered bits; the base holds no -0.0 that d = +0.0
+    could turn).  Teeth: on zero values the same run ends on other boards in more than half of the lanes."""
+    seed, id0, gamma = 17, 1000, 0.97
+    V = base_values()
+    env_loop, st_loop, _ = four_call_run(pkg, O, dev, V, B, steps, seed, id0, eps, 0.0, gamma)
+    env, agent = fused_run(pkg, dev, V, B, (1, steps - 1), seed, id0, eps, 0.0, gamma)
+    st = LT.assert_same_run(env, agent, env_loop, st_loop, f"B = {B}")
+    assert st["episodes"] > 0 and (st["explored"] == 0) == (eps == 0.0)
+    assert_same_bits(agent.weights, V, "frozen values were written")
+    agent.weights.zero_()
+    env0 = pkg.BatchedGame2048Env(B, seed=seed, env_id0=id0, device=dev)
+    agent.ctr = 0
+    agent.fused_rollout(env0, 1)
+    agent.fused_rollout(env0, steps - 1)
+    differ = int((env0.boards.cpu() != env.boards.cpu()).any(dim=1).sum())
+    print(f"zero values end on other boards in {differ} of {B} lanes")
+    assert differ > B // 2, f"the values decide the boards of only {differ} of {B} lanes"
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+def test_fused_rollout_one_lane_many_steps(pkg, O, dev):
+    """RE-READING.  B = 1, lr 0.1, gamma 0.97, epsilon 0.3, 300 steps in launches of 1, 63 and 236: one lane is the
+    sequential learner, so the expected values are model_update applied step by step to the transitions of the
+    four-call loop (the draws make them the same transitions).  All 256 MiB bit for bit, boards, aux and statistics
+    equal.  Every evaluation the lane makes must see its own earlier writes: the test counts, from the model, the steps
+    (not done) on which a candidate of s' reads an entry the TD step of that step writes -- the next step's evaluation
+    of s' as s then differs from one made before the write -- per pattern, and needs such a step for two different
+    patterns at least."""
+    seed, id0, eps, lr, gamma, cuts = 5, 77, 0.3, 0.1, 0.97, (1, 63, 236)
+    want = base_values().copy()
+    env_loop, st_loop, trans = four_call_run(pkg, O, dev, want, 1, sum(cuts), seed, id0, eps, lr, gamma, learn=True)
+    per_pattern = np.zeros(4, np.int64)
+    for s, a, s2, d, written in trans:
+        if d[0] or written[0, 0, 0] < 0:
+            continue
+        cand = model_idx(model_moves(O, s2)[0][0])                                   # [4 candidates, 4, 8]
+        for p in range(4):
+            per_pattern[p] += bool(np.isin(cand[:, p, :], written[0, p]).any())
+    print(f"steps on which an entry of s' was written by the TD step, per pattern: {per_pattern.tolist()}; "
+          f"episodes {st_loop['episodes']}")
+    assert (per_pattern > 0).sum() >= 2 and st_loop["episodes"] > 0
+    env, agent = fused_run(pkg, dev, base_values(), 1, cuts, seed, id0, eps, lr, gamma)
+    LT.assert_same_run(env, agent, env_loop, st_loop, "B = 1")
+    assert_same_bits(agent.weights, want, "300 sequential steps")
+    assert np.count_nonzero(bits(want) != bits(base_values())) > 300
+
+
+def nonracing_boards(pkg, O, V, B, seed, id0, eps):
+    """Boards for one fused learning step whose lanes cannot race, found as test_afterstate finds them (on the CPU
+    twin, once: both devices get the same boards): B `crowded` boards, one step of the four-call loop with lr = 0, the
+    lanes that conflict with an earlier lane under the acceptance rule WITH THE FUSED READ SET (candidates of s and of
+    s') get fresh boards, until none conflicts -- within 3,000 candidates."""
+    if ("nonracing", B) in _SHARED:
+        return _SHARED[("nonracing", B)]
+    pool = AV.crowded()
+    nxt = B
+    boards = pool[:B].copy()
+    sets, fresh = [None] * B, range(B)
+    for _ in range(400):
+        _, _, trans = four_call_run(pkg, O, "cpu", V, B, 1, seed, id0, eps, 0.0, 0.0, boards=boards, keep=True)
+        s, a, s2, _, _ = trans[0]
+        fresh = list(fresh)
+        for i, rw in zip(fresh, entry_sets_many(O, s[fresh], a[fresh].astype(np.int64), s2[fresh], fused=True)):
+            sets[i] = rw
+        fresh = conflicts(sets)
+        if not fresh:
+            _SHARED[("nonracing", B)] = boards
+            return boards
+        assert nxt + len(fresh) <= MAX_CANDIDATES, f"more than {MAX_CANDIDATES} candidates for {B} lanes"
+        boards[fresh] = pool[nxt:nxt + len(fresh)]
+        nxt += len(fresh)
+    raise AssertionError("no set of lanes that cannot race was found")
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+@pytest.mark.parametrize("B", [65, 257, 1000])
+def test_fused_rollout_one_learning_step(pkg, O, dev, B):
+    """One learning step (lr 0.1, gamma 0.97, epsilon 0.3) on lanes that cannot race: model_update on the transitions of
+    the four-call loop is the specification.  All 256 MiB bit for bit; boards, aux and statistics equal."""
+    seed, id0, eps, lr, gamma = 23, 4000, 0.3, 0.1, 0.97
+    boards = nonracing_boards(pkg, O, base_values(), B, seed, id0, eps)
+    want = base_values().copy()
+    env_loop, st_loop, trans = four_call_run(pkg, O, dev, want, B, 1, seed, id0, eps, lr, gamma, boards=boards, learn=True)
+    wrote = int((trans[0][4][:, 0, 0] >= 0).sum())
+    assert wrote > B // 2 and 0 < st_loop["explored"] < B
+    assert np.count_nonzero(bits(want) != bits(base_values())) >= 16 * wrote
+    env, agent = fused_run(pkg, dev, base_values(), B, (1,), seed, id0, eps, lr, gamma, boards=boards)
+    LT.assert_same_run(env, agent, env_loop, st_loop, f"B = {B}")
+    assert_same_bits(agent.weights, want, f"B = {B}")
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+def test_racing_learning_at_65536_boards_properties(pkg, O, dev):
+    """65,536 lanes, epsilon = 1, 4 steps in launches of 1 + 3: an exploring choice does not read the values, so the
+    trajectories are exact whatever the racing writes do and equal those of the four-call loop (lr = 0).  From its
+    transitions and the oracle's move: the entries some lane's afterstate visited.  The values stay finite, ONLY
+    visited entries change, and every step, valid move and exploration is counted."""
+    B, steps, seed = 65536, 4, 31
+    env = pkg.BatchedGame2048Env(B, seed=seed, device=dev)
+    agent = make_agent(pkg, dev, eps=1.0, lr=0.05, gamma=0.9, seed=seed, id0=0)
+    agent.fused_rollout(env, 1)
+    agent.fused_rollout(env, steps - 1)
+    loop_env = pkg.BatchedGame2048Env(B, seed=seed, device=dev)
+    loop = agent.__class__.__new__(agent.__class__)      # the same weights serve the loop: an exploring choice reads none
+    loop.__dict__.update(agent.__dict__)
+    loop.schedule, loop.ctr = type(agent.schedule)(100, 1.0, 0.01), 0
+    visited = np.zeros(4 * NIDX, bool)
+    valid = explored = 0
+    for _ in range(steps):
+        s = loop_env.boards.cpu().numpy().copy()
+        explored += int((loop_env.legal_moves() != 0).sum())
+        a = loop.choose_action(loop_env.boards)
+        _, _, done, _ = loop_env.step(a)
+        a = a.cpu().numpy()
+        moved, _, legal = model_moves(O, s)
+        took = legal[np.arange(B), a]
+        valid += int(took.sum())
+        visited[entry_ids(moved[np.arange(B), a][took]).ravel()] = True
+        loop_env.reset(done)
+    P.sync(dev)
+    assert torch.equal(env.boards, loop_env.boards) and torch.equal(env.aux, loop_env.aux)
+    st = agent.stats()
+    assert st["steps"] == B * steps and st["valid_moves"] == valid and st["explored"] == explored == valid
+    v = agent.weights.cpu().numpy().ravel()
+    changed = np.flatnonzero(v)
+    assert np.isfinite(v[changed]).all() and np.abs(v[changed]).max() < 1e4
+    assert len(changed) and visited[changed].all(), "an entry no lane visited was written"
+    assert len(changed) > int(visited.sum()) // 2 and agent.check_status() == 0
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 7. the player
+# ---------------------------------------------------------------------------------------------------------------
+def random_agent(pkg, dev, **kw):
+    agent = make_agent(pkg, dev, **kw)
+    agent.weights = base_on(dev)            # only read by what follows; each test asserts so
+    return agent
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+@pytest.mark.parametrize("B", [65, 1000])
+@pytest.mark.parametrize("profile,rss", [("shaped", False), ("shaped", True), ("nopenalty", False), ("nopenalty", True)])
+def test_player_equals_the_four_call_loop(pkg, O, dev, profile, rss, B):
+    """Mid-game boards with dead boards planted in front, then 200 steps played twice: by play_rollout in launches of
+    1 + 63 + 136 and by the four-call loop (nt_lookup, legal_moves, env step, env reset) on a second env with the same
+    boards, seed and counter, on the same agent.  Boards, aux, every statistic and all 256 MiB of V (unchanged) are
+    compared; `status` is never written and the training statistics never see the player."""
+    env, dead = AV.midgame_env(pkg, dev, B, profile, rss)
+    agent = random_agent(pkg, dev)
+    q = agent.q_values(env.boards).cpu().numpy()
+    mq, mlegal, _ = model_eval(O, base_values(), env.boards.cpu().numpy())
+    assert_same_bits(q, mq, "the row's definition")
+    legal = env.legal_moves().cpu().numpy()
+    assert np.array_equal(legal, mask_of(mlegal)) and int(((legal >> q.argmax(1)) & 1 == 0).sum()) > 0
+    env_loop = P.twin_of(pkg, env)
+    agent.status.fill_(0x777)
+    train_stats = agent.stats_i.clone(), agent.stats_f.clone()
+    for c in P.CUTS:
+        agent.play_rollout(env, c)
+    st_loop = P.four_call_loop(agent, env_loop, sum(P.CUTS))
+    P.sync(dev)
+    st = agent.play_stats()
+    assert torch.equal(env.boards, env_loop.boards), "boards differ"
+    assert torch.equal(env.aux, env_loop.aux), "aux records differ"
+    assert env.ctr == env_loop.ctr == P.WARM + sum(P.CUTS)
+    assert st["steps"] == st_loop["steps"] == B * sum(P.CUTS) and st["valid_moves"] == st_loop["valid_moves"]
+    assert st["episodes"] == st_loop["episodes"] and st["max_tile_hist"] == st_loop["max_tile_hist"]
+    assert st["score_sum"] == round(st_loop["mean_score"] * st_loop["episodes"])
+    assert st["explored"] == 0 and st["inserts"] == 0 and st["drops"] == 0
+    assert_base_unwritten(dev, "the player wrote to the weights")
+    assert torch.equal(agent.stats_i, train_stats[0]) and torch.equal(agent.stats_f, train_stats[1])
+    assert int(agent.status.item()) == 0x777, "status: required, never written"
+    assert st["episodes"] >= B and st["episodes"] >= dead, "the span must cover the reset path"
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+def test_player_exploration_against_a_model(pkg, O, dev):
+    """epsilon = 0.3 against the numpy model of the player's draw contract on the model's rows, through where the actions
+    lead: boards, aux, explored and valid counts."""
+    B, steps, eps = 257, 40, 0.3
+    env, _ = AV.midgame_env(pkg, dev, B, dead=3)
+    agent = random_agent(pkg, dev)
+    model = P.twin_of(pkg, env)
+    agent.play_rollout(env, 15, epsilon=eps)
+    agent.play_rollout(env, steps - 15, epsilon=eps)
+    explored = valid = 0
+    for _ in range(steps):
+        q, legal, _ = model_eval(O, base_values(), model.boards.cpu().numpy())
+        acts, e = P.model_actions(O, q, mask_of(legal), model.seed, model.env_id0, model.ctr, eps)
+        explored += e
+        valid += int(legal.any(axis=1).sum())
+        _, _, done, _ = model.step(torch.from_numpy(acts).to(dev))
+        model.reset(done)
+    P.sync(dev)
+    st = agent.play_stats()
+    assert torch.equal(env.boards, model.boards) and torch.equal(env.aux, model.aux)
+    assert st["explored"] == explored and st["valid_moves"] == valid and st["steps"] == B * steps
+    assert 0.2 * B * steps < explored < 0.4 * B * steps
+    assert_base_unwritten(dev, "the player wrote to the weights")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 8. checkpoint and the Python surface
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dev", DEVICES)
+def test_checkpoint_resumes_the_run(pkg, dev):
+    """state_dict -> load_state_dict round-trips bit for bit, and 120 steps, a checkpoint, a fresh agent and env, 80
+    more == 200 uninterrupted steps at B = 1 in all of V, boards, aux, statistics, counters and epsilon."""
+    def run(cuts):
+        env = P.make_env(pkg, dev, 1)
+        agent = make_agent(pkg, dev, eps=0.9, epochs=10)
+        for k, steps in enumerate(cuts):
+            agent.fused_rollout(env, steps)
+            agent.decay_exploration(k)
+            yield env, agent
+
+    for env, agent in run([120, 80]):
+        pass
+    whole = P.learner_state(agent, env)
+    del agent
+    (env1, agent1), = run([120])
+    sd, esd = agent1.state_dict(), env1.state_dict()
+    assert sd["kind"] == "ntuple6_afterstate" and sd["board_size"] == 4 and sd["weights"].device.type == "cpu"
+    assert sd["weights"].dtype == torch.float32 and tuple(sd["weights"].shape) == (4, NIDX)
+    assert set(sd) >= {"lr", "gamma", "schedule", "seed", "env_id0", "ctr", "stats_i", "stats_f"}
+    assert all(bool(sd["weights"][p].any()) for p in range(4))
+    env2 = P.make_env(pkg, dev, 1, seed=1, id0=2)
+    agent2 = make_agent(pkg, dev, eps=0.1, seed=1, id0=2, epochs=10)
+    agent2.load_state_dict(sd)
+    env2.load_state_dict(esd)
+    P.assert_same_state(P.learner_state(agent2, env2), P.learner_state(agent1, env1))      # the round trip
+    del agent1, sd
+    agent2.fused_rollout(env2, 80)
+    agent2.decay_exploration(1)
+    P.sync(dev)
+    P.assert_same_state(P.learner_state(agent2, env2), whole)
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+def test_a_wrong_checkpoint_writes_nothing(pkg, dev):
+    """Every other kind, shape and dtype is refused before anything is written, nothing is promoted, and the four other
+    agents refuse a 6-tuple checkpoint, name its class and keep their state."""
+    env, agent = P.make_env(pkg, dev, 64), make_agent(pkg, dev)
+    agent.fused_rollout(env, 20)
+    good = agent.state_dict()
+    before = P.learner_state(agent, env)
+    rt, lt, av = P.make_agent(pkg, dev), LT.make_agent(pkg, dev), AV.make_agent(pkg, dev)
+    ht = pkg.BatchedQLearningAgent(10, capacity_log2=12, device="cpu", placement="plain")
+    rt_sd, lt_sd, av_sd = rt.state_dict(), lt.state_dict(), av.state_dict()
+    marked = dict(good, ctr=999, stats_i=good["stats_i"] + 1)
+    small = good["weights"][:, :4096]
+    wrong = [dict(marked, weights=small), dict(marked, weights=good["weights"][:2]),
+             dict(marked, weights=good["weights"].view(torch.int32)), dict(marked, weights=good["weights"].numpy()),
+             dict(marked, weights=good["weights"].reshape(8, NIDX // 2)),
+             dict(marked, board_size=5), dict(marked, stats_i=marked["stats_i"].int()),
+             dict(marked, stats_f=marked["stats_f"][:2]), {k: v for k, v in marked.items() if k != "kind"},
+             dict(marked, kind="row_tuple"), dict(marked, kind="line_tuple"), dict(marked, kind="line_afterstate"),
+             dict(rt_sd, ctr=999), dict(lt_sd, ctr=999), dict(av_sd, ctr=999),
+             dict(av_sd, kind="ntuple6_afterstate"), ht.state_dict()]
+    for bad in wrong:
+        with pytest.raises(ValueError):
+            agent.load_state_dict(bad)
+    for bad in (rt_sd, lt_sd, av_sd, marked):
+        with pytest.raises(ValueError):
+            agent.load_row_tuple(bad)
+    P.sync(dev)
+    P.assert_same_state(P.learner_state(agent, env), before)
+    others = (rt, lt, av)
+    kept = [bits(o.weights).copy() for o in others]
+    for other in (rt, lt, av, ht):
+        with pytest.raises(ValueError, match=None if other is rt else "BatchedNTupleAgent"):
+            other.load_state_dict(marked)
+    for other in (lt, av):
+        with pytest.raises(ValueError):
+            other.load_row_tuple(marked)
+    assert all(np.array_equal(bits(o.weights), k) and o.ctr == 0 for o, k in zip(others, kept))
+    agent.load_state_dict(marked)
+    assert agent.ctr == 999 and torch.equal(agent.weights.cpu(), marked["weights"])
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+def test_python_surface(pkg, O, dev):
+    """`values` is q2048_nt_value, `q_values` the lookup, `update_q_value` is q2048_nt_update and ignores its reward
+    argument, and the agent refuses a 5x5 env and an env profile."""
+    agent = random_agent(pkg, dev, lr=0.1)
+    boards = AV.midgame(O)[0][:300]
+    tb = t8(dev, boards)
+    q, legal, moved = model_eval(O, base_values(), boards, tuple(m[:300] for m in AV.midgame(O)[1]))
+    assert_same_bits(agent.values(tb), model_v(base_values(), boards), "values")
+    assert_same_bits(agent.q_values(tb), q, "q_values")
+    assert_base_unwritten(dev, "reading wrote")
+    s, actions, s2 = nonracing_transitions(O, np.random.default_rng(365), 65)
+    done = np.zeros(65, np.uint8)
+    want, status, _ = model_update(O, base_values(), s, actions, s2, done, 0.1, 0.95)
+    agent.weights = t32(dev, base_values())
+    agent.update_q_value(t8(dev, s), actions, np.full(65, 1e6, F32), t8(dev, s2), done)
+    assert_same_bits(agent.weights, want, "update_q_value")
+    with pytest.raises(ValueError):
+        agent.check_status()                                            # the bad actions among the transitions
+    with pytest.raises(ValueError):
+        agent.update_q_value(t8(dev, s), actions, np.zeros(64, F32), t8(dev, s2), done)
+    with pytest.raises(ValueError):
+        agent.fused_rollout(pkg.BatchedGame2048Env(8, 5, dev, agent.seed, agent.env_id0), 1)
+    with pytest.raises(ValueError):
+        agent.fused_rollout(P.make_env(pkg, dev, 8, "nopenalty"), 1)

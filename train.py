@@ -83,13 +83,15 @@ def parse_args(argv=None):
                         "to 8x fewer rows for the same experience, so the table freezes that much later.  Learns a "
                         "different table than without the flag (every row is shared by its images); --save records it "
                         "and evaluate.py / --resume / merge_tables.py follow the file")
-    p.add_argument("--agent", choices=["hash", "row-tuple", "line-tuple", "afterstate"], default="hash",
+    p.add_argument("--agent", choices=["hash", "row-tuple", "line-tuple", "afterstate", "ntuple"], default="hash",
                    help="hash = the reference's whole-board Q-table; row-tuple = BASELINE configs[1]; line-tuple = the "
                         "row-tuple learner with the four columns as features beside the four rows (8 MiB of weights; "
                         "--resume of a row-tuple file promotes it: rows kept, columns start at zero); afterstate = one "
                         "VALUE per line entry (2 MiB), a state judged by the four boards its moves lead to: merge score + "
                         "value of the moved board (BatchedAfterstateAgent; its reward is the raw merge score, so --alpha "
-                        "may want another value; no other kind of file resumes into it)")
+                        "may want another value; no other kind of file resumes into it); ntuple = the afterstate learner "
+                        "on a 6-tuple network: four 6-cell patterns read on the eight images of the board, one table per "
+                        "pattern shared by the images (256 MiB; BatchedNTupleAgent; no other kind of file resumes into it)")
     p.add_argument("--log", default="debug_log.csv", help="CSV log path (Agent/main.py:71)")
     p.add_argument("--report-every", type=int, default=10, help="launches between CSV rows (batched)")
     p.add_argument("--max-steps", type=int, default=0, help="stop after this many env steps per env (0 = off)")
@@ -133,7 +135,7 @@ def parse_args(argv=None):
     p.add_argument("--eval-every", type=int, default=0,
                    help="batched mode, either agent: every N epochs measure the learner as a PLAYER -- greedy over the "
                         "moves that change the board (evaluate.py --policy legal --fused, q2048_play_rollout / "
-                        "q2048_rt_play_rollout / q2048_lt_play_rollout / q2048_av_play_rollout) on a "
+                        "q2048_rt_play_rollout / q2048_lt_play_rollout / q2048_av_play_rollout / q2048_nt_play_rollout) on a "
                         "separate env batch with its own seed, between two training launches on the training stream. "
                         "The table is only read and training's draws, counters and statistics are untouched: the run "
                         "trains what it trains without the flag.  0 (default) = off")
@@ -241,6 +243,9 @@ def train_batched(args, pkg):
     elif args.agent == "afterstate":
         agent = pkg.BatchedAfterstateAgent(args.episodes, 4, args.alpha, args.gamma, args.epsilon,
                                            args.epsilon_min, dev, args.seed, shard.env_id0)
+    elif args.agent == "ntuple":
+        agent = pkg.BatchedNTupleAgent(args.episodes, 4, args.alpha, args.gamma, args.epsilon,
+                                       args.epsilon_min, dev, args.seed, shard.env_id0)
     else:
         agent = pkg.BatchedQLearningAgent(args.episodes, 4, args.alpha, args.gamma, args.epsilon,
                                           args.epsilon_min, cap, dev, args.seed, shard.env_id0,
