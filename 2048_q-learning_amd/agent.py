@@ -1792,6 +1792,35 @@ class BatchedAfterstateAgent(BatchedLineTupleAgent):
             _stream(self.device)), self._FAMILY + "_play_rollout")
         env.ctr += int(steps)
 
+    def search_lookup(self, boards):
+        """The SEARCHED row (q2048_av_search_lookup): one level of expectimax over the spawn.  For a legal move a,
+        Q_a = merge score + the mean over the spawns of the moved board (a 2 with weight 9, a 4 with weight 1, in
+        every empty cell) of the greedy value of the resulting state; 0.0 for a move that does not change the board.
+        Returns (q float32 [B, 4], legal uint8 [B]: bit a = move a changes the board)."""
+        boards = self._boards(boards)
+        B = boards.shape[0]
+        q = torch.empty((B, 4), dtype=torch.float32, device=self.device)
+        legal = torch.empty((B,), dtype=torch.uint8, device=self.device)
+        N.check(self._fn("search_lookup")(_ptr(self.weights), _ptr(boards), B, _ptr(q), _ptr(legal),
+                                          _stream(self.device)), self._FAMILY + "_search_lookup")
+        return q, legal
+
+    def search_rollout(self, env: BatchedGame2048Env, steps: int, epsilon: float = 0.0) -> None:
+        """`play_rollout` with the searched row of `search_lookup` handed to the choice
+        (q2048_av_search_play_rollout): same draws, env profiles, statistics (`play_stats`) and episode handling."""
+        if env.device != self.device:
+            raise ValueError("env and agent live on different devices")
+        if env.board_size != 4:
+            raise ValueError("the afterstate learner plays 4x4 boards only")
+        if self._play_stats is None:
+            self._play_stats = new_stats_vectors(self.device)
+        si, sf = self._play_stats
+        N.check(self._fn("search_play_rollout")(
+            _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), env.num_envs, int(steps), float(epsilon), env.seed,
+            env.env_id0, env.ctr & 0xFFFFFFFF, env.env_flags, _ptr(si), _ptr(sf), _ptr(self.status),
+            _stream(self.device)), self._FAMILY + "_search_play_rollout")
+        env.ctr += int(steps)
+
     def state_dict(self, compact: bool = True) -> dict:
         """`BatchedRowTupleAgent.state_dict` with "kind": "line_afterstate" and weights float32 [8, 65536]."""
         sd = BatchedRowTupleAgent.state_dict(self, compact)

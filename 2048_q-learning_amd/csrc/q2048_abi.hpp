@@ -153,6 +153,20 @@ static inline int check_nt_play(const void* boards, const void* aux, const void*
   return check_av_play(boards, aux, weights, B, steps, eps, flags, status);
 }
 
+// The searched row of both afterstate families (q2048_{av,nt}_search_*): the checks of q2048_{av,nt}_lookup and
+// q2048_{av,nt}_play_rollout, in their order, with their codes; the legality mask is one more required pointer.
+static inline int check_search_lookup(const void* weights, const void* boards, int64_t B, const void* q_out,
+                                      const void* legal_out) {
+  if (int e = check_batch(B, 4)) return e;
+  if (!weights || !boards || !q_out || !legal_out) return Q2048_ERR_NULL;
+  if (!aligned16(weights) || !aligned16(boards) || !aligned16(q_out)) return Q2048_ERR_ALIGN;
+  return Q2048_OK;
+}
+static inline int check_search_play(const void* boards, const void* aux, const void* weights, int64_t B, int64_t steps,
+                                    double eps, uint32_t flags, const void* status) {
+  return check_av_play(boards, aux, weights, B, steps, eps, flags, status);
+}
+
 // q2048_strerror
 static inline const char* error_text(int code) {
   switch (code) {

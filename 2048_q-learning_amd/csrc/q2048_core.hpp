@@ -1176,4 +1176,70 @@ Q_HD void nt_td(const Board& x, const NtEval& en, bool done, double lr, double g
     for (int g = 0; g < kNtImages; ++g) st(p, ix.i[p][g], n.e[p][g] + d);
 }
 
+// ------------------------------------------------------------------------------------------
+// ONE-LEVEL EXPECTIMAX over the spawn, for both afterstate families (q2048_av_search_*, q2048_nt_search_*): the row
+// a player hands to play_action is, instead of q_a = score_a + v(c_a),
+//   Q_a = (float)score_a + E_a,   E_a = the mean of best(s') over the spawns s' of the afterstate c_a.
+// For a state s and a = 0..3, with c_a, score_a and legal_a the family's (move(), without the spawn):
+//   a not legal:  Q_a = 0.0f, nothing is evaluated for it.
+//   a legal:      c_a has n >= 1 empty cells (n <= 15).  For each empty cell j of c_a, ascending row-major:
+//                   b2_j = best(c_a with a 2 at j), b4_j = best(c_a with a 4 at j)   (best: av_best of the family's
+//                   evaluation -- q at the first maximum over the legal moves, 0.0f for a state without a move)
+//                   t_j = 9.0 * (double)b2_j + (double)b4_j      (the product is exact, an fma gives the same t_j)
+//                 S_a = ((0.0 + t_j0) + t_j1) + ...              double additions, in exactly this order
+//                 E_a = (float)(S_a / (double)(10 * n))          one IEEE double division, rounded to float32 once
+//                 Q_a = (float)score_a + E_a                     av_q
+// The weights 9 : 1 stand for the env's spawn rule (draw_is_four: a 4 for x >= 3865470567, probability
+// 0.1 - 0.6 * 2^-32); that 2^-32-sized difference from the integer threshold is ignored.
+// A state has at most 4 * 15 * 2 = 120 chance nodes; they have FIXED SLOTS, slot = a * 32 + j * 2 + tile (tile 0: a
+// 2, tile 1: a 4), 128 in all.  The CPU twin walks them serially; the device gives a wave to a state and spreads
+// the live nodes over its lanes (q2048_kernels.hip).  Both sum through search_row, so the order of the S_a sums is the same.
+// ------------------------------------------------------------------------------------------
+constexpr uint32_t kSearchSlots = 128u;
+// The chance node of a slot: false when the slot holds none (its move is illegal or its cell is not empty in c_a;
+// `node` is then meaningless).  One move per slot, not the four afterstates kept side by side.
+Q_HD bool search_node(const Board& s, uint32_t slot, Board& node) {
+  node = s;
+  uint32_t score;
+  const bool legal = move(node, (int)(slot >> 5), score);
+  const uint32_t j = (slot >> 1) & 15u;
+  const bool live = legal && ((empty_mask(node) >> j) & 1u) != 0u;
+  put_cell(node, j, 1u + (slot & 1u));
+  return live;
+}
+// The searched row of s.  best_at(slot, node) = best of the chance node in that slot; it is called for the live
+// slots only, in ascending slot order.  (The four moves are a loop with selects, as in nt_eval.)
+struct SearchEval { Row q; uint32_t legal; };
+template <class BestAt>
+Q_HD SearchEval search_row(const Board& s, BestAt best_at) {
+  Q2048_NO_CONTRACT
+  SearchEval ev{Row{0.0f, 0.0f, 0.0f, 0.0f}, 0u};
+#pragma unroll 1
+  for (int a = 0; a < 4; ++a) {
+    Board c = s;
+    uint32_t score;
+    if (!move(c, a, score)) continue;
+    ev.legal |= 1u << a;
+    const uint32_t em = empty_mask(c);
+    double sum = 0.0;
+#pragma unroll 1
+    for (uint32_t m = em; m != 0u; m &= m - 1u) {
+      const uint32_t j = (uint32_t)__builtin_ctz(m), slot = (uint32_t)a * 32u + j * 2u;
+      Board n2 = c, n4 = c;
+      put_cell(n2, j, 1u);
+      put_cell(n4, j, 2u);
+      const float b2 = best_at(slot, n2);
+      const float b4 = best_at(slot + 1u, n4);
+      const double t = 9.0 * (double)b2 + (double)b4;
+      sum = sum + t;
+    }
+    const float q = av_q(score, (float)(sum / (double)(10u * popc(em))));
+    ev.q.q0 = a == 0 ? q : ev.q.q0;
+    ev.q.q1 = a == 1 ? q : ev.q.q1;
+    ev.q.q2 = a == 2 ? q : ev.q.q2;
+    ev.q.q3 = a == 3 ? q : ev.q.q3;
+  }
+  return ev;
+}
+
 }  // namespace q2048

@@ -881,6 +881,83 @@ struct NtSt {
   void operator()(int p, uint32_t idx, float x) const { st_f32(v + ((size_t)p * kNtIdx + idx), x); }
 };
 
+// ---- one-level expectimax (q2048_{av,nt}_search_*): the chance nodes of a state, evaluated serially -------------
+// best(x) of the two families, what search_row asks for at every live node
+struct AvBest {
+  const float* v;
+  float operator()(const Board& x) const { const AvEval ev = av_eval(v, x); return av_best(ev.c.legal, av_row(ev)); }
+};
+struct NtBest {
+  const float* v;
+  float operator()(const Board& x) const { const NtEval ev = nt_eval(x, NtLd{v}); return av_best(ev.legal, ev.q); }
+};
+template <class Best>
+inline SearchEval search_eval(const Board& s, const Best& best) {
+  return search_row(s, [&](uint32_t, const Board& node) { return best(node); });
+}
+template <class Best>
+int search_lookup_impl(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out) {
+  if (int e = check_search_lookup(weights, boards, B, q_out, legal_out)) return e;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Board b;
+      load_board(boards, i, b);
+      const SearchEval ev = search_eval(b, Best{weights});
+      q_out[4 * i] = ev.q.q0; q_out[4 * i + 1] = ev.q.q1; q_out[4 * i + 2] = ev.q.q2; q_out[4 * i + 3] = ev.q.q3;
+      legal_out[i] = (uint8_t)ev.legal;
+    }
+  });
+  return Q2048_OK;
+}
+// q2048_{av,nt}_play_rollout with the searched row
+template <class Best>
+int search_play_impl(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
+                     uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i, double* stats_f,
+                     uint32_t* status) {
+  if (int e = check_search_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  const uint64_t eps_t = eps_threshold(eps);
+  const ImageLuts lut{&g_lut_image};
+  const int env = env_bits(flags);
+  const int T = threads_for(B);
+  std::vector<Stats> parts((size_t)T);
+  Stats* sp = parts.data();
+  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+    Stats& st = sp[tid];
+    for (int64_t i = lo; i < hi; ++i) {
+      const uint64_t id = env_id0 + (uint64_t)i;
+      Board b;
+      load_board(boards, i, b);
+      Aux a = ld_aux(aux, i);
+      const DrawPrep prep = draws_prepare(seed, id, kStreamStep);
+      double reward_sum = 0.0;
+      for (int64_t t = 0; t < steps; ++t) {
+        const Draws x = draws_at(prep, ctr0 + (uint32_t)t);
+        Draws y{0u, 0u, 0u, 0u};
+        if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+        const SearchEval ev = search_eval(b, Best{weights});
+        bool explored;
+        const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+        const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+        st.i[Q2048_ST_VALID] += o.valid != 0;
+        st.i[Q2048_ST_EXPLORE] += explored;
+        reward_sum += (double)o.reward;
+        if (o.done) {
+          st.i[Q2048_ST_EPISODES] += 1;
+          st.episode(a, o.max_log2);
+          begin_episode(b, a, seed, id, (env & kEnvResetShaping) != 0);
+        }
+      }
+      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
+      st.f[Q2048_SF_REWARD] += reward_sum;
+      store_board(boards, i, b);
+      st_aux(aux, i, a);
+    }
+  });
+  stats_merge(parts, used, stats_i, stats_f);
+  return Q2048_OK;
+}
+
 // ---- bulk moves of rows into a table (import, merge, fold, unfold) ----------------------------------------------
 // the one- or two-word key of a table, as the type the probes are compiled for: f(Geo<4>::Key) or f(Geo<5>::Key)
 template <class F>
@@ -2043,6 +2120,24 @@ int q2048_nt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights,
   });
   stats_merge(parts, used, stats_i, stats_f);
   return Q2048_OK;
+}
+
+// ---- one-level expectimax over the spawn: the players above with the searched row (search_row, q2048_core.hpp) ----
+int q2048_av_search_lookup(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out, void*) {
+  return search_lookup_impl<AvBest>(weights, boards, B, q_out, legal_out);
+}
+int q2048_av_search_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
+                                 uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                                 double* stats_f, uint32_t* status, void*) {
+  return search_play_impl<AvBest>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status);
+}
+int q2048_nt_search_lookup(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out, void*) {
+  return search_lookup_impl<NtBest>(weights, boards, B, q_out, legal_out);
+}
+int q2048_nt_search_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
+                                 uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                                 double* stats_f, uint32_t* status, void*) {
+  return search_play_impl<NtBest>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status);
 }
 
 }  // extern "C"

@@ -2635,6 +2635,140 @@ __global__ __launch_bounds__(kBlock) void k_nt_play_rollout(
 }
 
 // ---------------------------------------------------------------------------------------------
+// One-level expectimax over the spawn (q2048_{av,nt}_search_*; the definition is search_row in
+// q2048_core.hpp).  ONE WAVE PER BOARD, four boards per block: a searched step evaluates up to 120
+// successor states of a board, each as expensive as a whole greedy step, and with one lane per board
+// 65,536 boards would be one wave per SIMD waiting behind 120 evaluations in a row.  The board, its
+// aux and its draws are wave-uniform -- every lane holds them and steps the env redundantly; lane 0
+// stores.  The chance nodes have 128 fixed slots (a * 32 + j * 2 + tile); the live ones are spread
+// over the lanes (search_wave): a lane with a node runs the family's unchanged evaluation on it (32
+// loads in flight per candidate, ordinary loads) and publishes best to the node's slot in the wave's
+// 128 floats of LDS, a lane without a node issues no load.  Every lane then sums the row from LDS in
+// search_row's order.  The array is written, read by other lanes and written again on the next step: both
+// hazards are ordered by wave_lds_sync, not by the wave running in lockstep.  Statistics are per
+// BOARD: the counters are wave-uniform and lane 0 adds them once.  A wave whose board is past the
+// batch skips the body and still reaches every block barrier.  Kernels of their own; no existing
+// kernel changes.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSearchBoards = kBlock / 64;       // boards per block
+constexpr int64_t kSearchMaxBoards = (int64_t)0x7fffffff * kSearchBoards;   // per launch: grid.x is a 31-bit number
+constexpr int kFamAv = 0, kFamNt = 1;
+// best(x) of a family with the player's ordinary loads
+template <int FAM>
+__device__ __forceinline__ float search_best(const float* w, const Board& x) {
+  if constexpr (FAM == kFamAv) {
+    const AvEval ev = av_eval<false>(w, x);
+    return av_best(ev.c.legal, av_row(ev));
+  } else {
+    const NtEval ev = nt_eval(x, NtLd<false>{w});
+    return av_best(ev.legal, ev.q);
+  }
+}
+// the searched row of the wave's board; `best` = this wave's kSearchSlots floats of LDS.  Every lane calls it.
+// The live nodes are COMPACTED over the lanes: `cells` (wave-uniform; bit 16a + j = move a is legal and cell j of c_a
+// is empty) lists them in slot order, node k is tile k & 1 of the (k >> 1)-th set bit, and lane l takes the nodes l,
+// l + 64, ...  A mid-game board has about 38 nodes, so most steps are one round of evaluations, not the two that
+// fixed lanes per slot take (measured: profiles/r15_search_step_time.jsonl beside r15_search_step_time_fixed_slots.jsonl).
+// What a node publishes to is still its fixed slot.
+template <int FAM>
+__device__ __forceinline__ SearchEval search_wave(const float* w, const Board& s, float* best) {
+  const uint32_t lane = threadIdx.x & 63u;
+  u64 cells = 0ull;
+#pragma unroll 1
+  for (int a = 0; a < 4; ++a) {
+    Board c = s;
+    uint32_t score;
+    if (move(c, a, score)) cells |= (u64)empty_mask(c) << (16 * a);
+  }
+  const uint32_t p0 = popc((uint32_t)cells & 0xffffu), p1 = p0 + popc((uint32_t)(cells >> 16) & 0xffffu);
+  const uint32_t p2 = p1 + popc((uint32_t)(cells >> 32) & 0xffffu), total = 2u * (p2 + popc((uint32_t)(cells >> 48)));
+#pragma unroll 1
+  for (uint32_t k = lane; k < total; k += 64u) {          // k < total <= 120: at most two rounds
+    const uint32_t r = k >> 1;
+    const uint32_t a = (uint32_t)(r >= p0) + (uint32_t)(r >= p1) + (uint32_t)(r >= p2);
+    const uint32_t before = a == 0u ? 0u : a == 1u ? p0 : a == 2u ? p1 : p2;
+    const uint32_t j = kth_set_bit16((uint32_t)(cells >> (16u * a)) & 0xffffu, r - before);
+    const uint32_t slot = a * 32u + j * 2u + (k & 1u);    // < kSearchSlots: a < 4, j < 16
+    Board node;
+    if (search_node(s, slot, node)) best[slot] = search_best<FAM>(w, node);   // (live by construction)
+  }
+  wave_lds_sync();                                        // the nodes are published before any lane sums them
+  const SearchEval ev = search_row(s, [best](uint32_t slot, const Board&) { return best[slot]; });
+  wave_lds_sync();                                        // and summed before the next step publishes again
+  return ev;
+}
+
+template <int FAM>
+__global__ __launch_bounds__(kBlock) void k_search_lookup(const float* w, const uint8_t* boards, int64_t first, int64_t B,
+                                                          float* q_out, uint8_t* legal_out) {
+  __shared__ float best[kSearchBoards][kSearchSlots];
+  __shared__ Stage<4> st;
+  const int wave = (int)(threadIdx.x >> 6);
+  const int64_t i = first + (int64_t)blockIdx.x * kSearchBoards + wave;
+  if (i >= B) return;                                     // (no block barrier in this kernel)
+  const SearchEval ev = search_wave<FAM>(w, load_board(boards, i, B, st), best[wave]);
+  if ((threadIdx.x & 63u) == 0u) {
+    reinterpret_cast<float4*>(q_out)[i] = make_float4(ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3);
+    legal_out[i] = (uint8_t)ev.legal;
+  }
+}
+
+// the player with the searched row (q2048_{av,nt}_search_play_rollout): k_av_play_rollout / k_nt_play_rollout per wave
+template <int FAM, int ENV>
+__global__ __launch_bounds__(kBlock) void k_search_play_rollout(
+    uint8_t* boards, q2048_aux* aux, const float* w, int64_t first, int64_t B, int steps, double eps, uint64_t seed,
+    uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
+  __shared__ BlockStats bs;
+  __shared__ Stage<4> st;
+  __shared__ LutImage lut_lds;
+  __shared__ float best[kSearchBoards][kSearchSlots];
+  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
+  if (threadIdx.x < kLutImageDoubles)
+    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
+  stats_clear(bs);                                        // (its barrier publishes the image too)
+  const ImageLuts lut{&lut_lds};
+  const int wave = (int)(threadIdx.x >> 6);
+  const bool first_lane = (threadIdx.x & 63u) == 0u;
+  const int64_t i = first + (int64_t)blockIdx.x * kSearchBoards + wave;   // wave-uniform
+  if (i < B) {
+    const uint64_t id = env_id0 + (uint64_t)i;
+    Board b = load_board(boards, i, B, st);
+    Aux a = ld_aux(aux, i);
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;      // of this BOARD: the same in every lane
+    double reward_sum = 0.0;
+    const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
+    const uint64_t eps_t = eps_threshold(eps);
+    for (int t = 0; t < steps; ++t) {
+      const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
+      Draws y{0u, 0u, 0u, 0u};
+      if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+      const SearchEval ev = search_wave<FAM>(w, b, best[wave]);
+      bool explored;
+      const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+      if (o.done) {
+        if (first_lane) episode_stats(bs, a, o.max_log2);
+        begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
+      }
+      n_valid += o.valid != 0;
+      n_explore += explored;
+      n_done += o.done != 0;
+      reward_sum += (double)o.reward;
+    }
+    if (first_lane) {
+      store_board(boards, i, B, b, st);
+      st_aux(aux, i, a);
+      atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)steps);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  stats_flush(bs, stats_i, stats_f);
+}
+
+// ---------------------------------------------------------------------------------------------
 // table utilities
 // ---------------------------------------------------------------------------------------------
 // Streams the whole table once, in tiles of 16 Ki slots per block: a lane reads the first 16 bytes
@@ -3789,6 +3923,62 @@ int q2048_nt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights,
   switch (env_bits(flags) & 3) { Q2048_LAUNCH_NT_PLAY(0) Q2048_LAUNCH_NT_PLAY(1) Q2048_LAUNCH_NT_PLAY(2) Q2048_LAUNCH_NT_PLAY(3) }
 #undef Q2048_LAUNCH_NT_PLAY
   return launch_status();
+}
+
+// One-level expectimax: a block per kSearchBoards boards, so a batch beyond kSearchMaxBoards takes more than one launch
+// (the boards of a launch are [first, min(first + kSearchMaxBoards, B))).
+extern "C++" {
+template <int FAM>
+static int search_lookup_impl(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out,
+                              void* stream) {
+  if (int e = check_search_lookup(weights, boards, B, q_out, legal_out)) return e;
+  if (B == 0) return Q2048_OK;
+  for (int64_t first = 0; first < B; first += kSearchMaxBoards) {
+    const int64_t n = B - first < kSearchMaxBoards ? B - first : kSearchMaxBoards;
+    hipLaunchKernelGGL((k_search_lookup<FAM>), dim3((unsigned)((n + kSearchBoards - 1) / kSearchBoards)), dim3(kBlock), 0,
+                       (hipStream_t)stream, weights, boards, first, first + n, q_out, legal_out);
+  }
+  return launch_status();
+}
+template <int FAM>
+static int search_play_impl(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
+                            uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                            double* stats_f, uint32_t* status, void* stream) {
+  if (int e = check_search_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+#define Q2048_LAUNCH_SEARCH_PLAY(E)                                                                                \
+  case E:                                                                                                          \
+    hipLaunchKernelGGL((k_search_play_rollout<FAM, E>), grid, dim3(kBlock), 0, (hipStream_t)stream, boards, aux,   \
+                       weights, first, first + n, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);         \
+    break;
+  for (int64_t first = 0; first < B; first += kSearchMaxBoards) {
+    const int64_t n = B - first < kSearchMaxBoards ? B - first : kSearchMaxBoards;
+    const dim3 grid((unsigned)((n + kSearchBoards - 1) / kSearchBoards));
+    switch (env_bits(flags) & 3) {
+      Q2048_LAUNCH_SEARCH_PLAY(0) Q2048_LAUNCH_SEARCH_PLAY(1) Q2048_LAUNCH_SEARCH_PLAY(2) Q2048_LAUNCH_SEARCH_PLAY(3)
+    }
+  }
+#undef Q2048_LAUNCH_SEARCH_PLAY
+  return launch_status();
+}
+}  // extern "C++"
+int q2048_av_search_lookup(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out,
+                           void* stream) {
+  return search_lookup_impl<kFamAv>(weights, boards, B, q_out, legal_out, stream);
+}
+int q2048_av_search_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
+                                 uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                                 double* stats_f, uint32_t* status, void* stream) {
+  return search_play_impl<kFamAv>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status, stream);
+}
+int q2048_nt_search_lookup(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out,
+                           void* stream) {
+  return search_lookup_impl<kFamNt>(weights, boards, B, q_out, legal_out, stream);
+}
+int q2048_nt_search_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
+                                 uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                                 double* stats_f, uint32_t* status, void* stream) {
+  return search_play_impl<kFamNt>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status, stream);
 }
 
 int q2048_table_import(q2048_slot* table, int cap_log2, const uint64_t* keys, const float* q,

@@ -914,6 +914,37 @@ int q2048_nt_play_rollout(uint8_t *boards, q2048_aux *aux, const float *weights,
                           double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
                           int64_t *stats_i, double *stats_f, uint32_t *status, void *stream);
 
+/* ---- one-level expectimax over the spawn, for both afterstate families -------------------------------------------
+ * The SEARCHED ROW of a state s replaces q_a = score_a + v(c_a) by the mean of best over the spawns of c_a.  For
+ * a = 0..3, with c_a, score_a, legal_a and best as the family defines them above:
+ *   a not legal   Q_a = 0.0f; nothing is evaluated for it.
+ *   a legal       c_a has n >= 1 empty cells (n <= 15).  For each empty cell j of c_a in ascending row-major order:
+ *                 b2_j = best(c_a with a 2 at j), b4_j = best(c_a with a 4 at j), t_j = 9.0 * (double)b2_j + (double)b4_j;
+ *                 S_a = ((0.0 + t_j0) + t_j1) + ...: double additions in exactly that order;
+ *                 E_a = (float)(S_a / (double)(10 * n)): one IEEE double division, rounded to float32 once;
+ *                 Q_a = (float)score_a + E_a: one float32 addition.
+ * The weights 9 : 1 stand for the env's spawn rule (a 4 when the draw is >= 3865470567, i.e. with probability
+ * 0.1 - 0.6 * 2^-32); the 2^-32-sized difference is ignored.  A state has at most 4 * 15 * 2 = 120 chance nodes.
+ *   q2048_{av,nt}_search_lookup        writes the searched row to q_out[B][4] and the mask of the legal moves (bit a)
+ *                 to legal_out[B], which is required.  Arguments are checked as by q2048_{av,nt}_lookup.
+ *   q2048_{av,nt}_search_play_rollout  q2048_{av,nt}_play_rollout -- argument list, checks, codes, flags, draws
+ *                 (x0, x1 choice; x2, x3 spawn; the DQN profile's second spawn from stream 2), statistics, episode
+ *                 handling -- with the searched row handed to the choice: the first maximum over the legal moves, or
+ *                 the k-th legal move when exploring; no legal move = action 0, not explored.
+ * The weights are only read.  The device evaluates the chance nodes of a board on the lanes of one wave and sums them
+ * in the order above, so both libraries give the same bits.  A refused call writes nothing; B == 0 or steps == 0 is
+ * Q2048_OK. */
+int q2048_av_search_lookup(const float *weights, const uint8_t *boards, int64_t B, float *q_out,
+                           uint8_t *legal_out, void *stream);
+int q2048_av_search_play_rollout(uint8_t *boards, q2048_aux *aux, const float *weights, int64_t B, int64_t steps,
+                                 double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
+                                 int64_t *stats_i, double *stats_f, uint32_t *status, void *stream);
+int q2048_nt_search_lookup(const float *weights, const uint8_t *boards, int64_t B, float *q_out,
+                           uint8_t *legal_out, void *stream);
+int q2048_nt_search_play_rollout(uint8_t *boards, q2048_aux *aux, const float *weights, int64_t B, int64_t steps,
+                                 double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
+                                 int64_t *stats_i, double *stats_f, uint32_t *status, void *stream);
+
 /* Inverse of q2048_table_export (resume / load a table trained elsewhere): inserts `rows`
  * (key, q[4]) pairs into the table, key_words as above.  A key already present has its row
  * overwritten in place (its slot and key words stay, the four values change); a row that finds no slot
