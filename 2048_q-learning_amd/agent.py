@@ -1865,9 +1865,95 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
     -- q_a = merge score + v(moved board), the player's choice in every method, the TD step (the error spread over 32
     entries, lr / 32 each; a weight that a symmetric board reads several times moves once), `values`, the fused
     learner and the player -- through the q2048_nt_* entry points.  A checkpoint says "kind": "ntuple6_afterstate";
-    every other kind is refused in both directions, and nothing is promoted."""
+    every other kind is refused in both directions, and nothing is promoted.
+
+    `coherence=True` gives every weight a step size of its own (temporal-coherence learning, q2048_nt_tc_*): the agent
+    owns `self.coherence`, float32 [4, 16777216, 2] (512 MiB) of pairs {E, A} -- the signed sum of the weight's TD
+    errors and the sum of their magnitudes -- and `update_q_value` / `fused_rollout` scale each entry's step by
+    min(|E| / A, 1) (1 without history).  Everything that only reads V is inherited unchanged.  The checkpoint keeps
+    its kind and carries the pairs under "coherence"; a plain agent loads such a file and ignores them, a coherence
+    agent loads a plain file and starts its pairs at zero (rates restart at 1, same values)."""
 
     _FAMILY, _SHAPE, _KIND, _WHAT = "nt", (4, 1 << 24), "ntuple6_afterstate", "a 6-tuple afterstate network"
+    _ACC_SHAPE = (4, 1 << 24, 2)
+
+    def __init__(self, total_epochs, action_space=4, learning_rate=0.1, discount_factor=0.9,
+                 exploration_rate=1.0, exploration_min=0.01, device="cuda", seed: int = 0,
+                 env_id0: int = 0, coherence: bool = False):
+        super().__init__(total_epochs, action_space, learning_rate, discount_factor, exploration_rate,
+                         exploration_min, device, seed, env_id0)
+        self.coherence = torch.zeros(self._ACC_SHAPE, dtype=torch.float32, device=self.device) if coherence else None
+
+    def update_q_value(self, boards, actions, reward, next_boards, done) -> None:
+        if self.coherence is None:
+            return super().update_q_value(boards, actions, reward, next_boards, done)
+        boards, next_boards = self._boards(boards), self._boards(next_boards)
+        B = boards.shape[0]
+        vec = lambda v, dt: torch.as_tensor(v).to(device=self.device, dtype=dt).contiguous()  # noqa: E731
+        actions, done = vec(actions, torch.uint8), vec(done, torch.uint8)
+        if not (actions.shape == tuple(torch.as_tensor(reward).shape) == done.shape == (B,)):
+            raise ValueError("actions / reward / done must have shape (B,)")
+        N.check(self._L.q2048_nt_tc_update(_ptr(self.weights), _ptr(self.coherence), _ptr(boards), _ptr(actions),
+                                           _ptr(next_boards), _ptr(done), B, float(self.lr), float(self.gamma),
+                                           _ptr(self.status), _stream(self.device)), "nt_tc_update")
+
+    def fused_rollout(self, env: BatchedGame2048Env, steps: int) -> None:
+        if self.coherence is None:
+            return super().fused_rollout(env, steps)
+        if env.board_size != 4 or env.device != self.device:
+            raise ValueError("the afterstate learner needs a 4x4 env on the same device")
+        if env.env_flags:
+            raise ValueError("env profiles are supported by the hash-table agent only")
+        if (env.seed, env.env_id0, env.ctr) != (self.seed, self.env_id0, self.ctr):
+            raise ValueError("env and agent must share seed, env_id0 and step counter")
+        N.check(self._L.q2048_nt_tc_fused_rollout(
+            _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), _ptr(self.coherence), env.num_envs, int(steps),
+            float(self.epsilon), float(self.lr), float(self.gamma), self.seed, self.env_id0,
+            self.ctr & 0xFFFFFFFF, _ptr(self.stats_i), _ptr(self.stats_f), _ptr(self.status),
+            _stream(self.device)), "nt_tc_fused_rollout")
+        env.ctr += int(steps)
+        self.ctr += int(steps)
+
+    def coherence_summary(self) -> dict:
+        """{"visited": the share of pairs with A > 0, "mean_rate": the mean of min(|E| / A, 1) over them (1.0 where
+        there is none)}, by reductions on the agent's device; synchronises."""
+        if self.coherence is None:
+            raise ValueError("this agent was built without coherence=True")
+        E, A = self.coherence[..., 0], self.coherence[..., 1]
+        seen = A > 0
+        n = int(seen.sum().item())
+        rate = torch.where(seen, torch.clamp(E.abs() / A, max=1.0), torch.zeros((), device=self.device))
+        total = float(rate.sum(dtype=torch.float64).item())
+        return {"visited": n / seen.numel(), "mean_rate": total / n if n else 1.0}
+
+    def state_dict(self, compact: bool = True) -> dict:
+        """`BatchedAfterstateAgent.state_dict` ("kind": "ntuple6_afterstate", weights float32 [4, 16777216]); with
+        `coherence=True` also "coherence", the pairs float32 [4, 16777216, 2]."""
+        sd = super().state_dict(compact)
+        if self.coherence is not None:
+            sd["coherence"] = self.coherence.to("cpu", copy=True)
+        return sd
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Everything -- the pairs included, where this agent takes them -- is validated before anything of this agent
+        is written.  A plain agent ignores a file's pairs; a coherence agent without pairs in the file zeroes its own."""
+        acc = sd.get("coherence") if self.coherence is not None else None
+        if acc is not None:
+            if not isinstance(acc, torch.Tensor) or acc.dtype != torch.float32 or tuple(acc.shape) != self._ACC_SHAPE:
+                raise ValueError(f"coherence must be a float32 tensor of shape {self._ACC_SHAPE}, got "
+                                 f"{getattr(acc, 'dtype', type(acc).__name__)} {tuple(getattr(acc, 'shape', ()))}")
+            E, A = acc[..., 0], acc[..., 1]
+            if not bool(torch.isfinite(acc).all()):
+                raise ValueError("coherence holds a value that is not finite")
+            if not bool((A >= 0).all()) or not bool((E.abs() <= A).all()):
+                raise ValueError("coherence holds a pair with A < 0 or |E| > A: these are not accumulators of "
+                                 "q2048_nt_tc_*")
+        super().load_state_dict(sd)               # validates the rest, then writes
+        if self.coherence is not None:
+            if acc is None:
+                self.coherence.zero_()
+            else:
+                self.coherence.copy_(acc)
 
 
 def new_stats_vectors(device):

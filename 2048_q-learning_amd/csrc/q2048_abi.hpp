@@ -153,6 +153,35 @@ static inline int check_nt_play(const void* boards, const void* aux, const void*
   return check_av_play(boards, aux, weights, B, steps, eps, flags, status);
 }
 
+// Temporal-coherence step sizes for the network (q2048_nt_tc_*): the checks of the q2048_nt_* counterparts in their
+// order, `acc` directly after `weights` in the NULL and in the alignment list, and after the alignment checks one of
+// their own: V (256 MiB) and acc (512 MiB) may not overlap.
+static inline bool nt_tc_overlap(const void* weights, const void* acc) {
+  const uintptr_t w0 = reinterpret_cast<uintptr_t>(weights), a0 = reinterpret_cast<uintptr_t>(acc);
+  const uintptr_t w1 = w0 + ((uintptr_t)1 << 28), a1 = a0 + ((uintptr_t)1 << 29);
+  return a0 < w1 && w0 < a1;
+}
+static inline int check_nt_tc_update(const void* weights, const void* acc, const void* boards_s, const void* actions,
+                                     const void* boards_s2, const void* done, int64_t B, double lr, double gamma,
+                                     const void* status) {
+  if (int e = check_batch(B, 4)) return e;
+  if (!weights || !acc || !boards_s || !actions || !boards_s2 || !done || !status) return Q2048_ERR_NULL;
+  if (!aligned16(weights) || !aligned16(acc) || !aligned16(boards_s) || !aligned16(boards_s2)) return Q2048_ERR_ALIGN;
+  if (nt_tc_overlap(weights, acc)) return Q2048_ERR_RANGE;
+  if (!(lr == lr) || !(gamma == gamma)) return Q2048_ERR_RANGE;
+  return Q2048_OK;
+}
+static inline int check_nt_tc_fused(const void* boards, const void* aux, const void* weights, const void* acc, int64_t B,
+                                    int64_t steps, double eps, double lr, double gamma, const void* status) {
+  if (int e = check_batch(B, 4)) return e;
+  if (!boards || !aux || !weights || !acc || !status) return Q2048_ERR_NULL;
+  if (!aligned16(boards) || !aligned16(aux) || !aligned16(weights) || !aligned16(acc)) return Q2048_ERR_ALIGN;
+  if (nt_tc_overlap(weights, acc)) return Q2048_ERR_RANGE;
+  if (steps < 0 || steps > (1 << 30)) return Q2048_ERR_SIZE;
+  if (!(eps >= 0.0 && eps <= 1.0) || !(lr == lr) || !(gamma == gamma)) return Q2048_ERR_RANGE;
+  return Q2048_OK;
+}
+
 // The searched row of both afterstate families (q2048_{av,nt}_search_*): the checks of q2048_{av,nt}_lookup and
 // q2048_{av,nt}_play_rollout, in their order, with their codes; the legality mask is one more required pointer.
 static inline int check_search_lookup(const void* weights, const void* boards, int64_t B, const void* q_out,

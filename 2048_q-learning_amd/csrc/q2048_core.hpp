@@ -1176,6 +1176,86 @@ Q_HD void nt_td(const Board& x, const NtEval& en, bool done, double lr, double g
     for (int g = 0; g < kNtImages; ++g) st(p, ix.i[p][g], n.e[p][g] + d);
 }
 
+// TEMPORAL-COHERENCE STEP SIZES for the network (q2048_nt_tc_*): beside V sits acc = float[4][2^24][2], acc[p][idx] =
+// {E, A}: the signed sum of the TD errors that weight has seen and the sum of their magnitudes.  Its own rate is
+// |E| / A: 1 while its errors agree in sign, towards 0 as they cancel.  A pair is loaded and stored whole (`ldp(p, idx)`,
+// `stp(p, idx, pair)`: one 8-byte access each way in both libraries), so a stored pair derives from ONE earlier pair.
+struct NtPair { float E, A; };
+// the rate of a weight, in [0, 1] for ANY pair (a loaded file's included): no history, A <= 0 or a NaN give 1
+// (the quotient is formed for every pair and selected afterwards: 32 divisions in straight-line code, no branch per entry)
+Q_HD float nt_tc_rate(const NtPair& h) {
+  const float r = fminf(fabsf(h.E) / h.A, 1.0f);
+  return (h.A > 0.0f) ? r : 1.0f;
+}
+// err of the TD step, in double: nt_delta's live and target
+Q_HD double nt_tc_err(float v_x, float best_next, bool live, double gamma) {
+  Q2048_NO_CONTRACT
+  const double target = (gamma * (double)best_next) * (live ? 1.0 : 0.0);
+  return target - (double)v_x;
+}
+// d of one entry: nt_delta's product, times the entry's rate; at rate 1 it is nt_delta's d bit for bit
+Q_HD float nt_tc_delta(double err, float rate, double lr) {
+  Q2048_NO_CONTRACT
+  return (float)(((lr * 0.03125) * err) * (double)rate);
+}
+// the pair after an error e: |E + e| <= A + |e| in exact arithmetic, and rounding to nearest is monotone and
+// symmetric, so |E| <= A survives the two float32 additions exactly
+Q_HD NtPair nt_tc_fold(const NtPair& h, float e) { return NtPair{h.E + e, h.A + fabsf(e)}; }
+struct NtPairs { NtPair h[kNtPatterns][kNtImages]; };
+// nt_index for a pattern number that is a loop counter: masks, not `?:` (on a uniform counter hipcc turns each `?:`
+// into a branch)
+Q_HD uint32_t nt_index_at(uint64_t key, uint32_t p) {
+  const uint32_t sh = (p & 1u) << 4, split = 0u - ((p >> 1) & 1u);               // split: all ones for P2, P3
+  const uint32_t k = (uint32_t)(key >> sh), k1 = (uint32_t)(key >> (sh + 16u));
+  return (k & (0xffffffu ^ (split & 0xfff000u))) | (((k1 & 0xfffu) << 12) & split);
+}
+// nt_td with a rate per entry.  The 32 entries and the 32 pairs of x are gathered back to back (64 requests in
+// flight together); then each entry is written as gathered + d_i and each pair as gathered + {e, |e|}.  Entries of x
+// that are the same weight gathered the same value and the same pair and store the same, so that weight and its
+// pair move ONCE: the family's rule.
+template <class Ld, class LdP, class St, class StP>
+Q_HD void nt_tc_td(const Board& x, const NtEval& en, bool done, double lr, double gamma, Ld ld, LdP ldp, St st,
+                   StP stp) {
+  bool overflow;
+  uint64_t img[kNtImages];
+  key_images(pack_key(x, overflow), img);
+  NtEntries n;
+  NtPairs h;
+#pragma unroll
+  for (int p = 0; p < kNtPatterns; ++p)
+#pragma unroll
+    for (int g = 0; g < kNtImages; ++g) n.e[p][g] = ld(p, nt_index(img[g], p));
+#pragma unroll
+  for (int p = 0; p < kNtPatterns; ++p)
+#pragma unroll
+    for (int g = 0; g < kNtImages; ++g) h.h[p][g] = ldp(p, nt_index(img[g], p));
+  const bool live = !done && en.legal != 0u;
+  const double err = nt_tc_err(nt_v(n), av_best(en.legal, en.q), live, gamma);
+  const float e = (float)err;
+  // The patterns are a LOOP, as the candidates of nt_eval are, and for its reason: what stays alive across it is the
+  // eight image keys, the 32 values and the 32 pairs; the eight indices of a pattern are formed again from the keys
+  // when they are stored to.  Unrolled, hipcc keeps the 32 load offsets of V, the 32 of acc and every quotient alive
+  // beside them and needs more than 256 VGPRs.  The loop always works on row 0 and then moves the rows up by one: an
+  // array indexed by the loop counter would live in scratch memory, and selects on the (uniform) counter become a
+  // branch per entry.
+#pragma unroll 1
+  for (int p = 0; p < kNtPatterns; ++p) {
+#pragma unroll
+    for (int g = 0; g < kNtImages; ++g) {
+      const uint32_t idx = nt_index_at(img[g], (uint32_t)p);
+      st(p, idx, n.e[0][g] + nt_tc_delta(err, nt_tc_rate(h.h[0][g]), lr));
+      stp(p, idx, nt_tc_fold(h.h[0][g], e));
+    }
+#pragma unroll
+    for (int q = 0; q + 1 < kNtPatterns; ++q)
+#pragma unroll
+      for (int g = 0; g < kNtImages; ++g) {
+        n.e[q][g] = n.e[q + 1][g];
+        h.h[q][g] = h.h[q + 1][g];
+      }
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // ONE-LEVEL EXPECTIMAX over the spawn, for both afterstate families (q2048_av_search_*, q2048_nt_search_*): the row
 // a player hands to play_action is, instead of q_a = score_a + v(c_a),

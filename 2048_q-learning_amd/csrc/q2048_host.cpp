@@ -880,6 +880,26 @@ struct NtSt {
   float* v;
   void operator()(int p, uint32_t idx, float x) const { st_f32(v + ((size_t)p * kNtIdx + idx), x); }
 };
+// a pair {E, A} of acc = float[4][2^24][2]: one relaxed 64-bit atomic each way, packed through memcpy (a struct of two
+// floats may be split into two accesses by the compiler)
+struct NtTcLd {
+  const float* acc;
+  NtPair operator()(int p, uint32_t idx) const {
+    const uint64_t w = __atomic_load_n(reinterpret_cast<const uint64_t*>(acc) + ((size_t)p * kNtIdx + idx), __ATOMIC_RELAXED);
+    float f[2];
+    std::memcpy(f, &w, sizeof w);
+    return NtPair{f[0], f[1]};
+  }
+};
+struct NtTcSt {
+  float* acc;
+  void operator()(int p, uint32_t idx, const NtPair& h) const {
+    const float f[2] = {h.E, h.A};
+    uint64_t w;
+    std::memcpy(&w, f, sizeof w);
+    __atomic_store_n(reinterpret_cast<uint64_t*>(acc) + ((size_t)p * kNtIdx + idx), w, __ATOMIC_RELAXED);
+  }
+};
 
 // ---- one-level expectimax (q2048_{av,nt}_search_*): the chance nodes of a state, evaluated serially -------------
 // best(x) of the two families, what search_row asks for at every live node
@@ -2057,6 +2077,72 @@ int q2048_nt_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, int6
         const StepOut o = env_step(b, a, act, x.x2, x.x3);
         const NtEval en = nt_eval(b, NtLd{weights});
         if (legal) nt_td(c, en, o.done != 0, lr, gamma, NtLd{weights}, NtSt{weights});
+        st.i[Q2048_ST_VALID] += o.valid != 0;
+        st.i[Q2048_ST_EXPLORE] += explored;
+        reward_sum += (double)o.reward;
+        if (o.done) {
+          st.i[Q2048_ST_EPISODES] += 1;
+          st.episode(a, o.max_log2);
+          begin_episode(b, a, seed, id);
+        }
+      }
+      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
+      st.f[Q2048_SF_REWARD] += reward_sum;
+      store_board(boards, i, b);
+      st_aux(aux, i, a);
+    }
+  });
+  stats_merge(parts, used, stats_i, stats_f);
+  return Q2048_OK;
+}
+// ---- temporal-coherence step sizes: q2048_nt_update / q2048_nt_fused_rollout with nt_tc_td for nt_td ----
+int q2048_nt_tc_update(float* weights, float* acc, const uint8_t* boards_s, const uint8_t* actions,
+                       const uint8_t* boards_s2, const uint8_t* done, int64_t B, double lr, double gamma,
+                       uint32_t* status, void*) {
+  if (int e = check_nt_tc_update(weights, acc, boards_s, actions, boards_s2, done, B, lr, gamma, status)) return e;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      const int act = actions[i];
+      if (act > 3) { status_or(status, Q2048_STATUS_BAD_ACTION); continue; }
+      Board x, b_n;
+      load_board(boards_s, i, x);
+      load_board(boards_s2, i, b_n);
+      uint32_t score;
+      if (!move(x, act, score)) continue;   // the step on which the env reports the end
+      const NtEval en = nt_eval(b_n, NtLd{weights});
+      nt_tc_td(x, en, done[i] != 0, lr, gamma, NtLd{weights}, NtTcLd{acc}, NtSt{weights}, NtTcSt{acc});
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_nt_tc_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, float* acc, int64_t B, int64_t steps,
+                              double eps, double lr, double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0,
+                              int64_t* stats_i, double* stats_f, uint32_t* status, void*) {
+  if (int e = check_nt_tc_fused(boards, aux, weights, acc, B, steps, eps, lr, gamma, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  const uint64_t eps_t = eps_threshold(eps);
+  const int T = threads_for(B);
+  std::vector<Stats> parts((size_t)T);
+  Stats* sp = parts.data();
+  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+    Stats& st = sp[tid];
+    for (int64_t i = lo; i < hi; ++i) {
+      const uint64_t id = env_id0 + (uint64_t)i;
+      Board b;
+      load_board(boards, i, b);
+      Aux a = ld_aux(aux, i);
+      double reward_sum = 0.0;
+      for (int64_t t = 0; t < steps; ++t) {
+        const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+        const NtEval ev = nt_eval(b, NtLd{weights});
+        bool explored;
+        const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+        Board c = b;                    // the afterstate of the move played
+        uint32_t score;
+        const bool legal = move(c, act, score);
+        const StepOut o = env_step(b, a, act, x.x2, x.x3);
+        const NtEval en = nt_eval(b, NtLd{weights});
+        if (legal) nt_tc_td(c, en, o.done != 0, lr, gamma, NtLd{weights}, NtTcLd{acc}, NtSt{weights}, NtTcSt{acc});
         st.i[Q2048_ST_VALID] += o.valid != 0;
         st.i[Q2048_ST_EXPLORE] += explored;
         reward_sum += (double)o.reward;

@@ -2581,6 +2581,102 @@ __global__ __launch_bounds__(kBlock) void k_nt_fused_rollout(
   stats_flush(bs, stats_i, stats_f);
 }
 
+// Temporal-coherence step sizes (q2048_nt_tc_*): acc = float[4][2^24][2] beside V, a pair {E, A} per weight,
+// interleaved so that a weight's history is ONE request each way (two arrays would be two): a relaxed agent-scope
+// 64-bit atomic load, and one ordinary 8-byte vector store from plain C++.  Neither can tear, so a pair a reader
+// sees was written whole by one lane.  k_nt_update / k_nt_fused_rollout with nt_tc_td for nt_td; kernels of their own.
+struct NtTcLd {
+  const float* acc;
+  __device__ __forceinline__ NtPair operator()(int p, uint32_t idx) const {
+    const u64 w = __hip_atomic_load(reinterpret_cast<const u64*>(acc) + ((size_t)p * kNtIdx + idx), __ATOMIC_RELAXED,
+                                    __HIP_MEMORY_SCOPE_AGENT);
+    return NtPair{bits_f32((uint32_t)w), bits_f32((uint32_t)(w >> 32))};
+  }
+};
+// (the stores of nt_tc_td come from a loop over the patterns: one 32-bit byte offset from the pattern number and the
+// index -- below 2^28 for V, below 2^29 for acc -- on the uniform base)
+struct NtTcVSt {
+  float* v;
+  __device__ __forceinline__ void operator()(int p, uint32_t idx, float x) const {
+    const uint32_t byte = (((uint32_t)p << 24) | idx) << 2;
+    *reinterpret_cast<float*>(reinterpret_cast<char*>(v) + byte) = x;
+  }
+};
+struct NtTcSt {
+  float* acc;
+  __device__ __forceinline__ void operator()(int p, uint32_t idx, const NtPair& h) const {
+    const uint32_t byte = (((uint32_t)p << 24) | idx) << 3;
+    *reinterpret_cast<float2*>(reinterpret_cast<char*>(acc) + byte) = make_float2(h.E, h.A);
+  }
+};
+
+__global__ __launch_bounds__(kBlock) void k_nt_tc_update(float* w, float* acc, const uint8_t* s, const uint8_t* actions,
+                                                         const uint8_t* s2, const uint8_t* done, int64_t B, double lr,
+                                                         double gamma, uint32_t* status) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const int act = actions[i];
+  if (act > 3) { atomicOr(status, Q2048_STATUS_BAD_ACTION); return; }
+  Board x = load_board(s, i, B, st);
+  const Board b_n = load_board(s2, i, B, st);
+  uint32_t score;
+  if (!move(x, act, score)) return;   // the step on which the env reports the end
+  const NtEval en = nt_eval(b_n, NtLd<true>{w});
+  nt_tc_td(x, en, done[i] != 0, lr, gamma, NtLd<true>{w}, NtTcLd{acc}, NtTcVSt{w}, NtTcSt{acc});
+}
+
+// (two waves per SIMD asked for: left to itself hipcc takes 256 VGPRs and two AGPRs here -- one wave per SIMD -- for code
+// that fits 186 without a spill)
+__global__ __launch_bounds__(kBlock, 2) void k_nt_tc_fused_rollout(
+    uint8_t* boards, q2048_aux* aux, float* w, float* acc, int64_t B, int steps, double eps, double lr,
+    double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f,
+    uint32_t* /*status: as on k_nt_fused_rollout*/) {
+  __shared__ BlockStats bs;
+  stats_clear(bs);
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < B) {
+    Stage<4> st;
+    const uint64_t id = env_id0 + (uint64_t)i;
+    Board b = load_board(boards, i, B, st);
+    Aux a = ld_aux(aux, i);
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
+    double reward_sum = 0.0;
+    const uint64_t eps_t = eps_threshold(eps);
+    for (int t = 0; t < steps; ++t) {
+      const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+      const NtEval ev = nt_eval(b, NtLd<true>{w});      // from memory on every step, as in k_nt_fused_rollout
+      bool explored;
+      const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+      Board c = b;                    // the afterstate of the move played
+      uint32_t score;
+      const bool legal = move(c, act, score);
+      const StepOut o = env_step(b, a, act, x.x2, x.x3);
+      const NtEval en = nt_eval(b, NtLd<true>{w});
+      if (legal) nt_tc_td(c, en, o.done != 0, lr, gamma, NtLd<true>{w}, NtTcLd{acc}, NtTcVSt{w}, NtTcSt{acc});
+      n_valid += wave_count(o.valid != 0);
+      n_explore += wave_count(explored);
+      n_done += wave_count(o.done != 0);
+      reward_sum += (double)o.reward;
+      if (o.done) {
+        episode_stats(bs, a, o.max_log2);
+        begin_episode(b, a, seed, id);
+      }
+    }
+    store_board(boards, i, B, b, st);
+    st_aux(aux, i, a);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+    const uint32_t n_active = wave_count(true);
+    if (wave_leader()) {
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  stats_flush(bs, stats_i, stats_f);
+}
+
 // the greedy player on the network (q2048_nt_play_rollout): k_av_play_rollout with q2048_nt_lookup's row
 template <int ENV>
 __global__ __launch_bounds__(kBlock) void k_nt_play_rollout(
@@ -3906,6 +4002,28 @@ int q2048_nt_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, int6
   if (B == 0 || steps == 0) return Q2048_OK;
   hipLaunchKernelGGL(k_nt_fused_rollout, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream,
                      boards, aux, weights, B, (int)steps, eps, lr, gamma, seed, env_id0, ctr0, stats_i,
+                     stats_f, status);
+  return launch_status();
+}
+
+int q2048_nt_tc_update(float* weights, float* acc, const uint8_t* boards_s, const uint8_t* actions,
+                       const uint8_t* boards_s2, const uint8_t* done, int64_t B, double lr, double gamma,
+                       uint32_t* status, void* stream) {
+  if (int e = check_nt_tc_update(weights, acc, boards_s, actions, boards_s2, done, B, lr, gamma, status)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_nt_tc_update, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights, acc,
+                     boards_s, actions, boards_s2, done, B, lr, gamma, status);
+  return launch_status();
+}
+
+int q2048_nt_tc_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, float* acc, int64_t B, int64_t steps,
+                              double eps, double lr, double gamma, uint64_t seed, uint64_t env_id0,
+                              uint32_t ctr0, int64_t* stats_i, double* stats_f, uint32_t* status,
+                              void* stream) {
+  if (int e = check_nt_tc_fused(boards, aux, weights, acc, B, steps, eps, lr, gamma, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_nt_tc_fused_rollout, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream,
+                     boards, aux, weights, acc, B, (int)steps, eps, lr, gamma, seed, env_id0, ctr0, stats_i,
                      stats_f, status);
   return launch_status();
 }

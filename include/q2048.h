@@ -914,6 +914,44 @@ int q2048_nt_play_rollout(uint8_t *boards, q2048_aux *aux, const float *weights,
                           double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
                           int64_t *stats_i, double *stats_f, uint32_t *status, void *stream);
 
+/* ---- temporal-coherence step sizes for the 6-tuple afterstate network --------------------------------------------
+ * The network's learner with a step size of its own per weight (TC learning): a weight learns at full rate while its
+ * TD errors agree in sign and stops by itself as they cancel.
+ *   weights   V = float[4][16777216] of the family above, unchanged: every q2048_nt_* reader works on a V trained here.
+ *   acc       float[4][16777216][2] (512 MiB, 16-byte aligned) beside it: acc[p][idx] = {E, A}, the signed sum of the
+ *             TD errors the weight V[p][idx] has seen and the sum of their magnitudes.  All zero = no history.  A pair
+ *             is 8 bytes, 8-byte aligned, always read with one 8-byte load and written with one 8-byte store: a
+ *             reader never sees the E of one writer with the A of another.
+ *   TD step   for (s, a, s2, done), x = c_a(s), with q2048_nt_update's skip rules (an action > 3 sets
+ *             Q2048_STATUS_BAD_ACTION and skips the lane; an action that does not change s writes nothing).  The lane
+ *             gathers the 32 entries of x from V and the 32 pairs of x from acc.  live and target are those of the
+ *             afterstate family;  err = target - (double)v(x), in double;  e = (float)err, rounded once.  Per entry i:
+ *               r_i = (A_i > 0.0f) ? fminf(fabsf(E_i) / A_i, 1.0f) : 1.0f      one IEEE float32 division; in [0, 1] for
+ *                     ANY contents of acc (a loaded file's included), and 1 where a NaN is involved;
+ *               d_i = (float)(((lr * 0.03125) * err) * (double)r_i)             rounded once, no contraction.
+ *             Then V[p][idx] = (the value gathered there) + d_i and acc[p][idx] = {E_i + e, A_i + fabsf(e)}: plain
+ *             stores, the last writer wins.  Entries of one lane that are the same weight gathered the same values and
+ *             store the same values, so that weight and its pair move ONCE (the family's rule).
+ *   (a)       On an all-zero acc every r_i is 1 and d_i is bit for bit q2048_nt_update's d: one step from no history
+ *             is the plain step.
+ *   (b)       |E| <= A holds exactly for every pair ever stored, racing lanes included: it holds for zero;
+ *             |E + e| <= A + |e| holds in exact arithmetic; rounding to nearest is monotone and symmetric; and every
+ *             stored pair derives from ONE untorn pair.
+ *   fused     q2048_nt_tc_fused_rollout is q2048_nt_fused_rollout step for step -- evaluation from memory, the
+ *             player's draw contract, env step, statistics, reset -- with this TD step; nothing is carried between
+ *             steps, so B = 1 is exactly the four-call loop q2048_nt_choose / env step / q2048_nt_tc_update / reset
+ *             on all 768 MiB, and lr = 0 leaves V bit-identical while acc accumulates.
+ * Argument checks are the q2048_nt_* counterpart's in its order, with acc checked for NULL and for 16-byte alignment
+ * directly after weights; then, after the alignment checks, Q2048_ERR_RANGE if the byte ranges of weights (256 MiB)
+ * and acc (512 MiB) overlap.  A refused call writes nothing; B == 0 or steps == 0 is Q2048_OK. */
+int q2048_nt_tc_update(float *weights, float *acc, const uint8_t *boards_s, const uint8_t *actions,
+                       const uint8_t *boards_s2, const uint8_t *done, int64_t B,
+                       double lr, double gamma, uint32_t *status, void *stream);
+int q2048_nt_tc_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weights, float *acc, int64_t B,
+                              int64_t steps, double eps, double lr, double gamma, uint64_t seed,
+                              uint64_t env_id0, uint32_t ctr0, int64_t *stats_i, double *stats_f,
+                              uint32_t *status, void *stream);
+
 /* ---- one-level expectimax over the spawn, for both afterstate families -------------------------------------------
  * The SEARCHED ROW of a state s replaces q_a = score_a + v(c_a) by the mean of best over the spawns of c_a.  For
  * a = 0..3, with c_a, score_a, legal_a and best as the family defines them above:

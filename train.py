@@ -92,6 +92,12 @@ def parse_args(argv=None):
                         "may want another value; no other kind of file resumes into it); ntuple = the afterstate learner "
                         "on a 6-tuple network: four 6-cell patterns read on the eight images of the board, one table per "
                         "pattern shared by the images (256 MiB; BatchedNTupleAgent; no other kind of file resumes into it)")
+    p.add_argument("--coherence", action="store_true",
+                   help="--agent ntuple only: TEMPORAL-COHERENCE step sizes (q2048_nt_tc_*).  Every weight carries the "
+                        "signed sum E and the absolute sum A of its TD errors (512 MiB beside the 256 MiB of weights) and "
+                        "learns at --alpha / 32 * min(|E| / A, 1): at full rate while its errors agree in sign, ever "
+                        "slower as they cancel.  --save keeps the accumulators; --resume of a plain file starts them at "
+                        "zero, and a file that holds them needs this flag")
     p.add_argument("--log", default="debug_log.csv", help="CSV log path (Agent/main.py:71)")
     p.add_argument("--report-every", type=int, default=10, help="launches between CSV rows (batched)")
     p.add_argument("--max-steps", type=int, default=0, help="stop after this many env steps per env (0 = off)")
@@ -245,7 +251,7 @@ def train_batched(args, pkg):
                                            args.epsilon_min, dev, args.seed, shard.env_id0)
     elif args.agent == "ntuple":
         agent = pkg.BatchedNTupleAgent(args.episodes, 4, args.alpha, args.gamma, args.epsilon,
-                                       args.epsilon_min, dev, args.seed, shard.env_id0)
+                                       args.epsilon_min, dev, args.seed, shard.env_id0, coherence=args.coherence)
     else:
         agent = pkg.BatchedQLearningAgent(args.episodes, 4, args.alpha, args.gamma, args.epsilon,
                                           args.epsilon_min, cap, dev, args.seed, shard.env_id0,
@@ -258,6 +264,13 @@ def train_batched(args, pkg):
     epoch0 = 0
     if args.resume:
         sd = _load(args.resume, rank)
+        if args.agent == "ntuple" and sd.get("kind") == "ntuple6_afterstate":
+            if "coherence" in sd and not args.coherence:
+                raise SystemExit(f"{args.resume} holds temporal-coherence accumulators: resume it with --coherence "
+                                 "(without the flag a --save would silently drop them)")
+            if args.coherence and "coherence" not in sd and rank == 0:
+                print(f"{args.resume} holds no temporal-coherence accumulators: the weights continue, the accumulators "
+                      "start at zero (every rate restarts at 1)", flush=True)
         if args.fold:
             _fold_into(pkg, agent, sd, args, dev)
         elif args.unfold:
@@ -358,6 +371,9 @@ def train_batched(args, pkg):
         if args.max_steps and env.ctr >= args.max_steps:
             break
     agent.check_status()
+    if args.coherence and rank == 0:
+        cs = agent.coherence_summary()
+        print(f"coherence: {cs['visited']:.6f} of the weights visited, mean rate {cs['mean_rate']:.6f} over them", flush=True)
     if args.agent == "hash":
         check = agent.verify_table()                      # (waits for a growth still in flight and checks it too)
         grown = _report_growths(agent, grown, rank)
@@ -403,12 +419,15 @@ class _Evaluator:
             agent.play_rollout(env, args.steps_per_launch)
             st = agent.play_stats()
         games = max(st["episodes"], 1)
-        with open(self.path, "a") as fh:
-            fh.write(self._json.dumps({
-                "epoch": epoch, "env_steps": env_steps, "games": st["episodes"], "mean_score": st["score_sum"] / games,
+        line = {"epoch": epoch, "env_steps": env_steps, "games": st["episodes"], "mean_score": st["score_sum"] / games,
                 "mean_return": st["return_sum"] / games,
                 "max_tile_hist": {str(k): v for k, v in st["max_tile_hist"].items()},
-                "valid_move_frac": st["valid_moves"] / max(st["steps"], 1)}) + "\n")
+                "valid_move_frac": st["valid_moves"] / max(st["steps"], 1)}
+        if getattr(agent, "coherence", None) is not None:      # --coherence: the two numbers of coherence_summary()
+            cs = agent.coherence_summary()
+            line.update({"coherence_visited": cs["visited"], "coherence_mean_rate": cs["mean_rate"]})
+        with open(self.path, "a") as fh:
+            fh.write(self._json.dumps(line) + "\n")
 
 
 def _report_growths(agent, grown, rank) -> int:
@@ -523,6 +542,11 @@ def main(argv=None):
         if args.num_envs == 1 and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
             raise SystemExit("--symmetric needs the batched mode (--num-envs > 1): the one-state loop learns through "
                              "choose_action / update_q_value, which do not take the flag")
+    if args.coherence:
+        if args.agent != "ntuple":
+            raise SystemExit(f"--coherence applies to --agent ntuple (the 6-tuple afterstate network), not to --agent {args.agent}")
+        if args.num_envs == 1 and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+            raise SystemExit("--coherence needs the batched mode (--num-envs > 1): the one-state loop runs the hash-table agent")
     if args.fold:
         if not args.symmetric:
             raise SystemExit("--fold folds a plain file into a symmetry-folded table: it needs --symmetric")
