@@ -278,6 +278,16 @@ _SIGNATURES = {
     "q2048_nt_search_play_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double,
                                                C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "q2048_av_search_lookup_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
+    "q2048_av_search_play_rollout_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
+                                                     C.c_double, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "q2048_nt_search_lookup_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
+    "q2048_nt_search_play_rollout_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
+                                                     C.c_double, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "q2048_table_import": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_int, C.c_void_p, C.c_void_p]),
     "q2048_table_export": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,

@@ -1792,22 +1792,37 @@ class BatchedAfterstateAgent(BatchedLineTupleAgent):
             _stream(self.device)), self._FAMILY + "_play_rollout")
         env.ctr += int(steps)
 
-    def search_lookup(self, boards):
+    @staticmethod
+    def _search_depth(depth) -> int:
+        if depth not in (1, 2) or isinstance(depth, bool):
+            raise ValueError(f"search depth must be 1 or 2, not {depth!r}")
+        return int(depth)
+
+    def search_lookup(self, boards, depth: int = 1):
         """The SEARCHED row (q2048_av_search_lookup): one level of expectimax over the spawn.  For a legal move a,
         Q_a = merge score + the mean over the spawns of the moved board (a 2 with weight 9, a 4 with weight 1, in
         every empty cell) of the greedy value of the resulting state; 0.0 for a move that does not change the board.
+        `depth=2` (q2048_av_search_lookup_depth) looks one level further: the value of a resulting state is the best
+        of ITS searched row instead of its greedy value.
         Returns (q float32 [B, 4], legal uint8 [B]: bit a = move a changes the board)."""
+        depth = self._search_depth(depth)
         boards = self._boards(boards)
         B = boards.shape[0]
         q = torch.empty((B, 4), dtype=torch.float32, device=self.device)
         legal = torch.empty((B,), dtype=torch.uint8, device=self.device)
-        N.check(self._fn("search_lookup")(_ptr(self.weights), _ptr(boards), B, _ptr(q), _ptr(legal),
-                                          _stream(self.device)), self._FAMILY + "_search_lookup")
+        if depth == 1:
+            N.check(self._fn("search_lookup")(_ptr(self.weights), _ptr(boards), B, _ptr(q), _ptr(legal),
+                                              _stream(self.device)), self._FAMILY + "_search_lookup")
+        else:
+            N.check(self._fn("search_lookup_depth")(_ptr(self.weights), _ptr(boards), B, depth, _ptr(q), _ptr(legal),
+                                                    _stream(self.device)), self._FAMILY + "_search_lookup_depth")
         return q, legal
 
-    def search_rollout(self, env: BatchedGame2048Env, steps: int, epsilon: float = 0.0) -> None:
+    def search_rollout(self, env: BatchedGame2048Env, steps: int, epsilon: float = 0.0, depth: int = 1) -> None:
         """`play_rollout` with the searched row of `search_lookup` handed to the choice
-        (q2048_av_search_play_rollout): same draws, env profiles, statistics (`play_stats`) and episode handling."""
+        (q2048_av_search_play_rollout; `depth=2`: q2048_av_search_play_rollout_depth): same draws, env profiles,
+        statistics (`play_stats`) and episode handling."""
+        depth = self._search_depth(depth)
         if env.device != self.device:
             raise ValueError("env and agent live on different devices")
         if env.board_size != 4:
@@ -1815,10 +1830,16 @@ class BatchedAfterstateAgent(BatchedLineTupleAgent):
         if self._play_stats is None:
             self._play_stats = new_stats_vectors(self.device)
         si, sf = self._play_stats
-        N.check(self._fn("search_play_rollout")(
-            _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), env.num_envs, int(steps), float(epsilon), env.seed,
-            env.env_id0, env.ctr & 0xFFFFFFFF, env.env_flags, _ptr(si), _ptr(sf), _ptr(self.status),
-            _stream(self.device)), self._FAMILY + "_search_play_rollout")
+        if depth == 1:
+            N.check(self._fn("search_play_rollout")(
+                _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), env.num_envs, int(steps), float(epsilon), env.seed,
+                env.env_id0, env.ctr & 0xFFFFFFFF, env.env_flags, _ptr(si), _ptr(sf), _ptr(self.status),
+                _stream(self.device)), self._FAMILY + "_search_play_rollout")
+        else:
+            N.check(self._fn("search_play_rollout_depth")(
+                _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), env.num_envs, int(steps), depth, float(epsilon),
+                env.seed, env.env_id0, env.ctr & 0xFFFFFFFF, env.env_flags, _ptr(si), _ptr(sf), _ptr(self.status),
+                _stream(self.device)), self._FAMILY + "_search_play_rollout_depth")
         env.ctr += int(steps)
 
     def state_dict(self, compact: bool = True) -> dict:

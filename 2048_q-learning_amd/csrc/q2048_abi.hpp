@@ -195,6 +195,18 @@ static inline int check_search_play(const void* boards, const void* aux, const v
                                     double eps, uint32_t flags, const void* status) {
   return check_av_play(boards, aux, weights, B, steps, eps, flags, status);
 }
+// The same with a search depth (q2048_{av,nt}_search_*_depth): the depth first -- 1 or 2, anything else is
+// Q2048_ERR_RANGE whatever the other arguments are -- then the depth-1 counterpart's checks, in its order, with its codes.
+static inline int check_search_lookup_depth(const void* weights, const void* boards, int64_t B, int depth,
+                                            const void* q_out, const void* legal_out) {
+  if (depth != 1 && depth != 2) return Q2048_ERR_RANGE;
+  return check_search_lookup(weights, boards, B, q_out, legal_out);
+}
+static inline int check_search_play_depth(const void* boards, const void* aux, const void* weights, int64_t B,
+                                          int64_t steps, int depth, double eps, uint32_t flags, const void* status) {
+  if (depth != 1 && depth != 2) return Q2048_ERR_RANGE;
+  return check_search_play(boards, aux, weights, B, steps, eps, flags, status);
+}
 
 // q2048_strerror
 static inline const char* error_text(int code) {
@@ -205,7 +217,7 @@ static inline const char* error_text(int code) {
     case Q2048_ERR_ALIGN: return "boards/aux/table must be 16-byte aligned";
     case Q2048_ERR_UNSUPPORTED: return "unsupported here (board side other than 4 or 5, or an entry point this library or geometry does not have)";
     case Q2048_ERR_LAUNCH: return "HIP launch failed";
-    case Q2048_ERR_RANGE: return "scalar out of range (eps in [0,1], lr and gamma finite)";
+    case Q2048_ERR_RANGE: return "scalar out of range (eps in [0,1], lr and gamma finite, search depth 1 or 2)";
     case Q2048_ERR_FLAGS: return "flag bits this entry point does not take";
     case Q2048_ERR_ALLOC: return "device memory could not be reserved, created or mapped";
     case Q2048_ERR_VERIFY: return "a table failed its self-check (a fresh table not all zeros, or rows lost while growing)";

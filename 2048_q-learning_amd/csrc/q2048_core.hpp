@@ -1322,4 +1322,28 @@ Q_HD SearchEval search_row(const Board& s, BestAt best_at) {
   return ev;
 }
 
+// ------------------------------------------------------------------------------------------
+// TWO-LEVEL EXPECTIMAX (q2048_{av,nt}_search_*_depth with depth 2).  Write best_0 for the family's best above.  For
+// d >= 1 the depth-d row of a state s is the searched row above with best_{d-1} in place of best:
+//   a not legal:  Q^d_a = 0.0f, nothing is evaluated for it.
+//   a legal:      for each empty cell j of c_a, ascending row-major:
+//                   t_j = 9.0 * (double)best_{d-1}(c_a + 2 at j) + (double)best_{d-1}(c_a + 4 at j)
+//                 S_a = ((0.0 + t_j0) + t_j1) + ...,  E_a = (float)(S_a / (double)(10 n)),  Q^d_a = (float)score_a + E_a
+//   best_d(x) = av_best on the depth-d row of x: Q^d at the first maximum over the legal moves of x, 0.0f for a state
+//               without a legal move -- nothing is evaluated beneath such a state.
+// Depth 1 is search_row with the family's best, bit for bit.  Depth 2 is search_row whose best_at is search_best_of the
+// search_row of the node: at most 120 level-one nodes with at most 120 leaves each, 14,400 family evaluations.  The
+// order of every S sum, at BOTH levels, is search_row's: the device spreads the level-one nodes of a board over the waves
+// of a block and the leaves of a node over the lanes of a wave, and sums each level through search_row.
+// ------------------------------------------------------------------------------------------
+// best_d(x) from the depth-d row of x
+Q_HD float search_best_of(const SearchEval& ev) { return av_best(ev.legal, ev.q); }
+// The depth-2 row of s.  best(x) = the family's best_0.
+template <class Best>
+Q_HD SearchEval search_row2(const Board& s, Best best) {
+  return search_row(s, [&best](uint32_t, const Board& node) {
+    return search_best_of(search_row(node, [&best](uint32_t, const Board& leaf) { return best(leaf); }));
+  });
+}
+
 }  // namespace q2048

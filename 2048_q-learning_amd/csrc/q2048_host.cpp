@@ -911,18 +911,20 @@ struct NtBest {
   const float* v;
   float operator()(const Board& x) const { const NtEval ev = nt_eval(x, NtLd{v}); return av_best(ev.legal, ev.q); }
 };
-template <class Best>
+// (DEPTH 2: the two-level row, search_row2 -- the same serial walk one level further down)
+template <class Best, int DEPTH = 1>
 inline SearchEval search_eval(const Board& s, const Best& best) {
-  return search_row(s, [&](uint32_t, const Board& node) { return best(node); });
+  if constexpr (DEPTH == 2) return search_row2(s, best);
+  else return search_row(s, [&](uint32_t, const Board& node) { return best(node); });
 }
-template <class Best>
+template <class Best, int DEPTH = 1>
 int search_lookup_impl(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out) {
   if (int e = check_search_lookup(weights, boards, B, q_out, legal_out)) return e;
   parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
     for (int64_t i = lo; i < hi; ++i) {
       Board b;
       load_board(boards, i, b);
-      const SearchEval ev = search_eval(b, Best{weights});
+      const SearchEval ev = search_eval<Best, DEPTH>(b, Best{weights});
       q_out[4 * i] = ev.q.q0; q_out[4 * i + 1] = ev.q.q1; q_out[4 * i + 2] = ev.q.q2; q_out[4 * i + 3] = ev.q.q3;
       legal_out[i] = (uint8_t)ev.legal;
     }
@@ -930,7 +932,7 @@ int search_lookup_impl(const float* weights, const uint8_t* boards, int64_t B, f
   return Q2048_OK;
 }
 // q2048_{av,nt}_play_rollout with the searched row
-template <class Best>
+template <class Best, int DEPTH = 1>
 int search_play_impl(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
                      uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i, double* stats_f,
                      uint32_t* status) {
@@ -955,7 +957,7 @@ int search_play_impl(uint8_t* boards, q2048_aux* aux, const float* weights, int6
         const Draws x = draws_at(prep, ctr0 + (uint32_t)t);
         Draws y{0u, 0u, 0u, 0u};
         if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-        const SearchEval ev = search_eval(b, Best{weights});
+        const SearchEval ev = search_eval<Best, DEPTH>(b, Best{weights});
         bool explored;
         const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
         const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
@@ -2224,6 +2226,35 @@ int q2048_nt_search_play_rollout(uint8_t* boards, q2048_aux* aux, const float* w
                                  uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                                  double* stats_f, uint32_t* status, void*) {
   return search_play_impl<NtBest>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status);
+}
+// ---- the same with a search depth: 1 = the functions above, 2 = the two-level row (search_row2, q2048_core.hpp) ----
+int q2048_av_search_lookup_depth(const float* weights, const uint8_t* boards, int64_t B, int depth, float* q_out,
+                                 uint8_t* legal_out, void*) {
+  if (int e = check_search_lookup_depth(weights, boards, B, depth, q_out, legal_out)) return e;
+  return depth == 1 ? search_lookup_impl<AvBest, 1>(weights, boards, B, q_out, legal_out)
+                    : search_lookup_impl<AvBest, 2>(weights, boards, B, q_out, legal_out);
+}
+int q2048_av_search_play_rollout_depth(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps,
+                                       int depth, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
+                                       int64_t* stats_i, double* stats_f, uint32_t* status, void*) {
+  if (int e = check_search_play_depth(boards, aux, weights, B, steps, depth, eps, flags, status)) return e;
+  return depth == 1
+      ? search_play_impl<AvBest, 1>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status)
+      : search_play_impl<AvBest, 2>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status);
+}
+int q2048_nt_search_lookup_depth(const float* weights, const uint8_t* boards, int64_t B, int depth, float* q_out,
+                                 uint8_t* legal_out, void*) {
+  if (int e = check_search_lookup_depth(weights, boards, B, depth, q_out, legal_out)) return e;
+  return depth == 1 ? search_lookup_impl<NtBest, 1>(weights, boards, B, q_out, legal_out)
+                    : search_lookup_impl<NtBest, 2>(weights, boards, B, q_out, legal_out);
+}
+int q2048_nt_search_play_rollout_depth(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps,
+                                       int depth, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
+                                       int64_t* stats_i, double* stats_f, uint32_t* status, void*) {
+  if (int e = check_search_play_depth(boards, aux, weights, B, steps, depth, eps, flags, status)) return e;
+  return depth == 1
+      ? search_play_impl<NtBest, 1>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status)
+      : search_play_impl<NtBest, 2>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status);
 }
 
 }  // extern "C"

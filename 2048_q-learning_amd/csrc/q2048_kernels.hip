@@ -2865,6 +2865,134 @@ __global__ __launch_bounds__(kBlock) void k_search_play_rollout(
 }
 
 // ---------------------------------------------------------------------------------------------
+// Two-level expectimax (q2048_{av,nt}_search_*_depth with depth 2; the definition is search_row2 in
+// q2048_core.hpp).  ONE BLOCK PER BOARD: a depth-2 step is up to 120 level-one nodes, each a whole
+// searched step of the one-level player, so a board gets the four waves that player gives to four
+// boards.  The board, its aux and its draws are block-uniform -- every lane holds them and steps the
+// env redundantly; thread 0 stores.  The live level-one nodes are compacted from the `cells` mask of
+// search_wave, in slot order (search2_slot); wave w takes the nodes w, w + 4, ...: it builds the node
+// (search_node), runs the unchanged search_wave on it with its own 128 floats of LDS -- the leaves of
+// the node over the wave's lanes -- takes best_1 = search_best_of the result, and lane 0 publishes it
+// to the node's fixed slot in the block's array of kSearchSlots floats.  A node without a legal move
+// has no leaves: search_wave evaluates nothing and best_1 is 0.0f.  The waves run different numbers of
+// nodes, so the node loop holds no block barrier; inside it wave_lds_sync (search_wave's) is the only
+// ordering.  One barrier after the loop publishes the array to the block, every lane sums the row
+// from it through search_row, and a second barrier keeps the next step's publishing behind that
+// sum.  No wave leaves before a barrier: a block always has a board.  Statistics are per BOARD:
+// block-uniform counters, added once by thread 0.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSearch2Waves = kBlock / 64;
+constexpr int64_t kSearch2MaxBoards = (int64_t)0x7fffffff;   // per launch: one block per board, grid.x is a 31-bit number
+// `cells` of a board (bit 16a + j = move a is legal and cell j of c_a is empty), as search_wave forms it
+__device__ __forceinline__ u64 search2_cells(const Board& s) {
+  u64 cells = 0ull;
+#pragma unroll 1
+  for (int a = 0; a < 4; ++a) {
+    Board c = s;
+    uint32_t score;
+    if (move(c, a, score)) cells |= (u64)empty_mask(c) << (16 * a);
+  }
+  return cells;
+}
+// the fixed slot of the k-th live node (k < 2 * popcount(cells)): tile k & 1 of the (k >> 1)-th set bit
+__device__ __forceinline__ uint32_t search2_slot(u64 cells, uint32_t k) {
+  const uint32_t p0 = popc((uint32_t)cells & 0xffffu), p1 = p0 + popc((uint32_t)(cells >> 16) & 0xffffu);
+  const uint32_t p2 = p1 + popc((uint32_t)(cells >> 32) & 0xffffu);
+  const uint32_t r = k >> 1;
+  const uint32_t a = (uint32_t)(r >= p0) + (uint32_t)(r >= p1) + (uint32_t)(r >= p2);
+  const uint32_t before = a == 0u ? 0u : a == 1u ? p0 : a == 2u ? p1 : p2;
+  const uint32_t j = kth_set_bit16((uint32_t)(cells >> (16u * a)) & 0xffffu, r - before);
+  return a * 32u + j * 2u + (k & 1u);                     // < kSearchSlots: a < 4, j < 16
+}
+// the depth-2 row of the block's board.  `leaf` = this wave's kSearchSlots floats, `best1` = the block's.  Every
+// thread of the block calls it (two block barriers).
+template <int FAM>
+__device__ __forceinline__ SearchEval search2_block(const float* w, const Board& s, float* leaf, float* best1) {
+  const uint32_t wave = threadIdx.x >> 6;
+  const u64 cells = search2_cells(s);
+  const uint32_t total = 2u * (uint32_t)__popcll(cells);  // <= 120
+#pragma unroll 1
+  for (uint32_t k = wave; k < total; k += (uint32_t)kSearch2Waves) {   // wave-uniform: no block barrier in here
+    const uint32_t slot = search2_slot(cells, k);
+    Board node;
+    search_node(s, slot, node);                           // (live by construction)
+    const float b = search_best_of(search_wave<FAM>(w, node, leaf));
+    if ((threadIdx.x & 63u) == 0u) best1[slot] = b;
+  }
+  __syncthreads();                                        // the level-one nodes are published before any lane sums them
+  const SearchEval ev = search_row(s, [best1](uint32_t slot, const Board&) { return best1[slot]; });
+  __syncthreads();                                        // and summed before the next step publishes again
+  return ev;
+}
+
+template <int FAM>
+__global__ __launch_bounds__(kBlock) void k_search2_lookup(const float* w, const uint8_t* boards, int64_t first, int64_t B,
+                                                           float* q_out, uint8_t* legal_out) {
+  __shared__ float leaf[kSearch2Waves][kSearchSlots];
+  __shared__ float best1[kSearchSlots];
+  __shared__ Stage<4> st;
+  const int64_t i = first + (int64_t)blockIdx.x;          // < B: the grid is the launch's boards
+  const SearchEval ev = search2_block<FAM>(w, load_board(boards, i, B, st), leaf[threadIdx.x >> 6], best1);
+  if (threadIdx.x == 0u && i < B) {
+    reinterpret_cast<float4*>(q_out)[i] = make_float4(ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3);
+    legal_out[i] = (uint8_t)ev.legal;
+  }
+}
+
+// k_search_play_rollout with the depth-2 row, a block per board
+template <int FAM, int ENV>
+__global__ __launch_bounds__(kBlock) void k_search2_play_rollout(
+    uint8_t* boards, q2048_aux* aux, const float* w, int64_t first, int64_t B, int steps, double eps, uint64_t seed,
+    uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
+  __shared__ BlockStats bs;
+  __shared__ Stage<4> st;
+  __shared__ LutImage lut_lds;
+  __shared__ float leaf[kSearch2Waves][kSearchSlots];
+  __shared__ float best1[kSearchSlots];
+  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
+  if (threadIdx.x < kLutImageDoubles)
+    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
+  stats_clear(bs);                                        // (its barrier publishes the image too)
+  const ImageLuts lut{&lut_lds};
+  const bool first_thread = threadIdx.x == 0u;
+  const int64_t i = first + (int64_t)blockIdx.x;          // block-uniform, < B: the grid is the launch's boards
+  const uint64_t id = env_id0 + (uint64_t)i;
+  Board b = load_board(boards, i, B, st);
+  Aux a = ld_aux(aux, i);
+  uint32_t n_valid = 0, n_explore = 0, n_done = 0;        // of this BOARD: the same in every thread
+  double reward_sum = 0.0;
+  const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
+  const uint64_t eps_t = eps_threshold(eps);
+  for (int t = 0; t < steps; ++t) {
+    const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
+    Draws y{0u, 0u, 0u, 0u};
+    if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+    const SearchEval ev = search2_block<FAM>(w, b, leaf[threadIdx.x >> 6], best1);
+    bool explored;
+    const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+    const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+    if (o.done) {
+      if (first_thread) episode_stats(bs, a, o.max_log2);
+      begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
+    }
+    n_valid += o.valid != 0;
+    n_explore += explored;
+    n_done += o.done != 0;
+    reward_sum += (double)o.reward;
+  }
+  if (first_thread) {
+    store_board(boards, i, B, b, st);
+    st_aux(aux, i, a);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+    atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)steps);
+    atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+    atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+    atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+  }
+  stats_flush(bs, stats_i, stats_f);
+}
+
+// ---------------------------------------------------------------------------------------------
 // table utilities
 // ---------------------------------------------------------------------------------------------
 // Streams the whole table once, in tiles of 16 Ki slots per block: a lane reads the first 16 bytes
@@ -4079,7 +4207,74 @@ static int search_play_impl(uint8_t* boards, q2048_aux* aux, const float* weight
 #undef Q2048_LAUNCH_SEARCH_PLAY
   return launch_status();
 }
+// Two-level expectimax: a block per board, so a batch beyond kSearch2MaxBoards takes more than one launch.  The callers
+// have checked the arguments.
+template <int FAM>
+static int search2_lookup_impl(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out,
+                               void* stream) {
+  if (B == 0) return Q2048_OK;
+  for (int64_t first = 0; first < B; first += kSearch2MaxBoards) {
+    const int64_t n = B - first < kSearch2MaxBoards ? B - first : kSearch2MaxBoards;
+    hipLaunchKernelGGL((k_search2_lookup<FAM>), dim3((unsigned)n), dim3(kBlock), 0, (hipStream_t)stream, weights, boards,
+                       first, first + n, q_out, legal_out);
+  }
+  return launch_status();
+}
+template <int FAM>
+static int search2_play_impl(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
+                             uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                             double* stats_f, void* stream) {
+  if (B == 0 || steps == 0) return Q2048_OK;
+#define Q2048_LAUNCH_SEARCH2_PLAY(E)                                                                               \
+  case E:                                                                                                          \
+    hipLaunchKernelGGL((k_search2_play_rollout<FAM, E>), grid, dim3(kBlock), 0, (hipStream_t)stream, boards, aux,  \
+                       weights, first, first + n, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);         \
+    break;
+  for (int64_t first = 0; first < B; first += kSearch2MaxBoards) {
+    const int64_t n = B - first < kSearch2MaxBoards ? B - first : kSearch2MaxBoards;
+    const dim3 grid((unsigned)n);
+    switch (env_bits(flags) & 3) {
+      Q2048_LAUNCH_SEARCH2_PLAY(0) Q2048_LAUNCH_SEARCH2_PLAY(1) Q2048_LAUNCH_SEARCH2_PLAY(2) Q2048_LAUNCH_SEARCH2_PLAY(3)
+    }
+  }
+#undef Q2048_LAUNCH_SEARCH2_PLAY
+  return launch_status();
+}
+template <int FAM>
+static int search_lookup_depth(const float* weights, const uint8_t* boards, int64_t B, int depth, float* q_out,
+                               uint8_t* legal_out, void* stream) {
+  if (int e = check_search_lookup_depth(weights, boards, B, depth, q_out, legal_out)) return e;
+  if (depth == 1) return search_lookup_impl<FAM>(weights, boards, B, q_out, legal_out, stream);
+  return search2_lookup_impl<FAM>(weights, boards, B, q_out, legal_out, stream);
+}
+template <int FAM>
+static int search_play_depth(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, int depth,
+                             double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                             double* stats_f, uint32_t* status, void* stream) {
+  if (int e = check_search_play_depth(boards, aux, weights, B, steps, depth, eps, flags, status)) return e;
+  if (depth == 1)
+    return search_play_impl<FAM>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status, stream);
+  return search2_play_impl<FAM>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, stream);
+}
 }  // extern "C++"
+int q2048_av_search_lookup_depth(const float* weights, const uint8_t* boards, int64_t B, int depth, float* q_out,
+                                 uint8_t* legal_out, void* stream) {
+  return search_lookup_depth<kFamAv>(weights, boards, B, depth, q_out, legal_out, stream);
+}
+int q2048_av_search_play_rollout_depth(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps,
+                                       int depth, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
+                                       int64_t* stats_i, double* stats_f, uint32_t* status, void* stream) {
+  return search_play_depth<kFamAv>(boards, aux, weights, B, steps, depth, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status, stream);
+}
+int q2048_nt_search_lookup_depth(const float* weights, const uint8_t* boards, int64_t B, int depth, float* q_out,
+                                 uint8_t* legal_out, void* stream) {
+  return search_lookup_depth<kFamNt>(weights, boards, B, depth, q_out, legal_out, stream);
+}
+int q2048_nt_search_play_rollout_depth(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps,
+                                       int depth, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
+                                       int64_t* stats_i, double* stats_f, uint32_t* status, void* stream) {
+  return search_play_depth<kFamNt>(boards, aux, weights, B, steps, depth, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status, stream);
+}
 int q2048_av_search_lookup(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out,
                            void* stream) {
   return search_lookup_impl<kFamAv>(weights, boards, B, q_out, legal_out, stream);

@@ -7,7 +7,8 @@ loads a learner written by `train.py --save` (a hash table, or -- "kind": "row_t
 weights, or -- "kind": "line_tuple" -- the line-tuple learner's, or -- "kind": "line_afterstate" -- the afterstate
 learner's values, or -- "kind": "ntuple6_afterstate" -- the 6-tuple afterstate network: the file says which, and the
 JSON line then carries "agent": "row-tuple" / "line-tuple" / "afterstate" / "ntuple"; `--fused --search` plays the two
-afterstate kinds with a one-level expectimax over the spawn, and the line carries "search": 1), plays `--episodes` games per env
+afterstate kinds with a one-level expectimax over the spawn, and the line carries "search": 1; `--search-depth 2` makes
+it two levels and "search": 2; the greedy players carry "search": 0), plays `--episodes` games per env
 with the stored values -- rows are read, nothing is created or written -- and prints one JSON line: games, mean
 score / return, max-tile histogram.  Two policies:
 
@@ -67,11 +68,18 @@ def parse_args(argv=None):
                         "ahead -- expectimax over the spawn (q2048_av_search_play_rollout / q2048_nt_search_play_rollout): a "
                         "move is worth its merge score plus the mean, over every cell and tile the spawn can produce, of "
                         "the greedy value of the resulting state")
+    p.add_argument("--search-depth", type=int, choices=[1, 2], default=None,
+                   help="with --search: levels of expectimax (default 1).  2: the value of a state the spawn leads to is "
+                        "the best of ITS searched row (q2048_{av,nt}_search_play_rollout_depth): up to 120 x 120 "
+                        "evaluations per move instead of 120")
     args = p.parse_args(argv)
     if args.fused and args.policy != "legal":
         p.error("--fused applies to --policy legal")
     if args.search and not args.fused:
         p.error("--search needs --fused: the one-level search runs in the fused player's kernel only")
+    if args.search_depth is not None and not args.search:
+        p.error("--search-depth needs --search: it is the depth of that search")
+    args.search_depth = (args.search_depth or 1) if args.search else 0      # 0: the greedy player
     return args
 
 
@@ -118,7 +126,7 @@ def main(argv=None):
            "valid_move_frac": st["valid_moves"] / max(st["steps"], 1),
            "max_tile_hist": {str(k): v for k, v in st["max_tile_hist"].items()},
            "best_tile": max(st["max_tile_hist"], default=0),
-           "search": int(args.search), "seconds": round(time.time() - t0, 3)}
+           "search": args.search_depth, "seconds": round(time.time() - t0, 3)}
     if args.fused:
         out["fused"] = True
     print(json.dumps(out))
@@ -163,7 +171,7 @@ def main_row_tuple(args, torch, pkg, sd):
            "valid_move_frac": st["valid_moves"] / max(st["steps"], 1),
            "max_tile_hist": {str(k): v for k, v in st["max_tile_hist"].items()},
            "best_tile": max(st["max_tile_hist"], default=0),
-           "search": int(args.search), "seconds": round(time.time() - t0, 3)}
+           "search": args.search_depth, "seconds": round(time.time() - t0, 3)}
     if args.fused:
         out["fused"] = True
     print(json.dumps(out))
@@ -176,7 +184,10 @@ def play_fused(agent, env, args, target) -> dict:
     agent.play_stats(reset=True)
     st = agent.play_stats()
     while st["episodes"] < target and env.ctr < args.max_steps:
-        (agent.search_rollout if args.search else agent.play_rollout)(env, args.steps_per_launch, args.epsilon)
+        if args.search:
+            agent.search_rollout(env, args.steps_per_launch, args.epsilon, depth=args.search_depth)
+        else:
+            agent.play_rollout(env, args.steps_per_launch, args.epsilon)
         st = agent.play_stats()
     games = max(st["episodes"], 1)
     st.update({"mean_score": st["score_sum"] / games, "mean_return": st["return_sum"] / games})

@@ -983,6 +983,39 @@ int q2048_nt_search_play_rollout(uint8_t *boards, q2048_aux *aux, const float *w
                                  double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
                                  int64_t *stats_i, double *stats_f, uint32_t *status, void *stream);
 
+/* ---- two-level expectimax: the searched row with a depth ---------------------------------------------------------
+ * Take c_a, score_a, legal_a and the family's best (call it best_0) as defined above.  For d >= 1 the DEPTH-d ROW of a
+ * state s is the searched row above with best_{d-1} in place of best:
+ *   a not legal   Q^d_a = 0.0f; nothing is evaluated for it.
+ *   a legal       for each empty cell j of c_a in ascending row-major order:
+ *                 t_j = 9.0 * (double)best_{d-1}(c_a with a 2 at j) + (double)best_{d-1}(c_a with a 4 at j);
+ *                 S_a = ((0.0 + t_j0) + t_j1) + ...: double additions in exactly that order;
+ *                 E_a = (float)(S_a / (double)(10 * n)); Q^d_a = (float)score_a + E_a.
+ *   best_d(x)     the depth-d row of x at the first maximum over the legal moves of x; 0.0f for a state without a legal
+ *                 move, and nothing is evaluated beneath such a state.
+ * Depth 1 is the searched row above, bit for bit.  Depth 2 evaluates at most 120 level-one nodes with at most 120
+ * leaves each: 14,400 evaluations of the family per state.  The order of every S sum, at both levels, is part of the
+ * contract: the device gives a board a block, spreads its level-one nodes over the block's waves and the leaves of a
+ * node over the lanes of a wave, and sums both levels in the order above, so both libraries give the same bits.
+ *   q2048_{av,nt}_search_lookup_depth        q2048_{av,nt}_search_lookup with `depth` after B.
+ *   q2048_{av,nt}_search_play_rollout_depth  q2048_{av,nt}_search_play_rollout with `depth` after steps: draws, flags,
+ *                 env profiles, statistics and episode handling unchanged.
+ * depth outside {1, 2} is Q2048_ERR_RANGE, checked before every other argument; then the checks of the function without
+ * a depth, in its order, with its codes.  With depth == 1 they ARE those functions (the same kernels, the same bytes).
+ * The weights are only read.  A refused call writes nothing; B == 0 or steps == 0 is Q2048_OK. */
+int q2048_av_search_lookup_depth(const float *weights, const uint8_t *boards, int64_t B, int depth, float *q_out,
+                                 uint8_t *legal_out, void *stream);
+int q2048_av_search_play_rollout_depth(uint8_t *boards, q2048_aux *aux, const float *weights, int64_t B, int64_t steps,
+                                       int depth, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0,
+                                       uint32_t flags, int64_t *stats_i, double *stats_f, uint32_t *status,
+                                       void *stream);
+int q2048_nt_search_lookup_depth(const float *weights, const uint8_t *boards, int64_t B, int depth, float *q_out,
+                                 uint8_t *legal_out, void *stream);
+int q2048_nt_search_play_rollout_depth(uint8_t *boards, q2048_aux *aux, const float *weights, int64_t B, int64_t steps,
+                                       int depth, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0,
+                                       uint32_t flags, int64_t *stats_i, double *stats_f, uint32_t *status,
+                                       void *stream);
+
 /* Inverse of q2048_table_export (resume / load a table trained elsewhere): inserts `rows`
  * (key, q[4]) pairs into the table, key_words as above.  A key already present has its row
  * overwritten in place (its slot and key words stay, the four values change); a row that finds no slot
