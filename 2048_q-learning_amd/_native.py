@@ -288,6 +288,26 @@ _SIGNATURES = {
     "q2048_nt_search_play_rollout_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
                                                      C.c_double, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the staged network: the q2048_nt_* lists with `stages` (uint32) directly after the weights
+    "q2048_nts_value": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "q2048_nts_lookup": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "q2048_nts_choose": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_double, C.c_uint64, C.c_uint64,
+                                   C.c_uint32, C.c_void_p, C.c_void_p]),
+    "q2048_nts_update": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "q2048_nts_fused_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64, C.c_int64,
+                                          C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_uint64,
+                                          C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "q2048_nts_play_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64, C.c_int64,
+                                         C.c_double, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "q2048_nts_search_lookup_depth": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
+    "q2048_nts_search_play_rollout_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64,
+                                                      C.c_int64, C.c_int, C.c_double, C.c_uint64, C.c_uint64,
+                                                      C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p]),
+    "q2048_nts_promote": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "q2048_table_import": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_int, C.c_void_p, C.c_void_p]),
     "q2048_table_export": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,

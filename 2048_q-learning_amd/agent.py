@@ -1830,7 +1830,12 @@ class BatchedAfterstateAgent(BatchedLineTupleAgent):
         if self._play_stats is None:
             self._play_stats = new_stats_vectors(self.device)
         si, sf = self._play_stats
-        if depth == 1:
+        if getattr(self, "stage_tiles", ()):      # the staged network (BatchedNTupleAgent): one entry point for both depths
+            N.check(self._L.q2048_nts_search_play_rollout_depth(
+                _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), self._stages, env.num_envs, int(steps), depth,
+                float(epsilon), env.seed, env.env_id0, env.ctr & 0xFFFFFFFF, env.env_flags, _ptr(si), _ptr(sf),
+                _ptr(self.status), _stream(self.device)), "nts_search_play_rollout_depth")
+        elif depth == 1:
             N.check(self._fn("search_play_rollout")(
                 _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), env.num_envs, int(steps), float(epsilon), env.seed,
                 env.env_id0, env.ctr & 0xFFFFFFFF, env.env_flags, _ptr(si), _ptr(sf), _ptr(self.status),
@@ -1893,19 +1898,132 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
     errors and the sum of their magnitudes -- and `update_q_value` / `fused_rollout` scale each entry's step by
     min(|E| / A, 1) (1 without history).  Everything that only reads V is inherited unchanged.  The checkpoint keeps
     its kind and carries the pairs under "coherence"; a plain agent loads such a file and ignores them, a coherence
-    agent loads a plain file and starts its pairs at zero (rates restart at 1, same values)."""
+    agent loads a plain file and starts its pairs at zero (rates restart at 1, same values).
+
+    `stage_tiles=(2048,)` makes the network MULTI-STAGE (q2048_nts_*): one table per stage of the game, V float32
+    [S, 4, 16777216] with S = 1 + the number of tiles given (powers of two, ascending, 2..32768, at most seven).  A
+    board reads the table of the stage its largest tile has reached -- stage = the number of given tiles it is >= --
+    and every candidate afterstate of an evaluation uses its own stage.  Every method goes through q2048_nts_*;
+    `stage_tiles=()` is the plain agent on the plain entry points.  `promote()` copies what an earlier stage has
+    learned into the entries of the next one that are still zero.  The checkpoint keeps its kind and carries
+    "stage_tiles"; a staged agent loads a plain file into stage 0 and promotes it through every stage, a file with
+    other tiles is refused, and a plain agent refuses a staged file.  Not combined with `coherence=True`."""
 
     _FAMILY, _SHAPE, _KIND, _WHAT = "nt", (4, 1 << 24), "ntuple6_afterstate", "a 6-tuple afterstate network"
     _ACC_SHAPE = (4, 1 << 24, 2)
 
     def __init__(self, total_epochs, action_space=4, learning_rate=0.1, discount_factor=0.9,
                  exploration_rate=1.0, exploration_min=0.01, device="cuda", seed: int = 0,
-                 env_id0: int = 0, coherence: bool = False):
+                 env_id0: int = 0, coherence: bool = False, stage_tiles=()):
+        self.stage_tiles = self._check_stage_tiles(stage_tiles)
+        if self.stage_tiles and coherence:
+            raise ValueError("coherence=True is not combined with stage_tiles: q2048_nt_tc_* knows one table")
+        # the stage spec of q2048_nts_*: nibble i = log2 of the (i + 1)-th threshold tile; 0 = the plain network
+        self._stages = sum((t.bit_length() - 1) << (4 * i) for i, t in enumerate(self.stage_tiles))
+        if self.stage_tiles:
+            self._SHAPE = (len(self.stage_tiles) + 1,) + type(self)._SHAPE      # [S, 4, 2^24], allocated by the base
         super().__init__(total_epochs, action_space, learning_rate, discount_factor, exploration_rate,
                          exploration_min, device, seed, env_id0)
         self.coherence = torch.zeros(self._ACC_SHAPE, dtype=torch.float32, device=self.device) if coherence else None
 
+    @staticmethod
+    def _check_stage_tiles(stage_tiles) -> tuple:
+        tiles = tuple(stage_tiles)
+        for t in tiles:
+            if isinstance(t, bool) or not isinstance(t, int) or t < 2 or t > 32768 or t & (t - 1):
+                raise ValueError(f"stage_tiles must be powers of two from 2 to 32768, not {t!r}")
+        if any(a >= b for a, b in zip(tiles, tiles[1:])):
+            raise ValueError(f"stage_tiles must ascend strictly, not {tiles!r}")
+        if len(tiles) > 7:
+            raise ValueError("at most seven stage_tiles (eight stages)")
+        return tiles
+
+    # ---- the staged network (stage_tiles given): every method through q2048_nts_*, the spec after the weights ----
+    def _nts(self, name: str):
+        return getattr(self._L, "q2048_nts_" + name)
+
+    def choose_action(self, boards) -> torch.Tensor:
+        if not self.stage_tiles:
+            return super().choose_action(boards)
+        boards = self._boards(boards)
+        B = boards.shape[0]
+        actions = torch.empty(B, dtype=torch.uint8, device=self.device)
+        N.check(self._nts("choose")(_ptr(self.weights), self._stages, _ptr(boards), B, float(self.epsilon),
+                                    self.seed, self.env_id0, self.ctr & 0xFFFFFFFF, _ptr(actions),
+                                    _stream(self.device)), "nts_choose")
+        self.ctr += 1
+        return actions
+
+    def q_values(self, boards) -> torch.Tensor:
+        if not self.stage_tiles:
+            return super().q_values(boards)
+        boards = self._boards(boards)
+        q = torch.empty((boards.shape[0], 4), dtype=torch.float32, device=self.device)
+        N.check(self._nts("lookup")(_ptr(self.weights), self._stages, _ptr(boards), boards.shape[0], _ptr(q),
+                                    _stream(self.device)), "nts_lookup")
+        return q
+
+    def values(self, boards) -> torch.Tensor:
+        if not self.stage_tiles:
+            return super().values(boards)
+        boards = self._boards(boards)
+        v = torch.empty((boards.shape[0],), dtype=torch.float32, device=self.device)
+        N.check(self._nts("value")(_ptr(self.weights), self._stages, _ptr(boards), boards.shape[0], _ptr(v),
+                                   _stream(self.device)), "nts_value")
+        return v
+
+    def play_rollout(self, env: BatchedGame2048Env, steps: int, epsilon: float = 0.0) -> None:
+        if not self.stage_tiles:
+            return super().play_rollout(env, steps, epsilon)
+        if env.device != self.device:
+            raise ValueError("env and agent live on different devices")
+        if env.board_size != 4:
+            raise ValueError("the afterstate learner plays 4x4 boards only")
+        if self._play_stats is None:
+            self._play_stats = new_stats_vectors(self.device)
+        si, sf = self._play_stats
+        N.check(self._nts("play_rollout")(
+            _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), self._stages, env.num_envs, int(steps), float(epsilon),
+            env.seed, env.env_id0, env.ctr & 0xFFFFFFFF, env.env_flags, _ptr(si), _ptr(sf), _ptr(self.status),
+            _stream(self.device)), "nts_play_rollout")
+        env.ctr += int(steps)
+
+    def search_lookup(self, boards, depth: int = 1):
+        if not self.stage_tiles:
+            return super().search_lookup(boards, depth)
+        depth = self._search_depth(depth)
+        boards = self._boards(boards)
+        B = boards.shape[0]
+        q = torch.empty((B, 4), dtype=torch.float32, device=self.device)
+        legal = torch.empty((B,), dtype=torch.uint8, device=self.device)
+        N.check(self._nts("search_lookup_depth")(_ptr(self.weights), self._stages, _ptr(boards), B, depth, _ptr(q),
+                                                 _ptr(legal), _stream(self.device)), "nts_search_lookup_depth")
+        return q, legal
+
+    def promote(self) -> list:
+        """BULK PROMOTION (q2048_nts_promote) over the pairs (0, 1), (1, 2), ... in ascending order: an entry of the
+        later stage whose bits are all zero takes the bits of the earlier stage's entry, where those are not zero.
+        Returns the number of entries copied per pair; synchronises."""
+        if not self.stage_tiles:
+            raise ValueError("this agent was built without stage_tiles")
+        counts = torch.zeros(len(self.stage_tiles), dtype=torch.int64, device=self.device)
+        for k in range(len(self.stage_tiles)):
+            N.check(self._nts("promote")(_ptr(self.weights), self._stages, k, k + 1, _ptr(counts[k:]),
+                                         _stream(self.device)), "nts_promote")
+        return [int(c) for c in counts.tolist()]
+
     def update_q_value(self, boards, actions, reward, next_boards, done) -> None:
+        if self.stage_tiles:
+            boards, next_boards = self._boards(boards), self._boards(next_boards)
+            B = boards.shape[0]
+            vec = lambda v, dt: torch.as_tensor(v).to(device=self.device, dtype=dt).contiguous()  # noqa: E731
+            actions, done = vec(actions, torch.uint8), vec(done, torch.uint8)
+            if not (actions.shape == tuple(torch.as_tensor(reward).shape) == done.shape == (B,)):
+                raise ValueError("actions / reward / done must have shape (B,)")
+            N.check(self._nts("update")(_ptr(self.weights), self._stages, _ptr(boards), _ptr(actions),
+                                        _ptr(next_boards), _ptr(done), B, float(self.lr), float(self.gamma),
+                                        _ptr(self.status), _stream(self.device)), "nts_update")
+            return None
         if self.coherence is None:
             return super().update_q_value(boards, actions, reward, next_boards, done)
         boards, next_boards = self._boards(boards), self._boards(next_boards)
@@ -1919,7 +2037,7 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
                                            _ptr(self.status), _stream(self.device)), "nt_tc_update")
 
     def fused_rollout(self, env: BatchedGame2048Env, steps: int) -> None:
-        if self.coherence is None:
+        if self.coherence is None and not self.stage_tiles:
             return super().fused_rollout(env, steps)
         if env.board_size != 4 or env.device != self.device:
             raise ValueError("the afterstate learner needs a 4x4 env on the same device")
@@ -1927,6 +2045,15 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
             raise ValueError("env profiles are supported by the hash-table agent only")
         if (env.seed, env.env_id0, env.ctr) != (self.seed, self.env_id0, self.ctr):
             raise ValueError("env and agent must share seed, env_id0 and step counter")
+        if self.stage_tiles:
+            N.check(self._nts("fused_rollout")(
+                _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), self._stages, env.num_envs, int(steps),
+                float(self.epsilon), float(self.lr), float(self.gamma), self.seed, self.env_id0,
+                self.ctr & 0xFFFFFFFF, _ptr(self.stats_i), _ptr(self.stats_f), _ptr(self.status),
+                _stream(self.device)), "nts_fused_rollout")
+            env.ctr += int(steps)
+            self.ctr += int(steps)
+            return None
         N.check(self._L.q2048_nt_tc_fused_rollout(
             _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), _ptr(self.coherence), env.num_envs, int(steps),
             float(self.epsilon), float(self.lr), float(self.gamma), self.seed, self.env_id0,
@@ -1953,11 +2080,32 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
         sd = super().state_dict(compact)
         if self.coherence is not None:
             sd["coherence"] = self.coherence.to("cpu", copy=True)
+        if self.stage_tiles:
+            sd["stage_tiles"] = list(self.stage_tiles)     # weights float32 [S, 4, 16777216]
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
         """Everything -- the pairs included, where this agent takes them -- is validated before anything of this agent
         is written.  A plain agent ignores a file's pairs; a coherence agent without pairs in the file zeroes its own."""
+        file_tiles = tuple(sd.get("stage_tiles") or ())
+        if sd.get("kind") == self._KIND and file_tiles != self.stage_tiles:
+            if not self.stage_tiles:
+                raise ValueError(f"this checkpoint holds a staged network (stage_tiles {list(file_tiles)}): a plain "
+                                 "BatchedNTupleAgent does not load it")
+            if file_tiles:
+                raise ValueError(f"this checkpoint's stage_tiles {list(file_tiles)} differ from the agent's "
+                                 f"{list(self.stage_tiles)}")
+            # a plain file into a staged agent: the file becomes stage 0, the later stages start at zero and take
+            # its values by promotion, so every stage equals the file
+            full, shape = self.weights, self._SHAPE
+            try:
+                self.weights, self._SHAPE = full[0], type(self)._SHAPE
+                super().load_state_dict(sd)           # validates everything, then writes stage 0
+            finally:
+                self.weights, self._SHAPE = full, shape
+            self.weights[1:].zero_()
+            self.promote()
+            return None
         acc = sd.get("coherence") if self.coherence is not None else None
         if acc is not None:
             if not isinstance(acc, torch.Tensor) or acc.dtype != torch.float32 or tuple(acc.shape) != self._ACC_SHAPE:

@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "q2048.h"
+#include "q2048_core.hpp"   // the stage spec of q2048_nts_* (nts_spec_ok, nts_count)
 
 namespace q2048 {
 
@@ -206,6 +207,60 @@ static inline int check_search_play_depth(const void* boards, const void* aux, c
                                           int64_t steps, int depth, double eps, uint32_t flags, const void* status) {
   if (depth != 1 && depth != 2) return Q2048_ERR_RANGE;
   return check_search_play(boards, aux, weights, B, steps, eps, flags, status);
+}
+
+// The staged network (q2048_nts_*): the stage spec first -- a malformed one is Q2048_ERR_RANGE whatever the other
+// arguments are, as the depth is -- then the checks of the q2048_nt_* counterpart, in its order, with its codes.
+// (What a well-formed spec is, and its S, are written in q2048_core.hpp: nts_spec_ok, nts_count.)
+static inline int check_nts_spec(uint32_t stages) { return nts_spec_ok(stages) ? Q2048_OK : Q2048_ERR_RANGE; }
+static inline int check_nts_value(const void* weights, uint32_t stages, const void* boards, int64_t B, const void* v_out) {
+  if (int e = check_nts_spec(stages)) return e;
+  return check_nt_value(weights, boards, B, v_out);
+}
+static inline int check_nts_lookup(const void* weights, uint32_t stages, const void* boards, int64_t B, const void* q_out) {
+  if (int e = check_nts_spec(stages)) return e;
+  return check_nt_lookup(weights, boards, B, q_out);
+}
+static inline int check_nts_choose(const void* weights, uint32_t stages, const void* boards, int64_t B, double eps,
+                                   const void* actions) {
+  if (int e = check_nts_spec(stages)) return e;
+  return check_nt_choose(weights, boards, B, eps, actions);
+}
+static inline int check_nts_update(const void* weights, uint32_t stages, const void* boards_s, const void* actions,
+                                   const void* boards_s2, const void* done, int64_t B, double lr, double gamma,
+                                   const void* status) {
+  if (int e = check_nts_spec(stages)) return e;
+  return check_nt_update(weights, boards_s, actions, boards_s2, done, B, lr, gamma, status);
+}
+static inline int check_nts_fused(const void* boards, const void* aux, const void* weights, uint32_t stages, int64_t B,
+                                  int64_t steps, double eps, double lr, double gamma, const void* status) {
+  if (int e = check_nts_spec(stages)) return e;
+  return check_nt_fused(boards, aux, weights, B, steps, eps, lr, gamma, status);
+}
+static inline int check_nts_play(const void* boards, const void* aux, const void* weights, uint32_t stages, int64_t B,
+                                 int64_t steps, double eps, uint32_t flags, const void* status) {
+  if (int e = check_nts_spec(stages)) return e;
+  return check_nt_play(boards, aux, weights, B, steps, eps, flags, status);
+}
+static inline int check_nts_search_lookup_depth(const void* weights, uint32_t stages, const void* boards, int64_t B,
+                                                int depth, const void* q_out, const void* legal_out) {
+  if (int e = check_nts_spec(stages)) return e;
+  return check_search_lookup_depth(weights, boards, B, depth, q_out, legal_out);
+}
+static inline int check_nts_search_play_depth(const void* boards, const void* aux, const void* weights, uint32_t stages,
+                                              int64_t B, int64_t steps, int depth, double eps, uint32_t flags,
+                                              const void* status) {
+  if (int e = check_nts_spec(stages)) return e;
+  return check_search_play_depth(boards, aux, weights, B, steps, depth, eps, flags, status);
+}
+// q2048_nts_promote: the spec, NULL, alignment, then the two stage numbers (from == to, or either >= S)
+static inline int check_nts_promote(const void* weights, uint32_t stages, int from, int to) {
+  if (int e = check_nts_spec(stages)) return e;
+  if (!weights) return Q2048_ERR_NULL;
+  if (!aligned16(weights)) return Q2048_ERR_ALIGN;
+  const int S = (int)nts_count(stages);
+  if (from < 0 || to < 0 || from >= S || to >= S || from == to) return Q2048_ERR_RANGE;
+  return Q2048_OK;
 }
 
 // q2048_strerror

@@ -1176,6 +1176,94 @@ Q_HD void nt_td(const Board& x, const NtEval& en, bool done, double lr, double g
     for (int g = 0; g < kNtImages; ++g) st(p, ix.i[p][g], n.e[p][g] + d);
 }
 
+// THE STAGED NETWORK (q2048_nts_*): a table per stage of the game, V = float[S][4][2^24], 1 <= S <= 8.  The largest
+// tile of a board selects its table.  `stages` holds the thresholds as nibbles: nibble i is t_{i+1}, a tile exponent
+// in 1..15 (the tile 2^t); the thresholds ascend strictly, the nonzero nibbles are contiguous from nibble 0 and the
+// top nibble is 0 (at most 7 thresholds); S = 1 + the number of nonzero nibbles; stages == 0 is the plain network.
+//   maxnib(x) = the largest nibble of pack_key(x)   (a cell >= 16 aliases by its low nibble, exactly as in nt_index)
+//   stage(x)  = the number of thresholds t_i with maxnib(x) >= t_i
+//   v(x)      = nt_v over the 32 entries of x taken from table stage(x)
+// In an evaluation of a state every candidate afterstate has its OWN stage: a merge that creates a threshold tile
+// puts that candidate in the next table while its siblings stay below.  The TD step is nt_td on table stage(c_act);
+// its target is the best of the staged evaluation of the next state.  q_a, best, the choice, live and target are the
+// afterstate family's.  A stage only selects the base of the table: the libraries hand in `ld_of(stage)` /
+// `st_of(stage)`, which give the `ld` / `st` of that table, and a staged evaluation makes the same 128 requests as a
+// plain one.
+constexpr int kNtsMaxStages = 8;
+constexpr size_t kNtsStageFloats = (size_t)kNtPatterns * kNtIdx;   // floats per stage table
+Q_HD bool nts_spec_ok(uint32_t stages) {
+  uint32_t prev = 0u;
+  bool ended = false;
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t t = (stages >> (4 * i)) & 15u;
+    if (t == 0u) { ended = true; continue; }
+    if (ended || t <= prev || i == 7) return false;
+    prev = t;
+  }
+  return true;
+}
+Q_HD uint32_t nts_count(uint32_t stages) {       // S of a well-formed spec
+  uint32_t n = 1u;
+  for (int i = 0; i < 7; ++i) n += ((stages >> (4 * i)) & 15u) != 0u;
+  return n;
+}
+Q_HD uint32_t nts_maxnib(uint64_t key) {
+  uint32_t m = 0u;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const uint32_t c = (uint32_t)(key >> (4 * i)) & 15u;
+    m = c > m ? c : m;
+  }
+  return m;
+}
+// (seven compares and adds on a wave-uniform spec; a zero nibble counts for nothing)
+Q_HD uint32_t nts_stage_of_key(uint64_t key, uint32_t stages) {
+  const uint32_t m = nts_maxnib(key);
+  uint32_t n = 0u;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    const uint32_t t = (stages >> (4 * i)) & 15u;
+    n += (uint32_t)(t != 0u && m >= t);
+  }
+  return n;
+}
+// the stage of a board, from the packed key that nt_indices forms too (one pack_key after inlining)
+Q_HD uint32_t nts_stage(const Board& x, uint32_t stages) {
+  bool overflow;
+  return nts_stage_of_key(pack_key(x, overflow), stages);
+}
+template <class LdOf>
+Q_HD float nts_v(const Board& x, uint32_t stages, LdOf ld_of) {
+  return nt_v(nt_gather(nt_indices(x), ld_of(nts_stage(x, stages))));
+}
+// nt_eval with each candidate's entries from the table of its own stage
+template <class LdOf>
+Q_HD NtEval nts_eval(const Board& s, uint32_t stages, LdOf ld_of) {
+  NtEval ev{Row{0.0f, 0.0f, 0.0f, 0.0f}, 0u};
+#pragma unroll 1
+  for (int a = 0; a < 4; ++a) {
+    Board m = s;
+    uint32_t score;
+    ev.legal |= (uint32_t)move(m, a, score) << a;
+    const float q = av_q(score, nts_v(m, stages, ld_of));
+    ev.q.q0 = a == 0 ? q : ev.q.q0;
+    ev.q.q1 = a == 1 ? q : ev.q.q1;
+    ev.q.q2 = a == 2 ? q : ev.q.q2;
+    ev.q.q3 = a == 3 ? q : ev.q.q3;
+  }
+  return ev;
+}
+// nt_td on the table of x's stage
+template <class LdOf, class StOf>
+Q_HD void nts_td(const Board& x, uint32_t stages, const NtEval& en, bool done, double lr, double gamma, LdOf ld_of,
+                 StOf st_of) {
+  const uint32_t k = nts_stage(x, stages);
+  nt_td(x, en, done, lr, gamma, ld_of(k), st_of(k));
+}
+// PROMOTION (q2048_nts_promote), on every (p, idx): if the bit pattern of V[to][p][idx] is 0x00000000 and that of
+// V[from][p][idx] is not, V[to][p][idx] takes the BITS of V[from][p][idx] (a NaN included); -0.0f counts as written.
+Q_HD bool nts_promotes(uint32_t to_bits, uint32_t from_bits) { return to_bits == 0u && from_bits != 0u; }
+
 // TEMPORAL-COHERENCE STEP SIZES for the network (q2048_nt_tc_*): beside V sits acc = float[4][2^24][2], acc[p][idx] =
 // {E, A}: the signed sum of the TD errors that weight has seen and the sum of their magnitudes.  Its own rate is
 // |E| / A: 1 while its errors agree in sign, towards 0 as they cancel.  A pair is loaded and stored whole (`ldp(p, idx)`,

@@ -911,6 +911,20 @@ struct NtBest {
   const float* v;
   float operator()(const Board& x) const { const NtEval ev = nt_eval(x, NtLd{v}); return av_best(ev.legal, ev.q); }
 };
+// the staged network: the table of a stage, and its best
+struct NtsLdOf {
+  const float* v;
+  NtLd operator()(uint32_t stage) const { return NtLd{v + (size_t)stage * kNtsStageFloats}; }
+};
+struct NtsStOf {
+  float* v;
+  NtSt operator()(uint32_t stage) const { return NtSt{v + (size_t)stage * kNtsStageFloats}; }
+};
+struct NtsBest {
+  const float* v;
+  uint32_t stages;
+  float operator()(const Board& x) const { const NtEval ev = nts_eval(x, stages, NtsLdOf{v}); return av_best(ev.legal, ev.q); }
+};
 // (DEPTH 2: the two-level row, search_row2 -- the same serial walk one level further down)
 template <class Best, int DEPTH = 1>
 inline SearchEval search_eval(const Board& s, const Best& best) {
@@ -2255,6 +2269,228 @@ int q2048_nt_search_play_rollout_depth(uint8_t* boards, q2048_aux* aux, const fl
   return depth == 1
       ? search_play_impl<NtBest, 1>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status)
       : search_play_impl<NtBest, 2>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status);
+}
+
+// ---- the staged network (q2048_nts_*): the functions above with nts_eval / nts_td, the table picked per candidate ----
+int q2048_nts_value(const float* weights, uint32_t stages, const uint8_t* boards, int64_t B, float* v_out, void*) {
+  if (int e = check_nts_value(weights, stages, boards, B, v_out)) return e;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Board b;
+      load_board(boards, i, b);
+      v_out[i] = nts_v(b, stages, NtsLdOf{weights});
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_nts_lookup(const float* weights, uint32_t stages, const uint8_t* boards, int64_t B, float* q_out, void*) {
+  if (int e = check_nts_lookup(weights, stages, boards, B, q_out)) return e;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Board b;
+      load_board(boards, i, b);
+      const Row q = nts_eval(b, stages, NtsLdOf{weights}).q;
+      q_out[4 * i] = q.q0; q_out[4 * i + 1] = q.q1; q_out[4 * i + 2] = q.q2; q_out[4 * i + 3] = q.q3;
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_nts_choose(const float* weights, uint32_t stages, const uint8_t* boards, int64_t B, double eps, uint64_t seed,
+                     uint64_t env_id0, uint32_t ctr, uint8_t* actions, void*) {
+  if (int e = check_nts_choose(weights, stages, boards, B, eps, actions)) return e;
+  const uint64_t eps_t = eps_threshold(eps);
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Board b;
+      load_board(boards, i, b);
+      const Draws x = draws(seed, env_id0 + (uint64_t)i, ctr, kStreamStep);
+      const NtEval ev = nts_eval(b, stages, NtsLdOf{weights});
+      bool explored;
+      actions[i] = (uint8_t)play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_nts_update(float* weights, uint32_t stages, const uint8_t* boards_s, const uint8_t* actions,
+                     const uint8_t* boards_s2, const uint8_t* done, int64_t B, double lr, double gamma, uint32_t* status,
+                     void*) {
+  if (int e = check_nts_update(weights, stages, boards_s, actions, boards_s2, done, B, lr, gamma, status)) return e;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      const int act = actions[i];
+      if (act > 3) { status_or(status, Q2048_STATUS_BAD_ACTION); continue; }
+      Board x, b_n;
+      load_board(boards_s, i, x);
+      load_board(boards_s2, i, b_n);
+      uint32_t score;
+      if (!move(x, act, score)) continue;   // the step on which the env reports the end
+      const NtEval en = nts_eval(b_n, stages, NtsLdOf{weights});
+      nts_td(x, stages, en, done[i] != 0, lr, gamma, NtsLdOf{weights}, NtsStOf{weights});
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_nts_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, uint32_t stages, int64_t B, int64_t steps,
+                            double eps, double lr, double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0,
+                            int64_t* stats_i, double* stats_f, uint32_t* status, void*) {
+  if (int e = check_nts_fused(boards, aux, weights, stages, B, steps, eps, lr, gamma, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  const uint64_t eps_t = eps_threshold(eps);
+  const int T = threads_for(B);
+  std::vector<Stats> parts((size_t)T);
+  Stats* sp = parts.data();
+  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+    Stats& st = sp[tid];
+    for (int64_t i = lo; i < hi; ++i) {
+      const uint64_t id = env_id0 + (uint64_t)i;
+      Board b;
+      load_board(boards, i, b);
+      Aux a = ld_aux(aux, i);
+      double reward_sum = 0.0;
+      for (int64_t t = 0; t < steps; ++t) {
+        const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+        const NtEval ev = nts_eval(b, stages, NtsLdOf{weights});
+        bool explored;
+        const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+        Board c = b;                    // the afterstate of the move played
+        uint32_t score;
+        const bool legal = move(c, act, score);
+        const StepOut o = env_step(b, a, act, x.x2, x.x3);
+        const NtEval en = nts_eval(b, stages, NtsLdOf{weights});
+        if (legal) nts_td(c, stages, en, o.done != 0, lr, gamma, NtsLdOf{weights}, NtsStOf{weights});
+        st.i[Q2048_ST_VALID] += o.valid != 0;
+        st.i[Q2048_ST_EXPLORE] += explored;
+        reward_sum += (double)o.reward;
+        if (o.done) {
+          st.i[Q2048_ST_EPISODES] += 1;
+          st.episode(a, o.max_log2);
+          begin_episode(b, a, seed, id);
+        }
+      }
+      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
+      st.f[Q2048_SF_REWARD] += reward_sum;
+      store_board(boards, i, b);
+      st_aux(aux, i, a);
+    }
+  });
+  stats_merge(parts, used, stats_i, stats_f);
+  return Q2048_OK;
+}
+// the players: one loop for the greedy row (DEPTH 0) and the searched rows (DEPTH 1, 2); the callers have checked
+extern "C++" {
+template <int DEPTH>
+static SearchEval nts_row(const Board& b, const NtsBest& best) {
+  if constexpr (DEPTH == 0) {
+    const NtEval ev = nts_eval(b, best.stages, NtsLdOf{best.v});
+    return SearchEval{ev.q, ev.legal};
+  } else {
+    return search_eval<NtsBest, DEPTH>(b, best);
+  }
+}
+template <int DEPTH>
+static int nts_play_impl(uint8_t* boards, q2048_aux* aux, const float* weights, uint32_t stages, int64_t B, int64_t steps,
+                         double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                         double* stats_f) {
+  if (B == 0 || steps == 0) return Q2048_OK;
+  const uint64_t eps_t = eps_threshold(eps);
+  const ImageLuts lut{&g_lut_image};
+  const int env = env_bits(flags);
+  const int T = threads_for(B);
+  std::vector<Stats> parts((size_t)T);
+  Stats* sp = parts.data();
+  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+    Stats& st = sp[tid];
+    for (int64_t i = lo; i < hi; ++i) {
+      const uint64_t id = env_id0 + (uint64_t)i;
+      Board b;
+      load_board(boards, i, b);
+      Aux a = ld_aux(aux, i);
+      const DrawPrep prep = draws_prepare(seed, id, kStreamStep);
+      double reward_sum = 0.0;
+      for (int64_t t = 0; t < steps; ++t) {
+        const Draws x = draws_at(prep, ctr0 + (uint32_t)t);
+        Draws y{0u, 0u, 0u, 0u};
+        if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+        const SearchEval ev = nts_row<DEPTH>(b, NtsBest{weights, stages});
+        bool explored;
+        const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+        const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+        st.i[Q2048_ST_VALID] += o.valid != 0;
+        st.i[Q2048_ST_EXPLORE] += explored;
+        reward_sum += (double)o.reward;
+        if (o.done) {
+          st.i[Q2048_ST_EPISODES] += 1;
+          st.episode(a, o.max_log2);
+          begin_episode(b, a, seed, id, (env & kEnvResetShaping) != 0);
+        }
+      }
+      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
+      st.f[Q2048_SF_REWARD] += reward_sum;
+      store_board(boards, i, b);
+      st_aux(aux, i, a);
+    }
+  });
+  stats_merge(parts, used, stats_i, stats_f);
+  return Q2048_OK;
+}
+}  // extern "C++"
+int q2048_nts_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, uint32_t stages, int64_t B, int64_t steps,
+                           double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                           double* stats_f, uint32_t* status, void*) {
+  if (int e = check_nts_play(boards, aux, weights, stages, B, steps, eps, flags, status)) return e;
+  return nts_play_impl<0>(boards, aux, weights, stages, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f);
+}
+int q2048_nts_search_lookup_depth(const float* weights, uint32_t stages, const uint8_t* boards, int64_t B, int depth,
+                                  float* q_out, uint8_t* legal_out, void*) {
+  if (int e = check_nts_search_lookup_depth(weights, stages, boards, B, depth, q_out, legal_out)) return e;
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Board b;
+      load_board(boards, i, b);
+      const NtsBest best{weights, stages};
+      const SearchEval ev = depth == 1 ? nts_row<1>(b, best) : nts_row<2>(b, best);
+      q_out[4 * i] = ev.q.q0; q_out[4 * i + 1] = ev.q.q1; q_out[4 * i + 2] = ev.q.q2; q_out[4 * i + 3] = ev.q.q3;
+      legal_out[i] = (uint8_t)ev.legal;
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_nts_search_play_rollout_depth(uint8_t* boards, q2048_aux* aux, const float* weights, uint32_t stages, int64_t B,
+                                        int64_t steps, int depth, double eps, uint64_t seed, uint64_t env_id0,
+                                        uint32_t ctr0, uint32_t flags, int64_t* stats_i, double* stats_f,
+                                        uint32_t* status, void*) {
+  if (int e = check_nts_search_play_depth(boards, aux, weights, stages, B, steps, depth, eps, flags, status)) return e;
+  return depth == 1
+      ? nts_play_impl<1>(boards, aux, weights, stages, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f)
+      : nts_play_impl<2>(boards, aux, weights, stages, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f);
+}
+// promotion: the rule of nts_promotes on every entry, bits in and bits out
+int q2048_nts_promote(float* weights, uint32_t stages, int from, int to, int64_t* count_out, void*) {
+  if (int e = check_nts_promote(weights, stages, from, to)) return e;
+  float* dst = weights + (size_t)to * kNtsStageFloats;
+  const float* src = weights + (size_t)from * kNtsStageFloats;
+  const int64_t n = (int64_t)kNtsStageFloats;
+  std::vector<int64_t> parts((size_t)threads_for(n), 0);
+  int64_t* pp = parts.data();
+  const int used = parallel_ranges(n, [=](int64_t lo, int64_t hi, int tid) {
+    int64_t copied = 0;
+    for (int64_t i = lo; i < hi; ++i) {
+      uint32_t d, s;
+      std::memcpy(&d, dst + i, sizeof d);
+      std::memcpy(&s, src + i, sizeof s);
+      if (nts_promotes(d, s)) {
+        std::memcpy(dst + i, &s, sizeof s);
+        ++copied;
+      }
+    }
+    pp[tid] = copied;
+  });
+  if (count_out != nullptr) {
+    int64_t total = 0;
+    for (int t = 0; t < used; ++t) total += parts[(size_t)t];
+    *count_out = total;
+  }
+  return Q2048_OK;
 }
 
 }  // extern "C"

@@ -2993,6 +2993,393 @@ __global__ __launch_bounds__(kBlock) void k_search2_play_rollout(
 }
 
 // ---------------------------------------------------------------------------------------------
+// The staged network (q2048_nts_*; the contract is "THE STAGED NETWORK" in q2048_core.hpp):
+// V = float[S][4][2^24], the largest tile of a board selects its table.  k_nt_* with nts_eval /
+// nts_td for nt_eval / nt_td: per candidate the stage comes from the packed key the index arithmetic
+// forms anyway (16 field extracts and maxima, seven compares against the wave-uniform spec), and ONE
+// 64-bit offset (stage * 256 MiB) is added to the base before the 32 back-to-back loads -- the loads
+// themselves are NtLd's, unchanged.  The `stages` word is a kernel argument (an SGPR).  Relaxed
+// agent-scope atomic loads in the learner kernels, ordinary loads in the players.  The search has
+// kernels of its own that call search_row / search_node / search2_cells / search2_slot unchanged:
+// the spec would otherwise have to travel through search_wave<FAM> and every function built on it.
+// Kernels of their own; no existing kernel changes.
+// ---------------------------------------------------------------------------------------------
+template <bool AGENT>
+struct NtsLdOf {
+  const float* v;
+  __device__ __forceinline__ NtLd<AGENT> operator()(uint32_t stage) const {
+    return NtLd<AGENT>{v + (size_t)stage * kNtsStageFloats};
+  }
+};
+struct NtsStOf {
+  float* v;
+  __device__ __forceinline__ NtSt operator()(uint32_t stage) const { return NtSt{v + (size_t)stage * kNtsStageFloats}; }
+};
+
+__global__ __launch_bounds__(kBlock) void k_nts_value(const float* w, uint32_t stages, const uint8_t* boards, int64_t B,
+                                                      float* v_out) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  v_out[i] = nts_v(load_board(boards, i, B, st), stages, NtsLdOf<true>{w});
+}
+
+__global__ __launch_bounds__(kBlock) void k_nts_lookup(const float* w, uint32_t stages, const uint8_t* boards, int64_t B,
+                                                       float* q_out) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const Row q = nts_eval(load_board(boards, i, B, st), stages, NtsLdOf<true>{w}).q;
+  reinterpret_cast<float4*>(q_out)[i] = make_float4(q.q0, q.q1, q.q2, q.q3);
+}
+
+__global__ __launch_bounds__(kBlock) void k_nts_choose(const float* w, uint32_t stages, const uint8_t* boards, int64_t B,
+                                                       double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr,
+                                                       uint8_t* actions) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const Board b = load_board(boards, i, B, st);
+  const Draws x = draws(seed, env_id0 + (uint64_t)i, ctr, kStreamStep);
+  const NtEval ev = nts_eval(b, stages, NtsLdOf<true>{w});
+  bool explored;
+  actions[i] = (uint8_t)play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_threshold(eps), x.x0, x.x1, explored);
+}
+
+__global__ __launch_bounds__(kBlock) void k_nts_update(float* w, uint32_t stages, const uint8_t* s, const uint8_t* actions,
+                                                       const uint8_t* s2, const uint8_t* done, int64_t B, double lr,
+                                                       double gamma, uint32_t* status) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const int act = actions[i];
+  if (act > 3) { atomicOr(status, Q2048_STATUS_BAD_ACTION); return; }
+  Board x = load_board(s, i, B, st);
+  const Board b_n = load_board(s2, i, B, st);
+  uint32_t score;
+  if (!move(x, act, score)) return;   // the step on which the env reports the end
+  const NtEval en = nts_eval(b_n, stages, NtsLdOf<true>{w});
+  nts_td(x, stages, en, done[i] != 0, lr, gamma, NtsLdOf<true>{w}, NtsStOf{w});
+}
+
+__global__ __launch_bounds__(kBlock) void k_nts_fused_rollout(
+    uint8_t* boards, q2048_aux* aux, float* w, uint32_t stages, int64_t B, int steps, double eps, double lr,
+    double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f,
+    uint32_t* /*status: as on k_nt_fused_rollout*/) {
+  __shared__ BlockStats bs;
+  stats_clear(bs);
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < B) {
+    Stage<4> st;
+    const uint64_t id = env_id0 + (uint64_t)i;
+    Board b = load_board(boards, i, B, st);
+    Aux a = ld_aux(aux, i);
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
+    double reward_sum = 0.0;
+    const uint64_t eps_t = eps_threshold(eps);
+    for (int t = 0; t < steps; ++t) {
+      const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+      const NtEval ev = nts_eval(b, stages, NtsLdOf<true>{w});   // from memory on every step, as in k_nt_fused_rollout
+      bool explored;
+      const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+      Board c = b;                    // the afterstate of the move played
+      uint32_t score;
+      const bool legal = move(c, act, score);
+      const StepOut o = env_step(b, a, act, x.x2, x.x3);
+      const NtEval en = nts_eval(b, stages, NtsLdOf<true>{w});
+      if (legal) nts_td(c, stages, en, o.done != 0, lr, gamma, NtsLdOf<true>{w}, NtsStOf{w});
+      n_valid += wave_count(o.valid != 0);
+      n_explore += wave_count(explored);
+      n_done += wave_count(o.done != 0);
+      reward_sum += (double)o.reward;
+      if (o.done) {
+        episode_stats(bs, a, o.max_log2);
+        begin_episode(b, a, seed, id);
+      }
+    }
+    store_board(boards, i, B, b, st);
+    st_aux(aux, i, a);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+    const uint32_t n_active = wave_count(true);
+    if (wave_leader()) {
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  stats_flush(bs, stats_i, stats_f);
+}
+
+// the greedy player on the staged network (q2048_nts_play_rollout): k_nt_play_rollout with q2048_nts_lookup's row
+template <int ENV>
+__global__ __launch_bounds__(kBlock) void k_nts_play_rollout(
+    uint8_t* boards, q2048_aux* aux, const float* w, uint32_t stages, int64_t B, int steps, double eps, uint64_t seed,
+    uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
+  __shared__ BlockStats bs;
+  __shared__ Stage<4> st;
+  __shared__ LutImage lut_lds;
+  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
+  if (threadIdx.x < kLutImageDoubles)
+    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
+  stats_clear(bs);                                        // (its barrier publishes the image too)
+  const ImageLuts lut{&lut_lds};
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  Board b = load_board(boards, i, B, st);
+  if (i < B) {
+    const uint64_t id = env_id0 + (uint64_t)i;
+    Aux a = ld_aux(aux, i);
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
+    double reward_sum = 0.0;
+    const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
+    const uint64_t eps_t = eps_threshold(eps);
+    for (int t = 0; t < steps; ++t) {
+      const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
+      Draws y{0u, 0u, 0u, 0u};
+      if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+      const NtEval ev = nts_eval(b, stages, NtsLdOf<false>{w});
+      bool explored;
+      const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+      if (o.done) {
+        episode_stats(bs, a, o.max_log2);
+        begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
+      }
+      n_valid += wave_count(o.valid != 0);
+      n_explore += wave_count(explored);
+      n_done += wave_count(o.done != 0);
+      reward_sum += (double)o.reward;
+    }
+    st_aux(aux, i, a);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+    const uint32_t n_active = wave_count(true);
+    if (wave_leader()) {
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  store_board(boards, i, B, b, st);
+  stats_flush(bs, stats_i, stats_f);
+}
+
+// ---- the search on the staged network: search_wave / search2_block and their four kernels with the staged best.  Every
+// chance node and every leaf is evaluated with nts_eval, so each of ITS candidates reads the table of its own stage (the
+// spawn of a threshold tile, or a merge at either level, crosses into the next table).  The slots, the compaction
+// over lanes and waves, the LDS arrays and both orderings are those kernels'; see their comments.
+__device__ __forceinline__ float nts_search_best(const float* w, uint32_t stages, const Board& x) {
+  const NtEval ev = nts_eval(x, stages, NtsLdOf<false>{w});
+  return av_best(ev.legal, ev.q);
+}
+__device__ __forceinline__ SearchEval nts_search_wave(const float* w, uint32_t stages, const Board& s, float* best) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const u64 cells = search2_cells(s);
+  const uint32_t total = 2u * (uint32_t)__popcll(cells);  // <= 120
+#pragma unroll 1
+  for (uint32_t k = lane; k < total; k += 64u) {          // at most two rounds
+    const uint32_t slot = search2_slot(cells, k);         // < kSearchSlots
+    Board node;
+    if (search_node(s, slot, node)) best[slot] = nts_search_best(w, stages, node);   // (live by construction)
+  }
+  wave_lds_sync();                                        // the nodes are published before any lane sums them
+  const SearchEval ev = search_row(s, [best](uint32_t slot, const Board&) { return best[slot]; });
+  wave_lds_sync();                                        // and summed before the next step publishes again
+  return ev;
+}
+
+__global__ __launch_bounds__(kBlock) void k_nts_search_lookup(const float* w, uint32_t stages, const uint8_t* boards,
+                                                              int64_t first, int64_t B, float* q_out, uint8_t* legal_out) {
+  __shared__ float best[kSearchBoards][kSearchSlots];
+  __shared__ Stage<4> st;
+  const int wave = (int)(threadIdx.x >> 6);
+  const int64_t i = first + (int64_t)blockIdx.x * kSearchBoards + wave;
+  if (i >= B) return;                                     // (no block barrier in this kernel)
+  const SearchEval ev = nts_search_wave(w, stages, load_board(boards, i, B, st), best[wave]);
+  if ((threadIdx.x & 63u) == 0u) {
+    reinterpret_cast<float4*>(q_out)[i] = make_float4(ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3);
+    legal_out[i] = (uint8_t)ev.legal;
+  }
+}
+
+template <int ENV>
+__global__ __launch_bounds__(kBlock) void k_nts_search_play_rollout(
+    uint8_t* boards, q2048_aux* aux, const float* w, uint32_t stages, int64_t first, int64_t B, int steps, double eps,
+    uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
+  __shared__ BlockStats bs;
+  __shared__ Stage<4> st;
+  __shared__ LutImage lut_lds;
+  __shared__ float best[kSearchBoards][kSearchSlots];
+  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
+  if (threadIdx.x < kLutImageDoubles)
+    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
+  stats_clear(bs);                                        // (its barrier publishes the image too)
+  const ImageLuts lut{&lut_lds};
+  const int wave = (int)(threadIdx.x >> 6);
+  const bool first_lane = (threadIdx.x & 63u) == 0u;
+  const int64_t i = first + (int64_t)blockIdx.x * kSearchBoards + wave;   // wave-uniform
+  if (i < B) {
+    const uint64_t id = env_id0 + (uint64_t)i;
+    Board b = load_board(boards, i, B, st);
+    Aux a = ld_aux(aux, i);
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;      // of this BOARD: the same in every lane
+    double reward_sum = 0.0;
+    const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
+    const uint64_t eps_t = eps_threshold(eps);
+    for (int t = 0; t < steps; ++t) {
+      const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
+      Draws y{0u, 0u, 0u, 0u};
+      if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+      const SearchEval ev = nts_search_wave(w, stages, b, best[wave]);
+      bool explored;
+      const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+      if (o.done) {
+        if (first_lane) episode_stats(bs, a, o.max_log2);
+        begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
+      }
+      n_valid += o.valid != 0;
+      n_explore += explored;
+      n_done += o.done != 0;
+      reward_sum += (double)o.reward;
+    }
+    if (first_lane) {
+      store_board(boards, i, B, b, st);
+      st_aux(aux, i, a);
+      atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)steps);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  stats_flush(bs, stats_i, stats_f);
+}
+
+// the depth-2 row of the block's board (search2_block with the staged leaves).  Every thread of the block calls it.
+__device__ __forceinline__ SearchEval nts_search2_block(const float* w, uint32_t stages, const Board& s, float* leaf,
+                                                        float* best1) {
+  const uint32_t wave = threadIdx.x >> 6;
+  const u64 cells = search2_cells(s);
+  const uint32_t total = 2u * (uint32_t)__popcll(cells);  // <= 120
+#pragma unroll 1
+  for (uint32_t k = wave; k < total; k += (uint32_t)kSearch2Waves) {   // wave-uniform: no block barrier in here
+    const uint32_t slot = search2_slot(cells, k);
+    Board node;
+    search_node(s, slot, node);                           // (live by construction)
+    const float b = search_best_of(nts_search_wave(w, stages, node, leaf));
+    if ((threadIdx.x & 63u) == 0u) best1[slot] = b;
+  }
+  __syncthreads();                                        // the level-one nodes are published before any lane sums them
+  const SearchEval ev = search_row(s, [best1](uint32_t slot, const Board&) { return best1[slot]; });
+  __syncthreads();                                        // and summed before the next step publishes again
+  return ev;
+}
+
+__global__ __launch_bounds__(kBlock) void k_nts_search2_lookup(const float* w, uint32_t stages, const uint8_t* boards,
+                                                               int64_t first, int64_t B, float* q_out, uint8_t* legal_out) {
+  __shared__ float leaf[kSearch2Waves][kSearchSlots];
+  __shared__ float best1[kSearchSlots];
+  __shared__ Stage<4> st;
+  const int64_t i = first + (int64_t)blockIdx.x;          // < B: the grid is the launch's boards
+  const SearchEval ev = nts_search2_block(w, stages, load_board(boards, i, B, st), leaf[threadIdx.x >> 6], best1);
+  if (threadIdx.x == 0u && i < B) {
+    reinterpret_cast<float4*>(q_out)[i] = make_float4(ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3);
+    legal_out[i] = (uint8_t)ev.legal;
+  }
+}
+
+template <int ENV>
+__global__ __launch_bounds__(kBlock) void k_nts_search2_play_rollout(
+    uint8_t* boards, q2048_aux* aux, const float* w, uint32_t stages, int64_t first, int64_t B, int steps, double eps,
+    uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
+  __shared__ BlockStats bs;
+  __shared__ Stage<4> st;
+  __shared__ LutImage lut_lds;
+  __shared__ float leaf[kSearch2Waves][kSearchSlots];
+  __shared__ float best1[kSearchSlots];
+  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
+  if (threadIdx.x < kLutImageDoubles)
+    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
+  stats_clear(bs);                                        // (its barrier publishes the image too)
+  const ImageLuts lut{&lut_lds};
+  const bool first_thread = threadIdx.x == 0u;
+  const int64_t i = first + (int64_t)blockIdx.x;          // block-uniform, < B: the grid is the launch's boards
+  const uint64_t id = env_id0 + (uint64_t)i;
+  Board b = load_board(boards, i, B, st);
+  Aux a = ld_aux(aux, i);
+  uint32_t n_valid = 0, n_explore = 0, n_done = 0;        // of this BOARD: the same in every thread
+  double reward_sum = 0.0;
+  const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
+  const uint64_t eps_t = eps_threshold(eps);
+  for (int t = 0; t < steps; ++t) {
+    const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
+    Draws y{0u, 0u, 0u, 0u};
+    if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
+    const SearchEval ev = nts_search2_block(w, stages, b, leaf[threadIdx.x >> 6], best1);
+    bool explored;
+    const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+    const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
+    if (o.done) {
+      if (first_thread) episode_stats(bs, a, o.max_log2);
+      begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
+    }
+    n_valid += o.valid != 0;
+    n_explore += explored;
+    n_done += o.done != 0;
+    reward_sum += (double)o.reward;
+  }
+  if (first_thread) {
+    store_board(boards, i, B, b, st);
+    st_aux(aux, i, a);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+    atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)steps);
+    atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+    atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+    atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+  }
+  stats_flush(bs, stats_i, stats_f);
+}
+
+// ---- promotion (q2048_nts_promote): one streaming pass over two stage tables, 2^24 groups of four entries each.  A lane
+// takes kPromoteGroups groups, a block's lanes on consecutive groups: 16-byte loads of the destination and of the source
+// (all in flight together), and ONE 16-byte vector store of the merged group where at least one of its entries is
+// copied -- a lane that copies nothing stores nothing, so an untouched group is never written.  The copies are counted
+// per lane, summed over the wave by shuffles and over the block through LDS; thread 0 adds the block's sum with one atomic.
+constexpr int kPromoteGroups = 4;
+constexpr uint32_t kPromoteBlocks = (uint32_t)(kNtsStageFloats / 4 / ((size_t)kBlock * kPromoteGroups));
+static_assert((size_t)kPromoteBlocks * kBlock * kPromoteGroups * 4 == kNtsStageFloats, "the grid covers a stage table exactly");
+__global__ __launch_bounds__(kBlock) void k_nts_promote(float* to, const float* from, u64* count) {
+  __shared__ uint32_t wave_n[kBlock / 64];
+  const size_t g0 = (size_t)blockIdx.x * (kBlock * kPromoteGroups) + threadIdx.x;   // < 2^24 by the grid
+  uint4 d[kPromoteGroups], s[kPromoteGroups];
+#pragma unroll
+  for (int j = 0; j < kPromoteGroups; ++j) d[j] = reinterpret_cast<const uint4*>(to)[g0 + (size_t)j * kBlock];
+#pragma unroll
+  for (int j = 0; j < kPromoteGroups; ++j) s[j] = reinterpret_cast<const uint4*>(from)[g0 + (size_t)j * kBlock];
+  uint32_t n = 0u;
+#pragma unroll
+  for (int j = 0; j < kPromoteGroups; ++j) {
+    const bool c0 = nts_promotes(d[j].x, s[j].x), c1 = nts_promotes(d[j].y, s[j].y);
+    const bool c2 = nts_promotes(d[j].z, s[j].z), c3 = nts_promotes(d[j].w, s[j].w);
+    if (c0 || c1 || c2 || c3)
+      reinterpret_cast<uint4*>(to)[g0 + (size_t)j * kBlock] =
+          make_uint4(c0 ? s[j].x : d[j].x, c1 ? s[j].y : d[j].y, c2 ? s[j].z : d[j].z, c3 ? s[j].w : d[j].w);
+    n += (uint32_t)c0 + (uint32_t)c1 + (uint32_t)c2 + (uint32_t)c3;
+  }
+#pragma unroll
+  for (int k = 32; k >= 1; k >>= 1) n += __shfl_xor(n, k);
+  if ((threadIdx.x & 63u) == 0u) wave_n[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0u && count != nullptr) {
+    uint32_t total = 0u;
+#pragma unroll
+    for (int k = 0; k < kBlock / 64; ++k) total += wave_n[k];
+    if (total != 0u) atomicAdd(count, (u64)total);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // table utilities
 // ---------------------------------------------------------------------------------------------
 // Streams the whole table once, in tiles of 16 Ki slots per block: a lane reads the first 16 bytes
@@ -4292,6 +4679,113 @@ int q2048_nt_search_play_rollout(uint8_t* boards, q2048_aux* aux, const float* w
                                  uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                                  double* stats_f, uint32_t* status, void* stream) {
   return search_play_impl<kFamNt>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status, stream);
+}
+
+// ---- the staged network: the q2048_nt_* entry points with `stages` directly after `weights` ----
+int q2048_nts_value(const float* weights, uint32_t stages, const uint8_t* boards, int64_t B, float* v_out, void* stream) {
+  if (int e = check_nts_value(weights, stages, boards, B, v_out)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_nts_value, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights, stages, boards, B, v_out);
+  return launch_status();
+}
+int q2048_nts_lookup(const float* weights, uint32_t stages, const uint8_t* boards, int64_t B, float* q_out, void* stream) {
+  if (int e = check_nts_lookup(weights, stages, boards, B, q_out)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_nts_lookup, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights, stages, boards, B, q_out);
+  return launch_status();
+}
+int q2048_nts_choose(const float* weights, uint32_t stages, const uint8_t* boards, int64_t B, double eps, uint64_t seed,
+                     uint64_t env_id0, uint32_t ctr, uint8_t* actions, void* stream) {
+  if (int e = check_nts_choose(weights, stages, boards, B, eps, actions)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_nts_choose, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights, stages,
+                     boards, B, eps, seed, env_id0, ctr, actions);
+  return launch_status();
+}
+int q2048_nts_update(float* weights, uint32_t stages, const uint8_t* boards_s, const uint8_t* actions,
+                     const uint8_t* boards_s2, const uint8_t* done, int64_t B, double lr, double gamma, uint32_t* status,
+                     void* stream) {
+  if (int e = check_nts_update(weights, stages, boards_s, actions, boards_s2, done, B, lr, gamma, status)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_nts_update, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights, stages,
+                     boards_s, actions, boards_s2, done, B, lr, gamma, status);
+  return launch_status();
+}
+int q2048_nts_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, uint32_t stages, int64_t B, int64_t steps,
+                            double eps, double lr, double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0,
+                            int64_t* stats_i, double* stats_f, uint32_t* status, void* stream) {
+  if (int e = check_nts_fused(boards, aux, weights, stages, B, steps, eps, lr, gamma, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_nts_fused_rollout, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream,
+                     boards, aux, weights, stages, B, (int)steps, eps, lr, gamma, seed, env_id0, ctr0, stats_i,
+                     stats_f, status);
+  return launch_status();
+}
+int q2048_nts_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, uint32_t stages, int64_t B, int64_t steps,
+                           double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
+                           double* stats_f, uint32_t* status, void* stream) {
+  if (int e = check_nts_play(boards, aux, weights, stages, B, steps, eps, flags, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+#define Q2048_LAUNCH_NTS_PLAY(E)                                                                                   \
+  case E:                                                                                                          \
+    hipLaunchKernelGGL((k_nts_play_rollout<E>), dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, boards,   \
+                       aux, weights, stages, B, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);           \
+    break;
+  switch (env_bits(flags) & 3) { Q2048_LAUNCH_NTS_PLAY(0) Q2048_LAUNCH_NTS_PLAY(1) Q2048_LAUNCH_NTS_PLAY(2) Q2048_LAUNCH_NTS_PLAY(3) }
+#undef Q2048_LAUNCH_NTS_PLAY
+  return launch_status();
+}
+int q2048_nts_search_lookup_depth(const float* weights, uint32_t stages, const uint8_t* boards, int64_t B, int depth,
+                                  float* q_out, uint8_t* legal_out, void* stream) {
+  if (int e = check_nts_search_lookup_depth(weights, stages, boards, B, depth, q_out, legal_out)) return e;
+  if (B == 0) return Q2048_OK;
+  const int64_t cap = depth == 1 ? kSearchMaxBoards : kSearch2MaxBoards;   // boards per launch
+  for (int64_t first = 0; first < B; first += cap) {
+    const int64_t n = B - first < cap ? B - first : cap;
+    if (depth == 1)
+      hipLaunchKernelGGL(k_nts_search_lookup, dim3((unsigned)((n + kSearchBoards - 1) / kSearchBoards)), dim3(kBlock), 0,
+                         (hipStream_t)stream, weights, stages, boards, first, first + n, q_out, legal_out);
+    else
+      hipLaunchKernelGGL(k_nts_search2_lookup, dim3((unsigned)n), dim3(kBlock), 0, (hipStream_t)stream, weights, stages,
+                         boards, first, first + n, q_out, legal_out);
+  }
+  return launch_status();
+}
+int q2048_nts_search_play_rollout_depth(uint8_t* boards, q2048_aux* aux, const float* weights, uint32_t stages, int64_t B,
+                                        int64_t steps, int depth, double eps, uint64_t seed, uint64_t env_id0,
+                                        uint32_t ctr0, uint32_t flags, int64_t* stats_i, double* stats_f,
+                                        uint32_t* status, void* stream) {
+  if (int e = check_nts_search_play_depth(boards, aux, weights, stages, B, steps, depth, eps, flags, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+#define Q2048_LAUNCH_NTS_SEARCH_PLAY(E)                                                                            \
+  case E:                                                                                                          \
+    if (depth == 1)                                                                                                \
+      hipLaunchKernelGGL((k_nts_search_play_rollout<E>), grid, dim3(kBlock), 0, (hipStream_t)stream, boards, aux,  \
+                         weights, stages, first, first + n, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f); \
+    else                                                                                                           \
+      hipLaunchKernelGGL((k_nts_search2_play_rollout<E>), grid, dim3(kBlock), 0, (hipStream_t)stream, boards, aux, \
+                         weights, stages, first, first + n, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f); \
+    break;
+  const int64_t cap = depth == 1 ? kSearchMaxBoards : kSearch2MaxBoards;   // boards per launch
+  for (int64_t first = 0; first < B; first += cap) {
+    const int64_t n = B - first < cap ? B - first : cap;
+    const dim3 grid((unsigned)(depth == 1 ? (n + kSearchBoards - 1) / kSearchBoards : n));
+    switch (env_bits(flags) & 3) {
+      Q2048_LAUNCH_NTS_SEARCH_PLAY(0) Q2048_LAUNCH_NTS_SEARCH_PLAY(1) Q2048_LAUNCH_NTS_SEARCH_PLAY(2)
+      Q2048_LAUNCH_NTS_SEARCH_PLAY(3)
+    }
+  }
+#undef Q2048_LAUNCH_NTS_SEARCH_PLAY
+  return launch_status();
+}
+int q2048_nts_promote(float* weights, uint32_t stages, int from, int to, int64_t* count_out, void* stream) {
+  if (int e = check_nts_promote(weights, stages, from, to)) return e;
+  if (count_out != nullptr && hipMemsetAsync(count_out, 0, sizeof(int64_t), (hipStream_t)stream) != hipSuccess)
+    return Q2048_ERR_LAUNCH;
+  hipLaunchKernelGGL(k_nts_promote, dim3(kPromoteBlocks), dim3(kBlock), 0, (hipStream_t)stream,
+                     weights + (size_t)to * kNtsStageFloats, weights + (size_t)from * kNtsStageFloats,
+                     reinterpret_cast<u64*>(count_out));
+  return launch_status();
 }
 
 int q2048_table_import(q2048_slot* table, int cap_log2, const uint64_t* keys, const float* q,

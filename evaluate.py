@@ -8,7 +8,8 @@ weights, or -- "kind": "line_tuple" -- the line-tuple learner's, or -- "kind": "
 learner's values, or -- "kind": "ntuple6_afterstate" -- the 6-tuple afterstate network: the file says which, and the
 JSON line then carries "agent": "row-tuple" / "line-tuple" / "afterstate" / "ntuple"; `--fused --search` plays the two
 afterstate kinds with a one-level expectimax over the spawn, and the line carries "search": 1; `--search-depth 2` makes
-it two levels and "search": 2; the greedy players carry "search": 0), plays `--episodes` games per env
+it two levels and "search": 2; the greedy players carry "search": 0; a network file with "stage_tiles" is played as
+the multi-stage network it is, and the line of every network file carries "stage_tiles", [] for a plain one), plays `--episodes` games per env
 with the stored values -- rows are read, nothing is created or written -- and prints one JSON line: games, mean
 score / return, max-tile histogram.  Two policies:
 
@@ -143,8 +144,10 @@ def main_row_tuple(args, torch, pkg, sd):
     cls, name = {"row_tuple": (pkg.BatchedRowTupleAgent, "row-tuple"), "line_tuple": (pkg.BatchedLineTupleAgent, "line-tuple"),
                  "line_afterstate": (pkg.BatchedAfterstateAgent, "afterstate"),
                  "ntuple6_afterstate": (pkg.BatchedNTupleAgent, "ntuple")}[kind]
+    stage_tiles = tuple(sd.get("stage_tiles") or ())              # a staged network: the file says so
+    extra = {"stage_tiles": stage_tiles} if stage_tiles else {}
     agent = cls(1, learning_rate=sd["lr"], discount_factor=sd["gamma"], exploration_rate=args.epsilon, seed=args.seed,
-                device=args.device)
+                device=args.device, **extra)
     agent.load_state_dict(sd)
     agent.seed, agent.ctr, agent.epsilon = args.seed, 0, args.epsilon     # evaluation has its own draws
     agent.stats(reset=True)
@@ -174,6 +177,8 @@ def main_row_tuple(args, torch, pkg, sd):
            "search": args.search_depth, "seconds": round(time.time() - t0, 3)}
     if args.fused:
         out["fused"] = True
+    if kind == "ntuple6_afterstate":
+        out["stage_tiles"] = list(stage_tiles)
     print(json.dumps(out))
     return st
 

@@ -1016,6 +1016,57 @@ int q2048_nt_search_play_rollout_depth(uint8_t *boards, q2048_aux *aux, const fl
                                        uint32_t flags, int64_t *stats_i, double *stats_f, uint32_t *status,
                                        void *stream);
 
+/* ---- the staged network: a weight table per largest-tile stage (q2048_nts_*) --------------------------------------
+ * The 6-tuple network above with one set of weights per stage of the game: weights = float32 [S][4][16777216],
+ * 1 <= S <= 8 (256 MiB per stage).  Arrived without an ABI bump, detected by its symbols.
+ *   stages    the thresholds as nibbles: nibble i is t_{i+1}, a tile exponent in 1..15 (the tile 2^t).  The thresholds
+ *             ascend strictly, the nonzero nibbles are contiguous from nibble 0, the top nibble is 0 (at most seven
+ *             thresholds); S = 1 + the number of nonzero nibbles.  stages == 0 is the plain network: every q2048_nts_*
+ *             function then gives what its q2048_nt_* counterpart gives, byte for byte.  Any other word is
+ *             Q2048_ERR_RANGE, checked before every other argument.
+ *   stage(x)  the number of thresholds t_i with maxnib(x) >= t_i, maxnib(x) = the largest nibble of the packed key of
+ *             x (a cell >= 16 aliases by its low nibble, as in the indices).
+ *   v(x)      the network's v over the 32 entries of x taken from table stage(x).  In the evaluation of a state every
+ *             candidate afterstate uses its OWN stage: a merge that creates a threshold tile puts that candidate in the
+ *             next table while its siblings stay below.  q_a, best, the choice, live and target are the afterstate
+ *             family's.
+ *   TD step   q2048_nt_update's on table stage(c_act): the 32 entries are gathered from that table and written back as
+ *             gathered + d; the target is the best of the staged evaluation of the next state.  A weight that a
+ *             symmetric board reads several times moves once, as in the plain network.
+ * The nine functions have the argument lists of their q2048_nt_* counterparts with `stages` directly after `weights`,
+ * their checks in their order after the spec, their draws, flags, statistics and episode handling.  depth is 1 or 2.
+ *   q2048_nts_promote   BULK PROMOTION from stage `from` to stage `to`, on every (p, idx): if the bit pattern of
+ *             V[to][p][idx] is 0x00000000 and that of V[from][p][idx] is not, V[to][p][idx] takes the bits of
+ *             V[from][p][idx] (a NaN included).  -0.0f counts as written and is never overwritten.  count_out: device
+ *             int64, may be NULL; receives the number of entries copied.  Errors, in this order: a malformed spec ->
+ *             Q2048_ERR_RANGE; weights NULL -> Q2048_ERR_NULL; not 16-byte aligned -> Q2048_ERR_ALIGN; from == to, or
+ *             either outside 0..S-1 -> Q2048_ERR_RANGE.  Stream-ordered; nothing else may touch the two tables while
+ *             it runs.  This is not the literature's promote-on-first-access: a weight copied early does not follow
+ *             what its source learns later, and the evaluation carries no sentinel test and no second load.
+ * A refused call writes nothing; B == 0 or steps == 0 is Q2048_OK. */
+int q2048_nts_value(const float *weights, uint32_t stages, const uint8_t *boards, int64_t B, float *v_out,
+                    void *stream);
+int q2048_nts_lookup(const float *weights, uint32_t stages, const uint8_t *boards, int64_t B, float *q_out,
+                     void *stream);
+int q2048_nts_choose(const float *weights, uint32_t stages, const uint8_t *boards, int64_t B, double eps,
+                     uint64_t seed, uint64_t env_id0, uint32_t ctr, uint8_t *actions, void *stream);
+int q2048_nts_update(float *weights, uint32_t stages, const uint8_t *boards_s, const uint8_t *actions,
+                     const uint8_t *boards_s2, const uint8_t *done, int64_t B, double lr, double gamma,
+                     uint32_t *status, void *stream);
+int q2048_nts_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weights, uint32_t stages, int64_t B,
+                            int64_t steps, double eps, double lr, double gamma, uint64_t seed, uint64_t env_id0,
+                            uint32_t ctr0, int64_t *stats_i, double *stats_f, uint32_t *status, void *stream);
+int q2048_nts_play_rollout(uint8_t *boards, q2048_aux *aux, const float *weights, uint32_t stages, int64_t B,
+                           int64_t steps, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
+                           int64_t *stats_i, double *stats_f, uint32_t *status, void *stream);
+int q2048_nts_search_lookup_depth(const float *weights, uint32_t stages, const uint8_t *boards, int64_t B, int depth,
+                                  float *q_out, uint8_t *legal_out, void *stream);
+int q2048_nts_search_play_rollout_depth(uint8_t *boards, q2048_aux *aux, const float *weights, uint32_t stages,
+                                        int64_t B, int64_t steps, int depth, double eps, uint64_t seed,
+                                        uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t *stats_i,
+                                        double *stats_f, uint32_t *status, void *stream);
+int q2048_nts_promote(float *weights, uint32_t stages, int from, int to, int64_t *count_out, void *stream);
+
 /* Inverse of q2048_table_export (resume / load a table trained elsewhere): inserts `rows`
  * (key, q[4]) pairs into the table, key_words as above.  A key already present has its row
  * overwritten in place (its slot and key words stay, the four values change); a row that finds no slot

@@ -98,6 +98,15 @@ def parse_args(argv=None):
                         "learns at --alpha / 32 * min(|E| / A, 1): at full rate while its errors agree in sign, ever "
                         "slower as they cancel.  --save keeps the accumulators; --resume of a plain file starts them at "
                         "zero, and a file that holds them needs this flag")
+    p.add_argument("--stage-tiles", default="", metavar="T1[,T2...]",
+                   help="--agent ntuple only: a MULTI-STAGE network (q2048_nts_*), one table of weights per stage of the "
+                        "game.  Tile values, powers of two, ascending (e.g. 2048 or 2048,8192): a board reads the table of "
+                        "the stage its largest tile has reached, 256 MiB per stage.  --save records the tiles; --resume of "
+                        "a plain ntuple file splits it (every stage starts as the file); a file with other tiles is "
+                        "refused.  Not combined with --coherence")
+    p.add_argument("--promote-every", type=int, default=None, metavar="N",
+                   help="with --stage-tiles: every N epochs, copy what each stage has learned into the entries of the next "
+                        "stage that are still zero (agent.promote()).  Default 1; 0 = never")
     p.add_argument("--log", default="debug_log.csv", help="CSV log path (Agent/main.py:71)")
     p.add_argument("--report-every", type=int, default=10, help="launches between CSV rows (batched)")
     p.add_argument("--max-steps", type=int, default=0, help="stop after this many env steps per env (0 = off)")
@@ -251,7 +260,8 @@ def train_batched(args, pkg):
                                            args.epsilon_min, dev, args.seed, shard.env_id0)
     elif args.agent == "ntuple":
         agent = pkg.BatchedNTupleAgent(args.episodes, 4, args.alpha, args.gamma, args.epsilon,
-                                       args.epsilon_min, dev, args.seed, shard.env_id0, coherence=args.coherence)
+                                       args.epsilon_min, dev, args.seed, shard.env_id0, coherence=args.coherence,
+                                       stage_tiles=args.stage_tiles)
     else:
         agent = pkg.BatchedQLearningAgent(args.episodes, 4, args.alpha, args.gamma, args.epsilon,
                                           args.epsilon_min, cap, dev, args.seed, shard.env_id0,
@@ -271,6 +281,9 @@ def train_batched(args, pkg):
             if args.coherence and "coherence" not in sd and rank == 0:
                 print(f"{args.resume} holds no temporal-coherence accumulators: the weights continue, the accumulators "
                       "start at zero (every rate restarts at 1)", flush=True)
+            if args.stage_tiles and not sd.get("stage_tiles") and rank == 0:
+                print(f"{args.resume} holds a plain network: every one of the {len(args.stage_tiles) + 1} stages starts "
+                      "as the file (stage 0 loaded, the later ones promoted from it)", flush=True)
         if args.fold:
             _fold_into(pkg, agent, sd, args, dev)
         elif args.unfold:
@@ -317,6 +330,7 @@ def train_batched(args, pkg):
     stop_epoch = min(args.episodes, args.stop_epoch) if args.stop_epoch else args.episodes
     target = stop_epoch * shard.total_envs
     best_tile, grown, reports, said_frozen = 0, 0, 0, False
+    promoted = epoch0 // args.promote_every if args.stage_tiles and args.promote_every else 0
     evaluator = None
     if args.eval_every > 0:
         evaluator = _Evaluator(args, pkg, agent, dev, rank, world, epoch)
@@ -343,6 +357,11 @@ def train_batched(args, pkg):
         while epoch < total_eps // shard.total_envs and epoch < args.episodes:
             agent.decay_exploration(epoch)                # Agent/main.py:109, once per epoch
             epoch += 1
+        if args.stage_tiles and args.promote_every and epoch // args.promote_every > promoted:
+            promoted = epoch // args.promote_every                # once per --promote-every epochs reached
+            counts = agent.promote()
+            if rank == 0:
+                print(f"epoch {epoch}: promoted {counts} entries into stages 1..{len(counts)}", flush=True)
         agent.train_progress = {"epoch": epoch}
         if evaluator is not None:
             evaluator.maybe(epoch, st["steps"])
@@ -542,6 +561,26 @@ def main(argv=None):
         if args.num_envs == 1 and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
             raise SystemExit("--symmetric needs the batched mode (--num-envs > 1): the one-state loop learns through "
                              "choose_action / update_q_value, which do not take the flag")
+    try:
+        args.stage_tiles = tuple(int(t) for t in args.stage_tiles.split(",") if t.strip())
+    except ValueError:
+        raise SystemExit(f"--stage-tiles takes tile values separated by commas, not {args.stage_tiles!r}")
+    if args.stage_tiles:
+        if args.agent != "ntuple":
+            raise SystemExit(f"--stage-tiles applies to --agent ntuple (the 6-tuple afterstate network), not to --agent {args.agent}")
+        if args.coherence:
+            raise SystemExit("--coherence is not combined with --stage-tiles: the temporal-coherence step knows one table")
+        if args.num_envs <= 1:
+            raise SystemExit("--stage-tiles needs the batched mode (--num-envs > 1)")
+        if any(t < 2 or t > 32768 or t & (t - 1) for t in args.stage_tiles) or \
+                any(x >= y for x, y in zip(args.stage_tiles, args.stage_tiles[1:])) or len(args.stage_tiles) > 7:
+            raise SystemExit(f"--stage-tiles: at most seven powers of two from 2 to 32768, ascending, not {list(args.stage_tiles)}")
+        if args.promote_every is None:
+            args.promote_every = 1
+        if args.promote_every < 0:
+            raise SystemExit("--promote-every counts epochs: 0 (never) or more")
+    elif args.promote_every is not None:
+        raise SystemExit("--promote-every applies with --stage-tiles")
     if args.coherence:
         if args.agent != "ntuple":
             raise SystemExit(f"--coherence applies to --agent ntuple (the 6-tuple afterstate network), not to --agent {args.agent}")
