@@ -308,6 +308,12 @@ _SIGNATURES = {
                                                       C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.c_void_p]),
     "q2048_nts_promote": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # carousel shaping: q2048_nts_fused_rollout with pool, counts, fresh and P after `stages`, and the commit
+    "q2048_car_fused_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double,
+                                          C.c_double, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "q2048_car_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64, C.c_int64, C.c_void_p]),
     "q2048_table_import": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_int, C.c_void_p, C.c_void_p]),
     "q2048_table_export": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,

@@ -1907,15 +1907,31 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
     `stage_tiles=()` is the plain agent on the plain entry points.  `promote()` copies what an earlier stage has
     learned into the entries of the next one that are still zero.  The checkpoint keeps its kind and carries
     "stage_tiles"; a staged agent loads a plain file into stage 0 and promotes it through every stage, a file with
-    other tiles is refused, and a plain agent refuses a staged file.  Not combined with `coherence=True`."""
+    other tiles is refused, and a plain agent refuses a staged file.  Not combined with `coherence=True`.
+
+    `carousel=P` (with `stage_tiles` only; 0 = off, and the agent is then the agent above) adds CAROUSEL SHAPING
+    (q2048_car_*): `fused_rollout` starts episodes in turn at the beginning of every stage -- episode number e of a lane
+    starts in stage e % S, from a board drawn from the agent's pool of boards on which earlier games entered that stage,
+    or from an empty board where the pool has none -- and commits the boards its games recorded to the pool afterwards,
+    on the same stream.  The agent owns `carousel_pool`, uint8 [S, P, 32], and `carousel_counts`, int64 [S] (records ever
+    committed per stage), and allocates `carousel_fresh`, uint8 [S, B, 32], for the env's B at the first
+    `fused_rollout`.  An "episode" of the statistics may then be a spliced game.  The four-call API, the players, the
+    search and `promote()` are untouched.  The checkpoint keeps its kind and carries "carousel": {"pool", "counts"};
+    a carousel agent loads a file without it (an empty pool), a plain staged agent ignores it, another P or S is
+    refused."""
 
     _FAMILY, _SHAPE, _KIND, _WHAT = "nt", (4, 1 << 24), "ntuple6_afterstate", "a 6-tuple afterstate network"
     _ACC_SHAPE = (4, 1 << 24, 2)
 
     def __init__(self, total_epochs, action_space=4, learning_rate=0.1, discount_factor=0.9,
                  exploration_rate=1.0, exploration_min=0.01, device="cuda", seed: int = 0,
-                 env_id0: int = 0, coherence: bool = False, stage_tiles=()):
+                 env_id0: int = 0, coherence: bool = False, stage_tiles=(), carousel: int = 0):
         self.stage_tiles = self._check_stage_tiles(stage_tiles)
+        if isinstance(carousel, bool) or not isinstance(carousel, int) or carousel < 0 or carousel > 1 << 32:
+            raise ValueError(f"carousel must be a number of records per stage from 0 (off) to 2^32, not {carousel!r}")
+        if carousel and not self.stage_tiles:
+            raise ValueError("carousel needs stage_tiles: the pool holds the boards on which games entered a stage")
+        self.carousel = carousel
         if self.stage_tiles and coherence:
             raise ValueError("coherence=True is not combined with stage_tiles: q2048_nt_tc_* knows one table")
         # the stage spec of q2048_nts_*: nibble i = log2 of the (i + 1)-th threshold tile; 0 = the plain network
@@ -1925,6 +1941,11 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
         super().__init__(total_epochs, action_space, learning_rate, discount_factor, exploration_rate,
                          exploration_min, device, seed, env_id0)
         self.coherence = torch.zeros(self._ACC_SHAPE, dtype=torch.float32, device=self.device) if coherence else None
+        self.carousel_pool = self.carousel_counts = self.carousel_fresh = None
+        if self.carousel:
+            S = len(self.stage_tiles) + 1
+            self.carousel_pool = torch.zeros((S, self.carousel, 32), dtype=torch.uint8, device=self.device)
+            self.carousel_counts = torch.zeros(S, dtype=torch.int64, device=self.device)
 
     @staticmethod
     def _check_stage_tiles(stage_tiles) -> tuple:
@@ -2045,6 +2066,22 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
             raise ValueError("env profiles are supported by the hash-table agent only")
         if (env.seed, env.env_id0, env.ctr) != (self.seed, self.env_id0, self.ctr):
             raise ValueError("env and agent must share seed, env_id0 and step counter")
+        if self.carousel:
+            B, S = env.num_envs, len(self.stage_tiles) + 1
+            if self.carousel_fresh is None or self.carousel_fresh.shape[1] != B:
+                self.carousel_fresh = torch.zeros((S, B, 32), dtype=torch.uint8, device=self.device)
+            N.check(self._L.q2048_car_fused_rollout(
+                _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), self._stages, _ptr(self.carousel_pool),
+                _ptr(self.carousel_counts), _ptr(self.carousel_fresh), self.carousel, B, int(steps),
+                float(self.epsilon), float(self.lr), float(self.gamma), self.seed, self.env_id0,
+                self.ctr & 0xFFFFFFFF, _ptr(self.stats_i), _ptr(self.stats_f), _ptr(self.status),
+                _stream(self.device)), "car_fused_rollout")
+            N.check(self._L.q2048_car_commit(_ptr(self.carousel_pool), _ptr(self.carousel_counts),
+                                             _ptr(self.carousel_fresh), self._stages, self.carousel, B,
+                                             _stream(self.device)), "car_commit")
+            env.ctr += int(steps)
+            self.ctr += int(steps)
+            return None
         if self.stage_tiles:
             N.check(self._nts("fused_rollout")(
                 _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), self._stages, env.num_envs, int(steps),
@@ -2061,6 +2098,14 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
             _stream(self.device)), "nt_tc_fused_rollout")
         env.ctr += int(steps)
         self.ctr += int(steps)
+
+    def carousel_summary(self) -> dict:
+        """{"counts": records ever committed per stage, "valid": records a restart can draw per stage (min(count, P))};
+        stage 0 has none by construction.  Synchronises."""
+        if not self.carousel:
+            raise ValueError("this agent was built without carousel=P")
+        counts = [int(c) for c in self.carousel_counts.cpu().tolist()]
+        return {"counts": counts, "valid": [min(c, self.carousel) for c in counts]}
 
     def coherence_summary(self) -> dict:
         """{"visited": the share of pairs with A > 0, "mean_rate": the mean of min(|E| / A, 1) over them (1.0 where
@@ -2082,12 +2127,37 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
             sd["coherence"] = self.coherence.to("cpu", copy=True)
         if self.stage_tiles:
             sd["stage_tiles"] = list(self.stage_tiles)     # weights float32 [S, 4, 16777216]
+        if self.carousel:
+            sd["carousel"] = {"pool": self.carousel_pool.to("cpu", copy=True),
+                              "counts": self.carousel_counts.to("cpu", copy=True)}
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
         """Everything -- the pairs included, where this agent takes them -- is validated before anything of this agent
         is written.  A plain agent ignores a file's pairs; a coherence agent without pairs in the file zeroes its own."""
         file_tiles = tuple(sd.get("stage_tiles") or ())
+        car = sd.get("carousel") if self.carousel else None      # a plain staged agent ignores a file's pool
+        if car is not None:
+            want = tuple(self.carousel_pool.shape)
+            pool, counts = (car.get("pool"), car.get("counts")) if isinstance(car, dict) else (None, None)
+            if not isinstance(pool, torch.Tensor) or pool.dtype != torch.uint8 or tuple(pool.shape) != want:
+                raise ValueError(f"carousel pool must be a uint8 tensor of shape {want} (stages, records per stage, 32), "
+                                 f"got {getattr(pool, 'dtype', type(pool).__name__)} {tuple(getattr(pool, 'shape', ()))}")
+            if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or tuple(counts.shape) != want[:1] \
+                    or bool((counts < 0).any()):
+                raise ValueError(f"carousel counts must be a non-negative int64 tensor of shape {want[:1]}")
+        self._load_weights_and_pairs(sd, file_tiles)             # validates the rest, then writes
+        if self.carousel:
+            if car is None:
+                self.carousel_pool.zero_()
+                self.carousel_counts.zero_()
+            else:
+                self.carousel_pool.copy_(car["pool"])
+                self.carousel_counts.copy_(car["counts"])
+            if self.carousel_fresh is not None:
+                self.carousel_fresh.zero_()
+
+    def _load_weights_and_pairs(self, sd: dict, file_tiles: tuple) -> None:
         if sd.get("kind") == self._KIND and file_tiles != self.stage_tiles:
             if not self.stage_tiles:
                 raise ValueError(f"this checkpoint holds a staged network (stage_tiles {list(file_tiles)}): a plain "

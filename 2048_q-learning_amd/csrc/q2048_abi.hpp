@@ -253,6 +253,31 @@ static inline int check_nts_search_play_depth(const void* boards, const void* au
   if (int e = check_nts_spec(stages)) return e;
   return check_search_play_depth(boards, aux, weights, B, steps, depth, eps, flags, status);
 }
+// Carousel shaping (q2048_car_*): the spec, NULL, alignment (16 bytes; counts 8), then the sizes and the scalars of
+// q2048_nts_fused_rollout.  A ring above 2^32 records is a size error: the slot of a restart is drawn from 32 bits.
+static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+static inline int check_car_fused(const void* boards, const void* aux, const void* weights, uint32_t stages,
+                                  const void* pool, const void* counts, const void* fresh, int64_t P, int64_t B,
+                                  int64_t steps, double eps, double lr, double gamma, const void* status) {
+  if (int e = check_nts_spec(stages)) return e;
+  if (!boards || !aux || !weights || !pool || !counts || !fresh || !status) return Q2048_ERR_NULL;
+  if (!aligned16(boards) || !aligned16(aux) || !aligned16(weights) || !aligned16(pool) || !aligned16(fresh) ||
+      !aligned8(counts))
+    return Q2048_ERR_ALIGN;
+  if (P < 1 || P > kCarMaxRing) return Q2048_ERR_SIZE;
+  if (int e = check_batch(B, 4)) return e;
+  if (steps < 0 || steps > (1 << 30)) return Q2048_ERR_SIZE;
+  if (!(eps >= 0.0 && eps <= 1.0) || !(lr == lr) || !(gamma == gamma)) return Q2048_ERR_RANGE;
+  return Q2048_OK;
+}
+static inline int check_car_commit(const void* pool, const void* counts, const void* fresh, uint32_t stages, int64_t P,
+                                   int64_t B) {
+  if (int e = check_nts_spec(stages)) return e;
+  if (!pool || !counts || !fresh) return Q2048_ERR_NULL;
+  if (!aligned16(pool) || !aligned16(fresh) || !aligned8(counts)) return Q2048_ERR_ALIGN;
+  if (P < 1 || P > kCarMaxRing) return Q2048_ERR_SIZE;
+  return check_batch(B, 4);
+}
 // q2048_nts_promote: the spec, NULL, alignment, then the two stage numbers (from == to, or either >= S)
 static inline int check_nts_promote(const void* weights, uint32_t stages, int from, int to) {
   if (int e = check_nts_spec(stages)) return e;

@@ -1263,6 +1263,54 @@ Q_HD void nts_td(const Board& x, uint32_t stages, const NtEval& en, bool done, d
 // PROMOTION (q2048_nts_promote), on every (p, idx): if the bit pattern of V[to][p][idx] is 0x00000000 and that of
 // V[from][p][idx] is not, V[to][p][idx] takes the BITS of V[from][p][idx] (a NaN included); -0.0f counts as written.
 Q_HD bool nts_promotes(uint32_t to_bits, uint32_t from_bits) { return to_bits == 0u && from_bits != 0u; }
+// CAROUSEL SHAPING (q2048_car_*): training episodes start in turn at the beginning of every stage, from boards on
+// which earlier games entered that stage.  Three buffers in the caller's memory:
+//   pool   uint8 [S][P][32], 16-byte aligned: a ring of P >= 1 records per stage; row 0 is never read or written
+//   counts uint64 [S]: counts[k] = records ever committed to stage k; n_k = min(counts[k], P) are valid, slots 0..n_k-1
+//   fresh  uint8 [S][B][32], 16-byte aligned: one record per (stage, lane), written by the learner, consumed by the commit
+// A RECORD is 32 bytes: the board (0..15), aux.score (16..19), the bits of aux.ep_return (20..23), zero (24..31).  A
+// record whose 16 board bytes are zero is EMPTY; a board after a step holds a tile, so no real record is empty.
+// RECORDING, in fused step t of lane i: k0 = nts_stage of the state the step starts from, k1 = that of the state
+// env_step leaves (spawn included); if !done && k1 > k0, fresh[k1][i] takes the record of (b, a) as env_step left them.
+// The last crossing of a lane into a stage within a launch wins, a jump over a stage records at k1 only, a restart
+// records nothing.
+// RESTART, in place of begin_episode: episode += 1, d = draws(seed, id, episode, kStreamReset), k = episode % S; k == 0
+// or n_k == 0 is reset_board(b, a, d) -- begin_episode bit for bit -- otherwise the board, score and ep_return come from
+// pool[k][(d.x0 * n_k) >> 32].  A restart writes what reset_board writes and nothing else of the lane.
+// The pool and the counts are read-only during a launch and a lane writes only its own fresh[.][i]: at fixed weights
+// a launch's boards, aux and records are a pure function of its inputs at any B.
+// COMMIT, per stage k = 1..S-1: the lanes with a non-empty fresh[k][i] in ascending i, m of them, rank r among them;
+// the record of rank r goes to pool[k][(counts[k] + r) % P] if r + P >= m (of more than P records the last P land,
+// each in a slot of its own); then counts[k] += m and every consumed fresh[k][i] is zeroed whole.
+constexpr int kCarRecordBytes = 32;
+constexpr int64_t kCarMaxRing = (int64_t)1 << 32;      // P above this is Q2048_ERR_SIZE (the slot draw is 32 bits)
+struct CarRecord { Board b; Words4 tail; };            // the two 16-byte halves of a record
+static_assert(sizeof(CarRecord) == kCarRecordBytes, "a record is two 16-byte accesses");
+Q_HD CarRecord car_record(const Board& b, const Aux& a) {
+  return CarRecord{b, Words4{(uint32_t)a.score, f32_bits(a.ep_return), 0u, 0u}};
+}
+Q_HD bool car_empty(const Board& b) { return (b.r0 | b.r1 | b.r2 | b.r3) == 0u; }
+Q_HD bool car_records(uint32_t k0, uint32_t k1, bool done) { return !done && k1 > k0; }
+Q_HD uint64_t car_valid(uint64_t count, uint64_t P) { return count < P ? count : P; }
+Q_HD uint32_t car_pick(uint32_t x0, uint64_t n) { return (uint32_t)(((uint64_t)x0 * n) >> 32); }
+Q_HD bool car_lands(uint64_t r, uint64_t m, uint64_t P) { return r + P >= m; }
+Q_HD uint64_t car_slot(uint64_t count, uint64_t r, uint64_t P) { return (count % P + r % P) % P; }   // (count + r) % P without the wrap at 2^64
+// `valid(k)` gives n_k, `ld(k, j)` the record pool[k][j]; both are called in the restart-from-the-pool case only
+template <class Valid, class LdRec>
+Q_HD void car_restart(Board& b, Aux& a, uint64_t seed, uint64_t env_id, uint32_t S, Valid valid, LdRec ld) {
+  a.episode += 1u;
+  const Draws d = draws(seed, env_id, a.episode, kStreamReset);
+  const uint32_t k = a.episode % S;
+  const uint64_t n = k == 0u ? 0u : valid(k);
+  if (n == 0u) {
+    reset_board(b, a, d);
+    return;
+  }
+  const CarRecord rec = ld(k, car_pick(d.x0, n));
+  b = rec.b;
+  a.score = (int32_t)rec.tail.w0;
+  a.ep_return = bits_f32(rec.tail.w1);
+}
 
 // TEMPORAL-COHERENCE STEP SIZES for the network (q2048_nt_tc_*): beside V sits acc = float[4][2^24][2], acc[p][idx] =
 // {E, A}: the signed sum of the TD errors that weight has seen and the sum of their magnitudes.  Its own rate is

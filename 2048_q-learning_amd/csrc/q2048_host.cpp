@@ -2376,6 +2376,98 @@ int q2048_nts_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, uin
   stats_merge(parts, used, stats_i, stats_f);
   return Q2048_OK;
 }
+// ---- carousel shaping (q2048_car_*; the contract is "CAROUSEL SHAPING" in q2048_core.hpp) ----
+// q2048_nts_fused_rollout with the recording test after env_step and car_restart for begin_episode
+int q2048_car_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, uint32_t stages, const uint8_t* pool,
+                            const uint64_t* counts, uint8_t* fresh, int64_t P, int64_t B, int64_t steps, double eps,
+                            double lr, double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i,
+                            double* stats_f, uint32_t* status, void*) {
+  if (int e = check_car_fused(boards, aux, weights, stages, pool, counts, fresh, P, B, steps, eps, lr, gamma, status))
+    return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  const uint64_t eps_t = eps_threshold(eps);
+  const uint32_t S = nts_count(stages);
+  const int T = threads_for(B);
+  std::vector<Stats> parts((size_t)T);
+  Stats* sp = parts.data();
+  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+    Stats& st = sp[tid];
+    const auto valid = [=](uint32_t k) { return car_valid(counts[k], (uint64_t)P); };
+    const auto ld_rec = [=](uint32_t k, uint32_t j) {
+      CarRecord rec;
+      std::memcpy(&rec, pool + ((size_t)k * (size_t)P + j) * kCarRecordBytes, kCarRecordBytes);
+      return rec;
+    };
+    for (int64_t i = lo; i < hi; ++i) {
+      const uint64_t id = env_id0 + (uint64_t)i;
+      Board b;
+      load_board(boards, i, b);
+      Aux a = ld_aux(aux, i);
+      double reward_sum = 0.0;
+      for (int64_t t = 0; t < steps; ++t) {
+        const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+        const NtEval ev = nts_eval(b, stages, NtsLdOf{weights});
+        bool explored;
+        const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+        Board c = b;                    // the afterstate of the move played
+        uint32_t score;
+        const bool legal = move(c, act, score);
+        const uint32_t k0 = nts_stage(b, stages);
+        const StepOut o = env_step(b, a, act, x.x2, x.x3);
+        const uint32_t k1 = nts_stage(b, stages);
+        if (car_records(k0, k1, o.done != 0)) {
+          const CarRecord rec = car_record(b, a);
+          std::memcpy(fresh + ((size_t)k1 * (size_t)B + (size_t)i) * kCarRecordBytes, &rec, kCarRecordBytes);
+        }
+        const NtEval en = nts_eval(b, stages, NtsLdOf{weights});
+        if (legal) nts_td(c, stages, en, o.done != 0, lr, gamma, NtsLdOf{weights}, NtsStOf{weights});
+        st.i[Q2048_ST_VALID] += o.valid != 0;
+        st.i[Q2048_ST_EXPLORE] += explored;
+        reward_sum += (double)o.reward;
+        if (o.done) {
+          st.i[Q2048_ST_EPISODES] += 1;
+          st.episode(a, o.max_log2);
+          car_restart(b, a, seed, id, S, valid, ld_rec);
+        }
+      }
+      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
+      st.f[Q2048_SF_REWARD] += reward_sum;
+      store_board(boards, i, b);
+      st_aux(aux, i, a);
+    }
+  });
+  stats_merge(parts, used, stats_i, stats_f);
+  return Q2048_OK;
+}
+// the commit, a stage at a time: count the non-empty records, then place them in ascending lane order
+int q2048_car_commit(uint8_t* pool, uint64_t* counts, uint8_t* fresh, uint32_t stages, int64_t P, int64_t B, void*) {
+  if (int e = check_car_commit(pool, counts, fresh, stages, P, B)) return e;
+  if (B == 0) return Q2048_OK;
+  const uint32_t S = nts_count(stages);
+  static const uint8_t zero[kCarRecordBytes] = {};
+  for (uint32_t k = 1; k < S; ++k) {
+    uint8_t* rows = fresh + (size_t)k * (size_t)B * kCarRecordBytes;
+    const auto empty = [=](int64_t i) {
+      Board b;
+      std::memcpy(&b, rows + (size_t)i * kCarRecordBytes, sizeof b);
+      return car_empty(b);
+    };
+    uint64_t m = 0;
+    for (int64_t i = 0; i < B; ++i) m += !empty(i);
+    uint64_t r = 0;
+    for (int64_t i = 0; i < B; ++i) {
+      if (empty(i)) continue;
+      uint8_t* rec = rows + (size_t)i * kCarRecordBytes;
+      if (car_lands(r, m, (uint64_t)P))
+        std::memcpy(pool + ((size_t)k * (size_t)P + car_slot(counts[k], r, (uint64_t)P)) * kCarRecordBytes, rec,
+                    kCarRecordBytes);
+      std::memcpy(rec, zero, kCarRecordBytes);
+      ++r;
+    }
+    counts[k] += m;
+  }
+  return Q2048_OK;
+}
 // the players: one loop for the greedy row (DEPTH 0) and the searched rows (DEPTH 1, 2); the callers have checked
 extern "C++" {
 template <int DEPTH>

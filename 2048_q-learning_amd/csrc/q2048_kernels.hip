@@ -3111,6 +3111,145 @@ __global__ __launch_bounds__(kBlock) void k_nts_fused_rollout(
   stats_flush(bs, stats_i, stats_f);
 }
 
+// Carousel shaping (q2048_car_*; the contract is "CAROUSEL SHAPING" in q2048_core.hpp).  k_nts_fused_rollout with
+// two changes: the recording test after env_step -- one nts_stage on each side of the step, k0 the only value it
+// keeps across the step, and two 16-byte stores on a crossing -- and car_restart in the o.done branch, whose count
+// and two 16-byte loads are issued by the lanes that ended a game only.  nts_eval's candidate loop is untouched.
+struct CarValid {
+  const u64* counts;
+  u64 P;
+  __device__ __forceinline__ u64 operator()(uint32_t k) const { return car_valid(counts[k], P); }
+};
+struct CarLdRec {
+  const uint4* pool;
+  u64 P;
+  __device__ __forceinline__ CarRecord operator()(uint32_t k, uint32_t j) const {
+    const uint4* rec = pool + ((size_t)k * (size_t)P + j) * 2;
+    const uint4 v = rec[0], t = rec[1];
+    return CarRecord{Board{v.x, v.y, v.z, v.w}, Words4{t.x, t.y, t.z, t.w}};
+  }
+};
+
+__global__ __launch_bounds__(kBlock) void k_car_fused_rollout(
+    uint8_t* boards, q2048_aux* aux, float* w, uint32_t stages, const uint8_t* pool, const u64* counts, uint8_t* fresh,
+    int64_t P, int64_t B, int steps, double eps, double lr, double gamma, uint64_t seed, uint64_t env_id0,
+    uint32_t ctr0, int64_t* stats_i, double* stats_f, uint32_t* /*status: as on k_nt_fused_rollout*/) {
+  __shared__ BlockStats bs;
+  stats_clear(bs);
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < B) {
+    Stage<4> st;
+    const uint64_t id = env_id0 + (uint64_t)i;
+    const uint32_t S = nts_count(stages);
+    Board b = load_board(boards, i, B, st);
+    Aux a = ld_aux(aux, i);
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
+    double reward_sum = 0.0;
+    const uint64_t eps_t = eps_threshold(eps);
+    for (int t = 0; t < steps; ++t) {
+      const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+      const NtEval ev = nts_eval(b, stages, NtsLdOf<true>{w});
+      bool explored;
+      const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+      Board c = b;                    // the afterstate of the move played
+      uint32_t score;
+      const bool legal = move(c, act, score);
+      const uint32_t k0 = nts_stage(b, stages);
+      const StepOut o = env_step(b, a, act, x.x2, x.x3);
+      const uint32_t k1 = nts_stage(b, stages);
+      if (car_records(k0, k1, o.done != 0)) {
+        const CarRecord rec = car_record(b, a);
+        uint4* dst = reinterpret_cast<uint4*>(fresh) + ((size_t)k1 * (size_t)B + (size_t)i) * 2;   // k1 < S, i < B
+        dst[0] = make_uint4(rec.b.r0, rec.b.r1, rec.b.r2, rec.b.r3);
+        dst[1] = make_uint4(rec.tail.w0, rec.tail.w1, rec.tail.w2, rec.tail.w3);
+      }
+      const NtEval en = nts_eval(b, stages, NtsLdOf<true>{w});
+      if (legal) nts_td(c, stages, en, o.done != 0, lr, gamma, NtsLdOf<true>{w}, NtsStOf{w});
+      n_valid += wave_count(o.valid != 0);
+      n_explore += wave_count(explored);
+      n_done += wave_count(o.done != 0);
+      reward_sum += (double)o.reward;
+      if (o.done) {
+        episode_stats(bs, a, o.max_log2);
+        car_restart(b, a, seed, id, S, CarValid{counts, (u64)P}, CarLdRec{reinterpret_cast<const uint4*>(pool), (u64)P});
+      }
+    }
+    store_board(boards, i, B, b, st);
+    st_aux(aux, i, a);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+    const uint32_t n_active = wave_count(true);
+    if (wave_leader()) {
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  stats_flush(bs, stats_i, stats_f);
+}
+
+// The commit: one block of 1024 threads per stage 1..S-1, two passes over the B lanes in tiles of 1024.  Pass one
+// counts the non-empty records, m.  Pass two places them: a wave ballots its lanes and counts them, the 16 counts
+// meet in LDS, a lane's rank is the running offset of the earlier tiles + the waves before its own + the set bits
+// below it.  A landing record goes to a slot of its own (car_lands, car_slot), so there are no atomics on the pool;
+// 16-byte loads and stores only.  Every lane index is < B and every slot < P.
+constexpr int kCarBlock = 1024, kCarWaves = kCarBlock / 64;
+__global__ __launch_bounds__(kCarBlock) void k_car_commit(uint8_t* pool, u64* counts, uint8_t* fresh, int64_t P, int64_t B) {
+  __shared__ u64 wave_m[kCarWaves];
+  __shared__ uint32_t wave_n[kCarWaves];
+  const uint32_t k = blockIdx.x + 1u;                       // the grid is S - 1 blocks
+  uint4* rows = reinterpret_cast<uint4*>(fresh) + (size_t)k * (size_t)B * 2;
+  uint4* ring = reinterpret_cast<uint4*>(pool) + (size_t)k * (size_t)P * 2;
+  const u64 count = counts[k];                              // read by all before the first barrier, written after the last
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  u64 in_wave = 0;                                          // of this wave's lanes over all tiles: the same in every lane
+  for (int64_t base = 0; base < B; base += kCarBlock) {
+    const int64_t i = base + (int64_t)threadIdx.x;
+    bool has = false;
+    if (i < B) {
+      const uint4 v = rows[2 * i];
+      has = !car_empty(Board{v.x, v.y, v.z, v.w});
+    }
+    in_wave += (u64)wave_count(has);
+  }
+  if (lane == 0u) wave_m[wave] = in_wave;
+  __syncthreads();
+  u64 m = 0;
+#pragma unroll
+  for (int wv = 0; wv < kCarWaves; ++wv) m += wave_m[wv];
+  u64 run = 0;                                              // records of the earlier tiles
+  for (int64_t base = 0; base < B; base += kCarBlock) {
+    const int64_t i = base + (int64_t)threadIdx.x;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (i < B) v = rows[2 * i];
+    const bool has = !car_empty(Board{v.x, v.y, v.z, v.w});
+    const u64 ballot = __ballot(has);
+    if (lane == 0u) wave_n[wave] = (uint32_t)__popcll(ballot);
+    __syncthreads();
+    uint32_t before = 0, tile = 0;
+#pragma unroll
+    for (int wv = 0; wv < kCarWaves; ++wv) {
+      const uint32_t n = wave_n[wv];
+      before += (uint32_t)wv < wave ? n : 0u;
+      tile += n;
+    }
+    if (has) {
+      const u64 r = run + before + (u64)__popcll(ballot & ((1ull << lane) - 1ull));
+      if (car_lands(r, m, (u64)P)) {
+        const uint4 tail = rows[2 * i + 1];
+        uint4* dst = ring + car_slot(count, r, (u64)P) * 2;
+        dst[0] = v;
+        dst[1] = tail;
+      }
+      rows[2 * i] = make_uint4(0u, 0u, 0u, 0u);
+      rows[2 * i + 1] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    run += tile;
+    __syncthreads();                                        // wave_n is written again by the next tile
+  }
+  if (threadIdx.x == 0u) counts[k] = count + m;
+}
+
 // the greedy player on the staged network (q2048_nts_play_rollout): k_nt_play_rollout with q2048_nts_lookup's row
 template <int ENV>
 __global__ __launch_bounds__(kBlock) void k_nts_play_rollout(
@@ -4719,6 +4858,27 @@ int q2048_nts_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, uin
   hipLaunchKernelGGL(k_nts_fused_rollout, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream,
                      boards, aux, weights, stages, B, (int)steps, eps, lr, gamma, seed, env_id0, ctr0, stats_i,
                      stats_f, status);
+  return launch_status();
+}
+int q2048_car_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, uint32_t stages, const uint8_t* pool,
+                            const uint64_t* counts, uint8_t* fresh, int64_t P, int64_t B, int64_t steps, double eps,
+                            double lr, double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i,
+                            double* stats_f, uint32_t* status, void* stream) {
+  if (int e = check_car_fused(boards, aux, weights, stages, pool, counts, fresh, P, B, steps, eps, lr, gamma, status))
+    return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_car_fused_rollout, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream,
+                     boards, aux, weights, stages, pool, reinterpret_cast<const u64*>(counts), fresh, P, B, (int)steps,
+                     eps, lr, gamma, seed, env_id0, ctr0, stats_i, stats_f, status);
+  return launch_status();
+}
+int q2048_car_commit(uint8_t* pool, uint64_t* counts, uint8_t* fresh, uint32_t stages, int64_t P, int64_t B,
+                     void* stream) {
+  if (int e = check_car_commit(pool, counts, fresh, stages, P, B)) return e;
+  const uint32_t S = nts_count(stages);
+  if (B == 0 || S == 1u) return Q2048_OK;
+  hipLaunchKernelGGL(k_car_commit, dim3(S - 1u), dim3(kCarBlock), 0, (hipStream_t)stream, pool,
+                     reinterpret_cast<u64*>(counts), fresh, P, B);
   return launch_status();
 }
 int q2048_nts_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, uint32_t stages, int64_t B, int64_t steps,

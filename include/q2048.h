@@ -1067,6 +1067,40 @@ int q2048_nts_search_play_rollout_depth(uint8_t *boards, q2048_aux *aux, const f
                                         double *stats_f, uint32_t *status, void *stream);
 int q2048_nts_promote(float *weights, uint32_t stages, int from, int to, int64_t *count_out, void *stream);
 
+/* CAROUSEL SHAPING for the staged network: training episodes start in turn at the beginning of every stage, from a pool
+ * of boards on which earlier games entered that stage.  Two functions, additive (the ABI version stays; detect them by
+ * their symbols).  `stages` is the spec of q2048_nts_*, S its number of stages.
+ *   pool      uint8 [S][P][32], 16-byte aligned: a ring of P >= 1 records per stage.  Row 0 is never read or written.
+ *   counts    uint64 [S]: counts[k] = records ever committed to stage k; n_k = min(counts[k], P) records are valid, in
+ *             slots 0 .. n_k-1.
+ *   fresh     uint8 [S][B][32], 16-byte aligned: one record per (stage, lane), written by the learner, consumed by the
+ *             commit.  Start it at zero.
+ *   record    32 bytes: the board (0..15), aux.score (int32, 16..19), the bits of aux.ep_return (20..23), zero
+ *             (24..31).  A record whose 16 board bytes are zero is EMPTY.
+ *   q2048_car_fused_rollout   q2048_nts_fused_rollout with two changes.  RECORDING: if a step does not end the game and
+ *             leaves a board (spawn included) of a later stage k1 than the one it started from, fresh[k1][lane] takes
+ *             the record of the board and aux as the step left them; a later crossing of the lane into the same stage
+ *             in the same call overwrites it, a jump over a stage records at k1 only, a restart records nothing.
+ *             RESTART: aux.episode += 1 and the four reset draws are taken as always; k = aux.episode % S; if k == 0 or
+ *             n_k == 0 the episode starts from an empty board exactly as in q2048_nts_fused_rollout, otherwise board,
+ *             score and ep_return come from pool[k][(x0 * n_k) >> 32], x0 the first reset draw.  The pool and the
+ *             counts are only read; a lane writes only its own fresh[.][lane].  stages == 0 gives
+ *             q2048_nts_fused_rollout's bytes.
+ *   q2048_car_commit   for each stage k = 1 .. S-1: the lanes with a non-empty fresh[k][i], in ascending i, m of them;
+ *             the record of rank r goes to pool[k][(counts[k] + r) % P] if r + P >= m (of more than P records the last
+ *             P land, each in a slot of its own); counts[k] += m; every consumed fresh[k][i] is zeroed whole.
+ *             Stream-ordered after the learner on the same stream.
+ * Errors, in this order: a malformed spec -> Q2048_ERR_RANGE; a NULL pointer (status included) -> Q2048_ERR_NULL; boards,
+ * aux, weights, pool or fresh not 16-byte aligned, counts not 8-byte aligned -> Q2048_ERR_ALIGN; P < 1 or P > 2^32, B or
+ * steps out of range -> Q2048_ERR_SIZE; eps outside [0, 1], lr or gamma NaN -> Q2048_ERR_RANGE.  A refused call writes
+ * nothing; B == 0 or steps == 0 is Q2048_OK and writes nothing. */
+int q2048_car_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weights, uint32_t stages, const uint8_t *pool,
+                            const uint64_t *counts, uint8_t *fresh, int64_t P, int64_t B, int64_t steps, double eps,
+                            double lr, double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t *stats_i,
+                            double *stats_f, uint32_t *status, void *stream);
+int q2048_car_commit(uint8_t *pool, uint64_t *counts, uint8_t *fresh, uint32_t stages, int64_t P, int64_t B,
+                     void *stream);
+
 /* Inverse of q2048_table_export (resume / load a table trained elsewhere): inserts `rows`
  * (key, q[4]) pairs into the table, key_words as above.  A key already present has its row
  * overwritten in place (its slot and key words stay, the four values change); a row that finds no slot

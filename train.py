@@ -107,6 +107,12 @@ def parse_args(argv=None):
     p.add_argument("--promote-every", type=int, default=None, metavar="N",
                    help="with --stage-tiles: every N epochs, copy what each stage has learned into the entries of the next "
                         "stage that are still zero (agent.promote()).  Default 1; 0 = never")
+    p.add_argument("--carousel", type=int, default=None, metavar="P",
+                   help="with --stage-tiles: CAROUSEL SHAPING (q2048_car_*).  Episodes start in turn at the beginning of "
+                        "every stage, from a pool of up to P boards per stage on which earlier games of this process "
+                        "entered that stage (an empty board while a stage's pool is empty).  An episode may then be a "
+                        "spliced game; it counts towards the epochs and the epsilon schedule like any other.  --save keeps "
+                        "the pool; --resume of a file without one starts it empty, another P is refused")
     p.add_argument("--log", default="debug_log.csv", help="CSV log path (Agent/main.py:71)")
     p.add_argument("--report-every", type=int, default=10, help="launches between CSV rows (batched)")
     p.add_argument("--max-steps", type=int, default=0, help="stop after this many env steps per env (0 = off)")
@@ -261,7 +267,7 @@ def train_batched(args, pkg):
     elif args.agent == "ntuple":
         agent = pkg.BatchedNTupleAgent(args.episodes, 4, args.alpha, args.gamma, args.epsilon,
                                        args.epsilon_min, dev, args.seed, shard.env_id0, coherence=args.coherence,
-                                       stage_tiles=args.stage_tiles)
+                                       stage_tiles=args.stage_tiles, **({"carousel": args.carousel} if args.carousel else {}))
     else:
         agent = pkg.BatchedQLearningAgent(args.episodes, 4, args.alpha, args.gamma, args.epsilon,
                                           args.epsilon_min, cap, dev, args.seed, shard.env_id0,
@@ -581,6 +587,11 @@ def main(argv=None):
             raise SystemExit("--promote-every counts epochs: 0 (never) or more")
     elif args.promote_every is not None:
         raise SystemExit("--promote-every applies with --stage-tiles")
+    if args.carousel is not None:
+        if not args.stage_tiles:
+            raise SystemExit("--carousel applies with --stage-tiles")
+        if args.carousel < 1 or args.carousel > 1 << 32:
+            raise SystemExit("--carousel counts the records of a stage's pool: 1 to 2^32")
     if args.coherence:
         if args.agent != "ntuple":
             raise SystemExit(f"--coherence applies to --agent ntuple (the 6-tuple afterstate network), not to --agent {args.agent}")
