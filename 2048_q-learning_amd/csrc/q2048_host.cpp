@@ -901,17 +901,10 @@ struct NtTcSt {
   }
 };
 
-// ---- one-level expectimax (q2048_{av,nt}_search_*): the chance nodes of a state, evaluated serially -------------
-// best(x) of the two families, what search_row asks for at every live node
-struct AvBest {
-  const float* v;
-  float operator()(const Board& x) const { const AvEval ev = av_eval(v, x); return av_best(ev.c.legal, av_row(ev)); }
-};
-struct NtBest {
-  const float* v;
-  float operator()(const Board& x) const { const NtEval ev = nt_eval(x, NtLd{v}); return av_best(ev.legal, ev.q); }
-};
-// the staged network: the table of a stage, and its best
+// ---- the row evaluators of the weight families, one per family, holding what the family needs: the row and the
+// legal-move mask of a board, what a player hands to play_action.  (search_best_of of it is what search_row asks for at
+// every live node.)
+// the staged network: the table of a stage
 struct NtsLdOf {
   const float* v;
   NtLd operator()(uint32_t stage) const { return NtLd{v + (size_t)stage * kNtsStageFloats}; }
@@ -920,37 +913,57 @@ struct NtsStOf {
   float* v;
   NtSt operator()(uint32_t stage) const { return NtSt{v + (size_t)stage * kNtsStageFloats}; }
 };
-struct NtsBest {
-  const float* v;
-  uint32_t stages;
-  float operator()(const Board& x) const { const NtEval ev = nts_eval(x, stages, NtsLdOf{v}); return av_best(ev.legal, ev.q); }
+struct RtEvalOf {
+  const float* w;
+  SearchEval operator()(const Board& b) const { return SearchEval{rt_q(rt_gather(w, b)), legal_mask(b)}; }
 };
-// (DEPTH 2: the two-level row, search_row2 -- the same serial walk one level further down)
-template <class Best, int DEPTH = 1>
-inline SearchEval search_eval(const Board& s, const Best& best) {
-  if constexpr (DEPTH == 2) return search_row2(s, best);
-  else return search_row(s, [&](uint32_t, const Board& node) { return best(node); });
+struct LtEvalOf {
+  const float* w;
+  SearchEval operator()(const Board& b) const { return SearchEval{lt_q(lt_gather(w, lt_indices(b))), legal_mask(b)}; }
+};
+struct AvEvalOf {
+  const float* w;
+  SearchEval operator()(const Board& b) const { const AvEval ev = av_eval(w, b); return SearchEval{av_row(ev), ev.c.legal}; }
+};
+struct NtEvalOf {
+  const float* w;
+  SearchEval operator()(const Board& b) const { const NtEval ev = nt_eval(b, NtLd{w}); return SearchEval{ev.q, ev.legal}; }
+};
+struct NtsEvalOf {
+  const float* w;
+  uint32_t stages;
+  SearchEval operator()(const Board& b) const {
+    const NtEval ev = nts_eval(b, stages, NtsLdOf{w});
+    return SearchEval{ev.q, ev.legal};
+  }
+};
+// the searched row of a board: DEPTH 1 = one level of expectimax over the spawn (search_row, the chance nodes evaluated
+// serially), 2 = the two-level row (search_row2: the same serial walk one level further down)
+template <int DEPTH, class Eval>
+inline SearchEval search_eval(const Board& s, const Eval& eval) {
+  if constexpr (DEPTH == 1) return search_row(s, [&](uint32_t, const Board& node) { return search_best_of(eval(node)); });
+  else return search_row2(s, [&](const Board& x) { return search_best_of(eval(x)); });
 }
-template <class Best, int DEPTH = 1>
-int search_lookup_impl(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out) {
-  if (int e = check_search_lookup(weights, boards, B, q_out, legal_out)) return e;
+// q2048_{av,nt,nts}_search_lookup*; the callers have checked the arguments
+template <int DEPTH, class Eval>
+int search_lookup_impl(Eval eval, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out) {
   parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
     for (int64_t i = lo; i < hi; ++i) {
       Board b;
       load_board(boards, i, b);
-      const SearchEval ev = search_eval<Best, DEPTH>(b, Best{weights});
+      const SearchEval ev = search_eval<DEPTH>(b, eval);
       q_out[4 * i] = ev.q.q0; q_out[4 * i + 1] = ev.q.q1; q_out[4 * i + 2] = ev.q.q2; q_out[4 * i + 3] = ev.q.q3;
       legal_out[i] = (uint8_t)ev.legal;
     }
   });
   return Q2048_OK;
 }
-// q2048_{av,nt}_play_rollout with the searched row
-template <class Best, int DEPTH = 1>
-int search_play_impl(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
-                     uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i, double* stats_f,
-                     uint32_t* status) {
-  if (int e = check_search_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
+// ---- the player on weights (q2048_{rt,lt,av,nt,nts}_play_rollout and the searched players): play_rollout_n's loop with
+// the row and the legal-move mask of `row_of(board)`; the same play_action as the kernels, envs split over the threads,
+// the weights only read.  The callers have checked the arguments.
+template <class RowOf>
+int play_loop(uint8_t* boards, q2048_aux* aux, int64_t B, int64_t steps, double eps, uint64_t seed, uint64_t env_id0,
+              uint32_t ctr0, uint32_t flags, int64_t* stats_i, double* stats_f, RowOf row_of) {
   if (B == 0 || steps == 0) return Q2048_OK;
   const uint64_t eps_t = eps_threshold(eps);
   const ImageLuts lut{&g_lut_image};
@@ -971,7 +984,7 @@ int search_play_impl(uint8_t* boards, q2048_aux* aux, const float* weights, int6
         const Draws x = draws_at(prep, ctr0 + (uint32_t)t);
         Draws y{0u, 0u, 0u, 0u};
         if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-        const SearchEval ev = search_eval<Best, DEPTH>(b, Best{weights});
+        const SearchEval ev = row_of(b);
         bool explored;
         const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
         const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
@@ -992,6 +1005,21 @@ int search_play_impl(uint8_t* boards, q2048_aux* aux, const float* weights, int6
   });
   stats_merge(parts, used, stats_i, stats_f);
   return Q2048_OK;
+}
+// the searched player at a depth the caller has checked (1 or 2)
+template <class Eval>
+int search_play_impl(Eval eval, int depth, uint8_t* boards, q2048_aux* aux, int64_t B, int64_t steps, double eps,
+                     uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i, double* stats_f) {
+  if (depth == 1)
+    return play_loop(boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f,
+                     [=](const Board& b) { return search_eval<1>(b, eval); });
+  return play_loop(boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f,
+                   [=](const Board& b) { return search_eval<2>(b, eval); });
+}
+template <class Eval>
+int search_lookup_depth(Eval eval, int depth, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out) {
+  return depth == 1 ? search_lookup_impl<1>(eval, boards, B, q_out, legal_out)
+                    : search_lookup_impl<2>(eval, boards, B, q_out, legal_out);
 }
 
 // ---- bulk moves of rows into a table (import, merge, fold, unfold) ----------------------------------------------
@@ -1638,53 +1666,12 @@ int q2048_rt_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, int6
   stats_merge(parts, used, stats_i, stats_f);
   return Q2048_OK;
 }
-// the greedy player on weights: play_rollout_n's loop with q2048_rt_lookup's row (rt_q of rt_gather); the same
-// legal_mask / play_action as the kernel, envs split over the threads, the weights only read
+// the greedy player on weights: play_loop with q2048_rt_lookup's row (RtEvalOf: rt_q of rt_gather)
 int q2048_rt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
                           uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                           double* stats_f, uint32_t* status, void*) {
   if (int e = check_rt_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
-  if (B == 0 || steps == 0) return Q2048_OK;
-  const uint64_t eps_t = eps_threshold(eps);
-  const ImageLuts lut{&g_lut_image};
-  const int env = env_bits(flags);
-  const int T = threads_for(B);
-  std::vector<Stats> parts((size_t)T);
-  Stats* sp = parts.data();
-  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
-    Stats& st = sp[tid];
-    for (int64_t i = lo; i < hi; ++i) {
-      const uint64_t id = env_id0 + (uint64_t)i;
-      Board b;
-      load_board(boards, i, b);
-      Aux a = ld_aux(aux, i);
-      const DrawPrep prep = draws_prepare(seed, id, kStreamStep);
-      double reward_sum = 0.0;
-      for (int64_t t = 0; t < steps; ++t) {
-        const Draws x = draws_at(prep, ctr0 + (uint32_t)t);
-        Draws y{0u, 0u, 0u, 0u};
-        if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-        const Row q = rt_q(rt_gather(weights, b));
-        bool explored;
-        const int act = play_action(legal_mask(b), q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
-        const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
-        st.i[Q2048_ST_VALID] += o.valid != 0;
-        st.i[Q2048_ST_EXPLORE] += explored;
-        reward_sum += (double)o.reward;
-        if (o.done) {
-          st.i[Q2048_ST_EPISODES] += 1;
-          st.episode(a, o.max_log2);
-          begin_episode(b, a, seed, id, (env & kEnvResetShaping) != 0);
-        }
-      }
-      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
-      st.f[Q2048_SF_REWARD] += reward_sum;
-      store_board(boards, i, b);
-      st_aux(aux, i, a);
-    }
-  });
-  stats_merge(parts, used, stats_i, stats_f);
-  return Q2048_OK;
+  return play_loop(boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, RtEvalOf{weights});
 }
 
 // ---- the line-tuple family: the row-tuple functions above with lt_gather / lt_q / lt_scatter ----
@@ -1794,47 +1781,7 @@ int q2048_lt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights,
                           uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                           double* stats_f, uint32_t* status, void*) {
   if (int e = check_rt_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
-  if (B == 0 || steps == 0) return Q2048_OK;
-  const uint64_t eps_t = eps_threshold(eps);
-  const ImageLuts lut{&g_lut_image};
-  const int env = env_bits(flags);
-  const int T = threads_for(B);
-  std::vector<Stats> parts((size_t)T);
-  Stats* sp = parts.data();
-  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
-    Stats& st = sp[tid];
-    for (int64_t i = lo; i < hi; ++i) {
-      const uint64_t id = env_id0 + (uint64_t)i;
-      Board b;
-      load_board(boards, i, b);
-      Aux a = ld_aux(aux, i);
-      const DrawPrep prep = draws_prepare(seed, id, kStreamStep);
-      double reward_sum = 0.0;
-      for (int64_t t = 0; t < steps; ++t) {
-        const Draws x = draws_at(prep, ctr0 + (uint32_t)t);
-        Draws y{0u, 0u, 0u, 0u};
-        if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-        const Row q = lt_q(lt_gather(weights, lt_indices(b)));
-        bool explored;
-        const int act = play_action(legal_mask(b), q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
-        const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
-        st.i[Q2048_ST_VALID] += o.valid != 0;
-        st.i[Q2048_ST_EXPLORE] += explored;
-        reward_sum += (double)o.reward;
-        if (o.done) {
-          st.i[Q2048_ST_EPISODES] += 1;
-          st.episode(a, o.max_log2);
-          begin_episode(b, a, seed, id, (env & kEnvResetShaping) != 0);
-        }
-      }
-      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
-      st.f[Q2048_SF_REWARD] += reward_sum;
-      store_board(boards, i, b);
-      st_aux(aux, i, a);
-    }
-  });
-  stats_merge(parts, used, stats_i, stats_f);
-  return Q2048_OK;
+  return play_loop(boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, LtEvalOf{weights});
 }
 
 // ---- the afterstate value family: one evaluation = the four moved boards and their 32 entries ----
@@ -1962,48 +1909,7 @@ int q2048_av_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights,
                           uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                           double* stats_f, uint32_t* status, void*) {
   if (int e = check_av_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
-  if (B == 0 || steps == 0) return Q2048_OK;
-  const uint64_t eps_t = eps_threshold(eps);
-  const ImageLuts lut{&g_lut_image};
-  const int env = env_bits(flags);
-  const int T = threads_for(B);
-  std::vector<Stats> parts((size_t)T);
-  Stats* sp = parts.data();
-  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
-    Stats& st = sp[tid];
-    for (int64_t i = lo; i < hi; ++i) {
-      const uint64_t id = env_id0 + (uint64_t)i;
-      Board b;
-      load_board(boards, i, b);
-      Aux a = ld_aux(aux, i);
-      const DrawPrep prep = draws_prepare(seed, id, kStreamStep);
-      double reward_sum = 0.0;
-      for (int64_t t = 0; t < steps; ++t) {
-        const Draws x = draws_at(prep, ctr0 + (uint32_t)t);
-        Draws y{0u, 0u, 0u, 0u};
-        if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-        const AvEval ev = av_eval(weights, b);
-        const Row q = av_row(ev);
-        bool explored;
-        const int act = play_action(ev.c.legal, q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
-        const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
-        st.i[Q2048_ST_VALID] += o.valid != 0;
-        st.i[Q2048_ST_EXPLORE] += explored;
-        reward_sum += (double)o.reward;
-        if (o.done) {
-          st.i[Q2048_ST_EPISODES] += 1;
-          st.episode(a, o.max_log2);
-          begin_episode(b, a, seed, id, (env & kEnvResetShaping) != 0);
-        }
-      }
-      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
-      st.f[Q2048_SF_REWARD] += reward_sum;
-      store_board(boards, i, b);
-      st_aux(aux, i, a);
-    }
-  });
-  stats_merge(parts, used, stats_i, stats_f);
-  return Q2048_OK;
+  return play_loop(boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, AvEvalOf{weights});
 }
 
 // ---- the 6-tuple afterstate network: one evaluation = the four moved boards and their 4 x 32 entries; nothing is
@@ -2181,94 +2087,52 @@ int q2048_nt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights,
                           uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                           double* stats_f, uint32_t* status, void*) {
   if (int e = check_nt_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
-  if (B == 0 || steps == 0) return Q2048_OK;
-  const uint64_t eps_t = eps_threshold(eps);
-  const ImageLuts lut{&g_lut_image};
-  const int env = env_bits(flags);
-  const int T = threads_for(B);
-  std::vector<Stats> parts((size_t)T);
-  Stats* sp = parts.data();
-  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
-    Stats& st = sp[tid];
-    for (int64_t i = lo; i < hi; ++i) {
-      const uint64_t id = env_id0 + (uint64_t)i;
-      Board b;
-      load_board(boards, i, b);
-      Aux a = ld_aux(aux, i);
-      const DrawPrep prep = draws_prepare(seed, id, kStreamStep);
-      double reward_sum = 0.0;
-      for (int64_t t = 0; t < steps; ++t) {
-        const Draws x = draws_at(prep, ctr0 + (uint32_t)t);
-        Draws y{0u, 0u, 0u, 0u};
-        if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-        const NtEval ev = nt_eval(b, NtLd{weights});
-        bool explored;
-        const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
-        const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
-        st.i[Q2048_ST_VALID] += o.valid != 0;
-        st.i[Q2048_ST_EXPLORE] += explored;
-        reward_sum += (double)o.reward;
-        if (o.done) {
-          st.i[Q2048_ST_EPISODES] += 1;
-          st.episode(a, o.max_log2);
-          begin_episode(b, a, seed, id, (env & kEnvResetShaping) != 0);
-        }
-      }
-      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
-      st.f[Q2048_SF_REWARD] += reward_sum;
-      store_board(boards, i, b);
-      st_aux(aux, i, a);
-    }
-  });
-  stats_merge(parts, used, stats_i, stats_f);
-  return Q2048_OK;
+  return play_loop(boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, NtEvalOf{weights});
 }
 
 // ---- one-level expectimax over the spawn: the players above with the searched row (search_row, q2048_core.hpp) ----
 int q2048_av_search_lookup(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out, void*) {
-  return search_lookup_impl<AvBest>(weights, boards, B, q_out, legal_out);
+  if (int e = check_search_lookup(weights, boards, B, q_out, legal_out)) return e;
+  return search_lookup_impl<1>(AvEvalOf{weights}, boards, B, q_out, legal_out);
 }
 int q2048_av_search_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
                                  uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                                  double* stats_f, uint32_t* status, void*) {
-  return search_play_impl<AvBest>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status);
+  if (int e = check_search_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
+  return search_play_impl(AvEvalOf{weights}, 1, boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f);
 }
 int q2048_nt_search_lookup(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out, void*) {
-  return search_lookup_impl<NtBest>(weights, boards, B, q_out, legal_out);
+  if (int e = check_search_lookup(weights, boards, B, q_out, legal_out)) return e;
+  return search_lookup_impl<1>(NtEvalOf{weights}, boards, B, q_out, legal_out);
 }
 int q2048_nt_search_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
                                  uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                                  double* stats_f, uint32_t* status, void*) {
-  return search_play_impl<NtBest>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status);
+  if (int e = check_search_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
+  return search_play_impl(NtEvalOf{weights}, 1, boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f);
 }
 // ---- the same with a search depth: 1 = the functions above, 2 = the two-level row (search_row2, q2048_core.hpp) ----
 int q2048_av_search_lookup_depth(const float* weights, const uint8_t* boards, int64_t B, int depth, float* q_out,
                                  uint8_t* legal_out, void*) {
   if (int e = check_search_lookup_depth(weights, boards, B, depth, q_out, legal_out)) return e;
-  return depth == 1 ? search_lookup_impl<AvBest, 1>(weights, boards, B, q_out, legal_out)
-                    : search_lookup_impl<AvBest, 2>(weights, boards, B, q_out, legal_out);
+  return search_lookup_depth(AvEvalOf{weights}, depth, boards, B, q_out, legal_out);
 }
 int q2048_av_search_play_rollout_depth(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps,
                                        int depth, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
                                        int64_t* stats_i, double* stats_f, uint32_t* status, void*) {
   if (int e = check_search_play_depth(boards, aux, weights, B, steps, depth, eps, flags, status)) return e;
-  return depth == 1
-      ? search_play_impl<AvBest, 1>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status)
-      : search_play_impl<AvBest, 2>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status);
+  return search_play_impl(AvEvalOf{weights}, depth, boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f);
 }
 int q2048_nt_search_lookup_depth(const float* weights, const uint8_t* boards, int64_t B, int depth, float* q_out,
                                  uint8_t* legal_out, void*) {
   if (int e = check_search_lookup_depth(weights, boards, B, depth, q_out, legal_out)) return e;
-  return depth == 1 ? search_lookup_impl<NtBest, 1>(weights, boards, B, q_out, legal_out)
-                    : search_lookup_impl<NtBest, 2>(weights, boards, B, q_out, legal_out);
+  return search_lookup_depth(NtEvalOf{weights}, depth, boards, B, q_out, legal_out);
 }
 int q2048_nt_search_play_rollout_depth(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps,
                                        int depth, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
                                        int64_t* stats_i, double* stats_f, uint32_t* status, void*) {
   if (int e = check_search_play_depth(boards, aux, weights, B, steps, depth, eps, flags, status)) return e;
-  return depth == 1
-      ? search_play_impl<NtBest, 1>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status)
-      : search_play_impl<NtBest, 2>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status);
+  return search_play_impl(NtEvalOf{weights}, depth, boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f);
 }
 
 // ---- the staged network (q2048_nts_*): the functions above with nts_eval / nts_td, the table picked per candidate ----
@@ -2468,93 +2332,24 @@ int q2048_car_commit(uint8_t* pool, uint64_t* counts, uint8_t* fresh, uint32_t s
   }
   return Q2048_OK;
 }
-// the players: one loop for the greedy row (DEPTH 0) and the searched rows (DEPTH 1, 2); the callers have checked
-extern "C++" {
-template <int DEPTH>
-static SearchEval nts_row(const Board& b, const NtsBest& best) {
-  if constexpr (DEPTH == 0) {
-    const NtEval ev = nts_eval(b, best.stages, NtsLdOf{best.v});
-    return SearchEval{ev.q, ev.legal};
-  } else {
-    return search_eval<NtsBest, DEPTH>(b, best);
-  }
-}
-template <int DEPTH>
-static int nts_play_impl(uint8_t* boards, q2048_aux* aux, const float* weights, uint32_t stages, int64_t B, int64_t steps,
-                         double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
-                         double* stats_f) {
-  if (B == 0 || steps == 0) return Q2048_OK;
-  const uint64_t eps_t = eps_threshold(eps);
-  const ImageLuts lut{&g_lut_image};
-  const int env = env_bits(flags);
-  const int T = threads_for(B);
-  std::vector<Stats> parts((size_t)T);
-  Stats* sp = parts.data();
-  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
-    Stats& st = sp[tid];
-    for (int64_t i = lo; i < hi; ++i) {
-      const uint64_t id = env_id0 + (uint64_t)i;
-      Board b;
-      load_board(boards, i, b);
-      Aux a = ld_aux(aux, i);
-      const DrawPrep prep = draws_prepare(seed, id, kStreamStep);
-      double reward_sum = 0.0;
-      for (int64_t t = 0; t < steps; ++t) {
-        const Draws x = draws_at(prep, ctr0 + (uint32_t)t);
-        Draws y{0u, 0u, 0u, 0u};
-        if (env & kEnvDqn) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-        const SearchEval ev = nts_row<DEPTH>(b, NtsBest{weights, stages});
-        bool explored;
-        const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
-        const StepOut o = env_step_any(env, b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
-        st.i[Q2048_ST_VALID] += o.valid != 0;
-        st.i[Q2048_ST_EXPLORE] += explored;
-        reward_sum += (double)o.reward;
-        if (o.done) {
-          st.i[Q2048_ST_EPISODES] += 1;
-          st.episode(a, o.max_log2);
-          begin_episode(b, a, seed, id, (env & kEnvResetShaping) != 0);
-        }
-      }
-      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
-      st.f[Q2048_SF_REWARD] += reward_sum;
-      store_board(boards, i, b);
-      st_aux(aux, i, a);
-    }
-  });
-  stats_merge(parts, used, stats_i, stats_f);
-  return Q2048_OK;
-}
-}  // extern "C++"
 int q2048_nts_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, uint32_t stages, int64_t B, int64_t steps,
                            double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                            double* stats_f, uint32_t* status, void*) {
   if (int e = check_nts_play(boards, aux, weights, stages, B, steps, eps, flags, status)) return e;
-  return nts_play_impl<0>(boards, aux, weights, stages, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f);
+  return play_loop(boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, NtsEvalOf{weights, stages});
 }
 int q2048_nts_search_lookup_depth(const float* weights, uint32_t stages, const uint8_t* boards, int64_t B, int depth,
                                   float* q_out, uint8_t* legal_out, void*) {
   if (int e = check_nts_search_lookup_depth(weights, stages, boards, B, depth, q_out, legal_out)) return e;
-  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
-    for (int64_t i = lo; i < hi; ++i) {
-      Board b;
-      load_board(boards, i, b);
-      const NtsBest best{weights, stages};
-      const SearchEval ev = depth == 1 ? nts_row<1>(b, best) : nts_row<2>(b, best);
-      q_out[4 * i] = ev.q.q0; q_out[4 * i + 1] = ev.q.q1; q_out[4 * i + 2] = ev.q.q2; q_out[4 * i + 3] = ev.q.q3;
-      legal_out[i] = (uint8_t)ev.legal;
-    }
-  });
-  return Q2048_OK;
+  return search_lookup_depth(NtsEvalOf{weights, stages}, depth, boards, B, q_out, legal_out);
 }
 int q2048_nts_search_play_rollout_depth(uint8_t* boards, q2048_aux* aux, const float* weights, uint32_t stages, int64_t B,
                                         int64_t steps, int depth, double eps, uint64_t seed, uint64_t env_id0,
                                         uint32_t ctr0, uint32_t flags, int64_t* stats_i, double* stats_f,
                                         uint32_t* status, void*) {
   if (int e = check_nts_search_play_depth(boards, aux, weights, stages, B, steps, depth, eps, flags, status)) return e;
-  return depth == 1
-      ? nts_play_impl<1>(boards, aux, weights, stages, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f)
-      : nts_play_impl<2>(boards, aux, weights, stages, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f);
+  return search_play_impl(NtsEvalOf{weights, stages}, depth, boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i,
+                          stats_f);
 }
 // promotion: the rule of nts_promotes on every entry, bits in and bits out
 int q2048_nts_promote(float* weights, uint32_t stages, int from, int to, int64_t* count_out, void*) {

@@ -1979,14 +1979,18 @@ __global__ __launch_bounds__(kBlock) void k_rt_fused_rollout(
   stats_flush(bs, stats_i, stats_f);
 }
 
-// the greedy player on weights (q2048_rt_play_rollout): k_play_rollout's loop with q2048_rt_lookup's row -- per step
-// the four entries of the state (requested together, one wait), rt_q, the trial-move mask, play_action, the env
-// step on the step's own draws, and on done the episode statistics and the reset.  One lane per env, board and aux
-// in registers for the launch, one LutImage per workgroup in LDS; every loop is bounded by `steps`, no lane waits
-// for another.  W is only read: the launch boundary orders it against the training launches of the stream (the
-// vector L1 starts a kernel invalid), so the loads are PLAIN loads, not the learner's agent-scope sc1 ones -- nothing
-// writes W while this runs, and the entries most lanes share (rows of few tiles) may then be served from the CU's L1.
-// A kernel of its own, not k_play_rollout templated on a row source: no existing instantiation changes.
+// the greedy player on weights (q2048_{rt,lt,av,nt,nts}_play_rollout: k_eval_play_rollout<EVAL, ENV>): k_play_rollout's
+// loop with the row of a family's evaluator -- per step the entries of the state (requested together, one wait), the
+// row and the legal-move mask, play_action, the env step on the step's own draws, and on done the episode statistics
+// and the reset.  One lane per env, board and aux in registers for the launch, one LutImage per workgroup in LDS; every
+// loop is bounded by `steps`, no lane waits for another.  W is only read: the launch boundary orders it against the
+// training launches of the stream (the vector L1 starts a kernel invalid), so the loads are PLAIN loads, not the
+// learner's agent-scope sc1 ones -- nothing writes W while this runs, and the entries most lanes share (rows of few
+// tiles) may then be served from the CU's L1.
+// An EVALUATOR (RtEvalOf, LtEvalOf, AvEvalOf, NtEvalOf, NtsEvalOf, each beside its family's kernels) holds what the
+// family needs -- the weights, for the staged network the `stages` word too -- and is ONE kernel argument, by value,
+// where `weights[, stages]` stand in the entry point; its operator() is the row and the legal-move mask of a board
+// (SearchEval) with the player's ordinary loads.  The search asks for search_best_of of the same evaluation at a node.
 __device__ __forceinline__ RtRows rt_gather_readonly(const float* w, const Board& b) {
   u32x4 v0, v1, v2, v3;
   asm volatile(
@@ -1999,16 +2003,27 @@ __device__ __forceinline__ RtRows rt_gather_readonly(const float* w, const Board
       : "memory");
   return RtRows{rt_row(v0), rt_row(v1), rt_row(v2), rt_row(v3)};
 }
-template <int ENV>
-__global__ __launch_bounds__(kBlock) void k_rt_play_rollout(
-    uint8_t* boards, q2048_aux* aux, const float* w, int64_t B, int steps, double eps, uint64_t seed,
+struct RtEvalOf {
+  const float* w;
+  __device__ __forceinline__ SearchEval operator()(const Board& b) const {
+    return SearchEval{rt_q(rt_gather_readonly(w, b)), legal_mask(b)};
+  }
+};
+// the players' LutImage of the workgroup, a double per thread: the block barrier that follows in every caller
+// (stats_clear's) publishes it
+__device__ __forceinline__ void lut_image_to_lds(LutImage& lut_lds) {
+  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
+  if (threadIdx.x < kLutImageDoubles)
+    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
+}
+template <class EVAL, int ENV>
+__global__ __launch_bounds__(kBlock) void k_eval_play_rollout(
+    uint8_t* boards, q2048_aux* aux, EVAL eval, int64_t B, int steps, double eps, uint64_t seed,
     uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
   __shared__ BlockStats bs;
   __shared__ Stage<4> st;
   __shared__ LutImage lut_lds;
-  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
-  if (threadIdx.x < kLutImageDoubles)
-    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
+  lut_image_to_lds(lut_lds);
   stats_clear(bs);                                        // (its barrier publishes the image too)
   const ImageLuts lut{&lut_lds};
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -2024,9 +2039,9 @@ __global__ __launch_bounds__(kBlock) void k_rt_play_rollout(
       const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
       Draws y{0u, 0u, 0u, 0u};
       if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-      const Row q = rt_q(rt_gather_readonly(w, b));
+      const SearchEval ev = eval(b);
       bool explored;
-      const int act = play_action(legal_mask(b), q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
+      const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
       const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
       if (o.done) {
         episode_stats(bs, a, o.max_log2);
@@ -2060,7 +2075,6 @@ __global__ __launch_bounds__(kBlock) void k_rt_play_rollout(
 // gathered, a plain 4-byte store, the last writer wins.  The column indices come from ONE
 // transpose per state (lt_indices): the fused loop computes the indices of s' once and uses them
 // for the gather, for the carried-entry rule and, one step later, for the scatter.
-// Kernels of their own, not the rt_ ones templated on a feature count: no existing kernel changes.
 // ---------------------------------------------------------------------------------------------
 struct LtRows { Row e[kLtFeatures]; };
 // the eight entries of a state: eight 16-byte agent-scope loads in flight together, one wait
@@ -2210,58 +2224,13 @@ __global__ __launch_bounds__(kBlock) void k_lt_fused_rollout(
   stats_flush(bs, stats_i, stats_f);
 }
 
-// the greedy player on line-tuple weights (q2048_lt_play_rollout): k_rt_play_rollout with q2048_lt_lookup's row
-template <int ENV>
-__global__ __launch_bounds__(kBlock) void k_lt_play_rollout(
-    uint8_t* boards, q2048_aux* aux, const float* w, int64_t B, int steps, double eps, uint64_t seed,
-    uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
-  __shared__ BlockStats bs;
-  __shared__ Stage<4> st;
-  __shared__ LutImage lut_lds;
-  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
-  if (threadIdx.x < kLutImageDoubles)
-    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
-  stats_clear(bs);                                        // (its barrier publishes the image too)
-  const ImageLuts lut{&lut_lds};
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  Board b = load_board(boards, i, B, st);
-  if (i < B) {
-    const uint64_t id = env_id0 + (uint64_t)i;
-    Aux a = ld_aux(aux, i);
-    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
-    double reward_sum = 0.0;
-    const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
-    const uint64_t eps_t = eps_threshold(eps);
-    for (int t = 0; t < steps; ++t) {
-      const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
-      Draws y{0u, 0u, 0u, 0u};
-      if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-      const Row q = lt_q(lt_gather_readonly(w, lt_indices(b)));
-      bool explored;
-      const int act = play_action(legal_mask(b), q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
-      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
-      if (o.done) {
-        episode_stats(bs, a, o.max_log2);
-        begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
-      }
-      n_valid += wave_count(o.valid != 0);
-      n_explore += wave_count(explored);
-      n_done += wave_count(o.done != 0);
-      reward_sum += (double)o.reward;
-    }
-    st_aux(aux, i, a);
-    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
-    const uint32_t n_active = wave_count(true);
-    if (wave_leader()) {
-      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
-      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
-      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
-      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
-    }
+// the player's evaluator (q2048_lt_play_rollout): q2048_lt_lookup's row with ordinary loads
+struct LtEvalOf {
+  const float* w;
+  __device__ __forceinline__ SearchEval operator()(const Board& b) const {
+    return SearchEval{lt_q(lt_gather_readonly(w, lt_indices(b))), legal_mask(b)};
   }
-  store_board(boards, i, B, b, st);
-  stats_flush(bs, stats_i, stats_f);
-}
+};
 
 // ---------------------------------------------------------------------------------------------
 // afterstate value learner on the line features (q2048_av_*): V = float[8][65536], 2 MiB, inside
@@ -2272,7 +2241,7 @@ __global__ __launch_bounds__(kBlock) void k_lt_play_rollout(
 // (another CU's stores must be seen: the compiler emits sc1 loads), ordinary loads in the player
 // -- because one asm block would need 64 operands.  No load is predicated on its move being
 // legal: all 32 are always issued.  A write stores gathered + d with a plain 4-byte store, the
-// last writer wins.  Kernels of their own; no existing kernel changes.
+// last writer wins.
 // ---------------------------------------------------------------------------------------------
 template <bool AGENT>
 __device__ __forceinline__ float av_ld(const float* v, int f, uint32_t idx) {
@@ -2407,59 +2376,15 @@ __global__ __launch_bounds__(kBlock) void k_av_fused_rollout(
   stats_flush(bs, stats_i, stats_f);
 }
 
-// the greedy player on afterstate values (q2048_av_play_rollout): k_lt_play_rollout with q2048_av_lookup's row
-template <int ENV>
-__global__ __launch_bounds__(kBlock) void k_av_play_rollout(
-    uint8_t* boards, q2048_aux* aux, const float* w, int64_t B, int steps, double eps, uint64_t seed,
-    uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
-  __shared__ BlockStats bs;
-  __shared__ Stage<4> st;
-  __shared__ LutImage lut_lds;
-  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
-  if (threadIdx.x < kLutImageDoubles)
-    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
-  stats_clear(bs);                                        // (its barrier publishes the image too)
-  const ImageLuts lut{&lut_lds};
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  Board b = load_board(boards, i, B, st);
-  if (i < B) {
-    const uint64_t id = env_id0 + (uint64_t)i;
-    Aux a = ld_aux(aux, i);
-    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
-    double reward_sum = 0.0;
-    const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
-    const uint64_t eps_t = eps_threshold(eps);
-    for (int t = 0; t < steps; ++t) {
-      const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
-      Draws y{0u, 0u, 0u, 0u};
-      if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-      const AvEval ev = av_eval<false>(w, b);
-      const Row q = av_row(ev);
-      bool explored;
-      const int act = play_action(ev.c.legal, q.q0, q.q1, q.q2, q.q3, eps_t, x.x0, x.x1, explored);
-      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
-      if (o.done) {
-        episode_stats(bs, a, o.max_log2);
-        begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
-      }
-      n_valid += wave_count(o.valid != 0);
-      n_explore += wave_count(explored);
-      n_done += wave_count(o.done != 0);
-      reward_sum += (double)o.reward;
-    }
-    st_aux(aux, i, a);
-    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
-    const uint32_t n_active = wave_count(true);
-    if (wave_leader()) {
-      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
-      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
-      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
-      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
-    }
+// the player's and the search's evaluator (q2048_av_play_rollout, q2048_av_search_*): q2048_av_lookup's row with
+// ordinary loads
+struct AvEvalOf {
+  const float* w;
+  __device__ __forceinline__ SearchEval operator()(const Board& b) const {
+    const AvEval ev = av_eval<false>(w, b);
+    return SearchEval{av_row(ev), ev.c.legal};
   }
-  store_board(boards, i, B, b, st);
-  stats_flush(bs, stats_i, stats_f);
-}
+};
 
 // ---------------------------------------------------------------------------------------------
 // 6-tuple afterstate network with shared symmetric weights (q2048_nt_*): V = float[4][2^24],
@@ -2471,7 +2396,6 @@ __global__ __launch_bounds__(kBlock) void k_av_play_rollout(
 // own writes, which is what makes B = 1 the four-call loop) and gathers the 32 entries of the
 // afterstate again for the TD step.  Loads in plain C++, relaxed agent-scope atomic loads in the
 // learner kernels, ordinary loads in the player; none is predicated on its move being legal.
-// Kernels of their own; no existing kernel changes.
 // ---------------------------------------------------------------------------------------------
 template <bool AGENT>
 struct NtLd {
@@ -2677,98 +2601,36 @@ __global__ __launch_bounds__(kBlock, 2) void k_nt_tc_fused_rollout(
   stats_flush(bs, stats_i, stats_f);
 }
 
-// the greedy player on the network (q2048_nt_play_rollout): k_av_play_rollout with q2048_nt_lookup's row
-template <int ENV>
-__global__ __launch_bounds__(kBlock) void k_nt_play_rollout(
-    uint8_t* boards, q2048_aux* aux, const float* w, int64_t B, int steps, double eps, uint64_t seed,
-    uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
-  __shared__ BlockStats bs;
-  __shared__ Stage<4> st;
-  __shared__ LutImage lut_lds;
-  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
-  if (threadIdx.x < kLutImageDoubles)
-    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
-  stats_clear(bs);                                        // (its barrier publishes the image too)
-  const ImageLuts lut{&lut_lds};
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  Board b = load_board(boards, i, B, st);
-  if (i < B) {
-    const uint64_t id = env_id0 + (uint64_t)i;
-    Aux a = ld_aux(aux, i);
-    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
-    double reward_sum = 0.0;
-    const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
-    const uint64_t eps_t = eps_threshold(eps);
-    for (int t = 0; t < steps; ++t) {
-      const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
-      Draws y{0u, 0u, 0u, 0u};
-      if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-      const NtEval ev = nt_eval(b, NtLd<false>{w});
-      bool explored;
-      const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
-      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
-      if (o.done) {
-        episode_stats(bs, a, o.max_log2);
-        begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
-      }
-      n_valid += wave_count(o.valid != 0);
-      n_explore += wave_count(explored);
-      n_done += wave_count(o.done != 0);
-      reward_sum += (double)o.reward;
-    }
-    st_aux(aux, i, a);
-    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
-    const uint32_t n_active = wave_count(true);
-    if (wave_leader()) {
-      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
-      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
-      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
-      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
-    }
+// the player's and the search's evaluator (q2048_nt_play_rollout, q2048_nt_search_*): q2048_nt_lookup's row with
+// ordinary loads
+struct NtEvalOf {
+  const float* w;
+  __device__ __forceinline__ SearchEval operator()(const Board& b) const {
+    const NtEval ev = nt_eval(b, NtLd<false>{w});
+    return SearchEval{ev.q, ev.legal};
   }
-  store_board(boards, i, B, b, st);
-  stats_flush(bs, stats_i, stats_f);
-}
+};
 
 // ---------------------------------------------------------------------------------------------
-// One-level expectimax over the spawn (q2048_{av,nt}_search_*; the definition is search_row in
-// q2048_core.hpp).  ONE WAVE PER BOARD, four boards per block: a searched step evaluates up to 120
-// successor states of a board, each as expensive as a whole greedy step, and with one lane per board
-// 65,536 boards would be one wave per SIMD waiting behind 120 evaluations in a row.  The board, its
-// aux and its draws are wave-uniform -- every lane holds them and steps the env redundantly; lane 0
-// stores.  The chance nodes have 128 fixed slots (a * 32 + j * 2 + tile); the live ones are spread
-// over the lanes (search_wave): a lane with a node runs the family's unchanged evaluation on it (32
-// loads in flight per candidate, ordinary loads) and publishes best to the node's slot in the wave's
-// 128 floats of LDS, a lane without a node issues no load.  Every lane then sums the row from LDS in
-// search_row's order.  The array is written, read by other lanes and written again on the next step: both
-// hazards are ordered by wave_lds_sync, not by the wave running in lockstep.  Statistics are per
-// BOARD: the counters are wave-uniform and lane 0 adds them once.  A wave whose board is past the
-// batch skips the body and still reaches every block barrier.  Kernels of their own; no existing
-// kernel changes.
+// One-level expectimax over the spawn (q2048_{av,nt}_search_*, q2048_nts_search_*; the definition is
+// search_row in q2048_core.hpp).  ONE WAVE PER BOARD, four boards per block: a searched step
+// evaluates up to 120 successor states of a board, each as expensive as a whole greedy step, and
+// with one lane per board 65,536 boards would be one wave per SIMD waiting behind 120 evaluations in
+// a row.  The board, its aux and its draws are wave-uniform -- every lane holds them and steps the
+// env redundantly; lane 0 stores.  The chance nodes have 128 fixed slots (a * 32 + j * 2 + tile); the
+// live ones are spread over the lanes (search_wave): a lane with a node runs the family's unchanged
+// evaluation on it (EVAL: 32 loads in flight per candidate, ordinary loads) and publishes best to the
+// node's slot in the wave's 128 floats of LDS, a lane without a node issues no load.  Every lane then
+// sums the row from LDS in search_row's order.  The array is written, read by other lanes and written
+// again on the next step: both hazards are ordered by wave_lds_sync, not by the wave running in
+// lockstep.  Statistics are per BOARD: the counters are wave-uniform and lane 0 adds them once.  A
+// wave whose board is past the batch skips the body and still reaches every block barrier.
 // ---------------------------------------------------------------------------------------------
 constexpr int kSearchBoards = kBlock / 64;       // boards per block
 constexpr int64_t kSearchMaxBoards = (int64_t)0x7fffffff * kSearchBoards;   // per launch: grid.x is a 31-bit number
-constexpr int kFamAv = 0, kFamNt = 1;
-// best(x) of a family with the player's ordinary loads
-template <int FAM>
-__device__ __forceinline__ float search_best(const float* w, const Board& x) {
-  if constexpr (FAM == kFamAv) {
-    const AvEval ev = av_eval<false>(w, x);
-    return av_best(ev.c.legal, av_row(ev));
-  } else {
-    const NtEval ev = nt_eval(x, NtLd<false>{w});
-    return av_best(ev.legal, ev.q);
-  }
-}
-// the searched row of the wave's board; `best` = this wave's kSearchSlots floats of LDS.  Every lane calls it.
-// The live nodes are COMPACTED over the lanes: `cells` (wave-uniform; bit 16a + j = move a is legal and cell j of c_a
-// is empty) lists them in slot order, node k is tile k & 1 of the (k >> 1)-th set bit, and lane l takes the nodes l,
-// l + 64, ...  A mid-game board has about 38 nodes, so most steps are one round of evaluations, not the two that
-// fixed lanes per slot take (measured: profiles/r15_search_step_time.jsonl beside r15_search_step_time_fixed_slots.jsonl).
-// What a node publishes to is still its fixed slot.
-template <int FAM>
-__device__ __forceinline__ SearchEval search_wave(const float* w, const Board& s, float* best) {
-  const uint32_t lane = threadIdx.x & 63u;
+// The live chance nodes of a board in slot order.  `cells` (bit 16a + j = move a is legal and cell j of c_a is empty)
+// lists them: node k is tile k & 1 of the (k >> 1)-th set bit.
+__device__ __forceinline__ u64 search_cells(const Board& s) {
   u64 cells = 0ull;
 #pragma unroll 1
   for (int a = 0; a < 4; ++a) {
@@ -2776,17 +2638,41 @@ __device__ __forceinline__ SearchEval search_wave(const float* w, const Board& s
     uint32_t score;
     if (move(c, a, score)) cells |= (u64)empty_mask(c) << (16 * a);
   }
-  const uint32_t p0 = popc((uint32_t)cells & 0xffffu), p1 = p0 + popc((uint32_t)(cells >> 16) & 0xffffu);
-  const uint32_t p2 = p1 + popc((uint32_t)(cells >> 32) & 0xffffu), total = 2u * (p2 + popc((uint32_t)(cells >> 48)));
+  return cells;
+}
+// the set bits of `cells` below move 1, 2, 3: counted once per board, before the loop over its nodes
+struct SearchCounts {
+  uint32_t p0, p1, p2;
+  __device__ __forceinline__ explicit SearchCounts(u64 cells) {
+    p0 = popc((uint32_t)cells & 0xffffu);
+    p1 = p0 + popc((uint32_t)(cells >> 16) & 0xffffu);
+    p2 = p1 + popc((uint32_t)(cells >> 32) & 0xffffu);
+  }
+};
+// the fixed slot of the k-th live node (k < 2 * popcount(cells))
+__device__ __forceinline__ uint32_t search_slot(u64 cells, SearchCounts n, uint32_t k) {
+  const uint32_t p0 = n.p0, p1 = n.p1, p2 = n.p2, r = k >> 1;
+  const uint32_t a = (uint32_t)(r >= p0) + (uint32_t)(r >= p1) + (uint32_t)(r >= p2);
+  const uint32_t before = a == 0u ? 0u : a == 1u ? p0 : a == 2u ? p1 : p2;
+  const uint32_t j = kth_set_bit16((uint32_t)(cells >> (16u * a)) & 0xffffu, r - before);
+  return a * 32u + j * 2u + (k & 1u);                     // < kSearchSlots: a < 4, j < 16
+}
+// the searched row of the wave's board; `best` = this wave's kSearchSlots floats of LDS.  Every lane calls it.
+// The live nodes are COMPACTED over the lanes: lane l takes the nodes l, l + 64, ... of search_cells (wave-uniform).  A
+// mid-game board has about 38 nodes, so most steps are one round of evaluations, not the two that fixed lanes per slot
+// take (measured: profiles/r15_search_step_time.jsonl beside r15_search_step_time_fixed_slots.jsonl).  What a node
+// publishes to is still its fixed slot.
+template <class EVAL>
+__device__ __forceinline__ SearchEval search_wave(const EVAL& eval, const Board& s, float* best) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const u64 cells = search_cells(s);
+  const SearchCounts n(cells);
+  const uint32_t total = 2u * (n.p2 + popc((uint32_t)(cells >> 48)));
 #pragma unroll 1
   for (uint32_t k = lane; k < total; k += 64u) {          // k < total <= 120: at most two rounds
-    const uint32_t r = k >> 1;
-    const uint32_t a = (uint32_t)(r >= p0) + (uint32_t)(r >= p1) + (uint32_t)(r >= p2);
-    const uint32_t before = a == 0u ? 0u : a == 1u ? p0 : a == 2u ? p1 : p2;
-    const uint32_t j = kth_set_bit16((uint32_t)(cells >> (16u * a)) & 0xffffu, r - before);
-    const uint32_t slot = a * 32u + j * 2u + (k & 1u);    // < kSearchSlots: a < 4, j < 16
+    const uint32_t slot = search_slot(cells, n, k);
     Board node;
-    if (search_node(s, slot, node)) best[slot] = search_best<FAM>(w, node);   // (live by construction)
+    if (search_node(s, slot, node)) best[slot] = search_best_of(eval(node));   // (live by construction)
   }
   wave_lds_sync();                                        // the nodes are published before any lane sums them
   const SearchEval ev = search_row(s, [best](uint32_t slot, const Board&) { return best[slot]; });
@@ -2794,43 +2680,42 @@ __device__ __forceinline__ SearchEval search_wave(const float* w, const Board& s
   return ev;
 }
 
-template <int FAM>
-__global__ __launch_bounds__(kBlock) void k_search_lookup(const float* w, const uint8_t* boards, int64_t first, int64_t B,
+template <class EVAL>
+__global__ __launch_bounds__(kBlock) void k_search_lookup(EVAL eval, const uint8_t* boards, int64_t first, int64_t B,
                                                           float* q_out, uint8_t* legal_out) {
   __shared__ float best[kSearchBoards][kSearchSlots];
   __shared__ Stage<4> st;
   const int wave = (int)(threadIdx.x >> 6);
   const int64_t i = first + (int64_t)blockIdx.x * kSearchBoards + wave;
   if (i >= B) return;                                     // (no block barrier in this kernel)
-  const SearchEval ev = search_wave<FAM>(w, load_board(boards, i, B, st), best[wave]);
+  const SearchEval ev = search_wave(eval, load_board(boards, i, B, st), best[wave]);
   if ((threadIdx.x & 63u) == 0u) {
     reinterpret_cast<float4*>(q_out)[i] = make_float4(ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3);
     legal_out[i] = (uint8_t)ev.legal;
   }
 }
 
-// the player with the searched row (q2048_{av,nt}_search_play_rollout): k_av_play_rollout / k_nt_play_rollout per wave
-template <int FAM, int ENV>
-__global__ __launch_bounds__(kBlock) void k_search_play_rollout(
-    uint8_t* boards, q2048_aux* aux, const float* w, int64_t first, int64_t B, int steps, double eps, uint64_t seed,
-    uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
+// the player of ONE board by many threads (a wave at depth 1, the block at depth 2): k_eval_play_rollout's loop with the
+// board `i`, its aux and its draws uniform over those threads -- every one of them holds them and steps the env
+// redundantly, the one for which `stores` holds writes the board, the aux record and the statistics, which are per
+// BOARD (plain counters, added once).  `row_of` yields the searched row; every thread of the board calls it.  `live`:
+// the board exists (i < B).  Every thread of the BLOCK calls this function: a wave whose board is past the batch skips
+// the body and still reaches every block barrier (stats_clear's and stats_flush's).
+template <int ENV, class RowOf>
+__device__ __forceinline__ void board_play_rollout(uint8_t* boards, q2048_aux* aux, int64_t i, bool live, bool stores,
+                                                   const RowOf& row_of, int64_t B, int steps, double eps, uint64_t seed,
+                                                   uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
   __shared__ BlockStats bs;
   __shared__ Stage<4> st;
   __shared__ LutImage lut_lds;
-  __shared__ float best[kSearchBoards][kSearchSlots];
-  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
-  if (threadIdx.x < kLutImageDoubles)
-    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
+  lut_image_to_lds(lut_lds);
   stats_clear(bs);                                        // (its barrier publishes the image too)
   const ImageLuts lut{&lut_lds};
-  const int wave = (int)(threadIdx.x >> 6);
-  const bool first_lane = (threadIdx.x & 63u) == 0u;
-  const int64_t i = first + (int64_t)blockIdx.x * kSearchBoards + wave;   // wave-uniform
-  if (i < B) {
+  if (live) {
     const uint64_t id = env_id0 + (uint64_t)i;
     Board b = load_board(boards, i, B, st);
     Aux a = ld_aux(aux, i);
-    uint32_t n_valid = 0, n_explore = 0, n_done = 0;      // of this BOARD: the same in every lane
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;      // of this BOARD: the same in every one of its threads
     double reward_sum = 0.0;
     const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
     const uint64_t eps_t = eps_threshold(eps);
@@ -2838,12 +2723,12 @@ __global__ __launch_bounds__(kBlock) void k_search_play_rollout(
       const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
       Draws y{0u, 0u, 0u, 0u};
       if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-      const SearchEval ev = search_wave<FAM>(w, b, best[wave]);
+      const SearchEval ev = row_of(b);
       bool explored;
       const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
       const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
       if (o.done) {
-        if (first_lane) episode_stats(bs, a, o.max_log2);
+        if (stores) episode_stats(bs, a, o.max_log2);
         begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
       }
       n_valid += o.valid != 0;
@@ -2851,7 +2736,7 @@ __global__ __launch_bounds__(kBlock) void k_search_play_rollout(
       n_done += o.done != 0;
       reward_sum += (double)o.reward;
     }
-    if (first_lane) {
+    if (stores) {
       store_board(boards, i, B, b, st);
       st_aux(aux, i, a);
       atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
@@ -2864,59 +2749,53 @@ __global__ __launch_bounds__(kBlock) void k_search_play_rollout(
   stats_flush(bs, stats_i, stats_f);
 }
 
+// the player with the searched row (q2048_{av,nt}_search_play_rollout, q2048_nts_search_play_rollout_depth at depth 1):
+// a wave per board, lane 0 stores
+template <class EVAL, int ENV>
+__global__ __launch_bounds__(kBlock) void k_search_play_rollout(
+    uint8_t* boards, q2048_aux* aux, EVAL eval, int64_t first, int64_t B, int steps, double eps, uint64_t seed,
+    uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
+  __shared__ float best[kSearchBoards][kSearchSlots];
+  float* mine = best[threadIdx.x >> 6];
+  const int64_t i = first + (int64_t)blockIdx.x * kSearchBoards + (int64_t)(threadIdx.x >> 6);   // wave-uniform
+  board_play_rollout<ENV>(boards, aux, i, i < B, (threadIdx.x & 63u) == 0u,
+                          [&](const Board& b) { return search_wave(eval, b, mine); }, B, steps, eps, seed, env_id0, ctr0,
+                          stats_i, stats_f);
+}
+
 // ---------------------------------------------------------------------------------------------
-// Two-level expectimax (q2048_{av,nt}_search_*_depth with depth 2; the definition is search_row2 in
-// q2048_core.hpp).  ONE BLOCK PER BOARD: a depth-2 step is up to 120 level-one nodes, each a whole
+// Two-level expectimax (q2048_{av,nt,nts}_search_*_depth with depth 2; the definition is search_row2
+// in q2048_core.hpp).  ONE BLOCK PER BOARD: a depth-2 step is up to 120 level-one nodes, each a whole
 // searched step of the one-level player, so a board gets the four waves that player gives to four
 // boards.  The board, its aux and its draws are block-uniform -- every lane holds them and steps the
-// env redundantly; thread 0 stores.  The live level-one nodes are compacted from the `cells` mask of
-// search_wave, in slot order (search2_slot); wave w takes the nodes w, w + 4, ...: it builds the node
-// (search_node), runs the unchanged search_wave on it with its own 128 floats of LDS -- the leaves of
-// the node over the wave's lanes -- takes best_1 = search_best_of the result, and lane 0 publishes it
-// to the node's fixed slot in the block's array of kSearchSlots floats.  A node without a legal move
-// has no leaves: search_wave evaluates nothing and best_1 is 0.0f.  The waves run different numbers of
-// nodes, so the node loop holds no block barrier; inside it wave_lds_sync (search_wave's) is the only
-// ordering.  One barrier after the loop publishes the array to the block, every lane sums the row
-// from it through search_row, and a second barrier keeps the next step's publishing behind that
-// sum.  No wave leaves before a barrier: a block always has a board.  Statistics are per BOARD:
-// block-uniform counters, added once by thread 0.
+// env redundantly; thread 0 stores.  The live level-one nodes are those of search_cells, in slot
+// order; wave w takes the nodes w, w + 4, ...: it builds the node (search_node), runs the unchanged
+// search_wave on it with its own 128 floats of LDS -- the leaves of the node over the wave's lanes --
+// takes best_1 = search_best_of the result, and lane 0 publishes it to the node's fixed slot in the
+// block's array of kSearchSlots floats.  A node without a legal move has no leaves: search_wave
+// evaluates nothing and best_1 is 0.0f.  The waves run different numbers of nodes, so the node loop
+// holds no block barrier; inside it wave_lds_sync (search_wave's) is the only ordering.  One barrier
+// after the loop publishes the array to the block, every lane sums the row from it through
+// search_row, and a second barrier keeps the next step's publishing behind that sum.  No wave leaves
+// before a barrier: a block always has a board.  Statistics are per BOARD: block-uniform counters,
+// added once by thread 0.
 // ---------------------------------------------------------------------------------------------
 constexpr int kSearch2Waves = kBlock / 64;
 constexpr int64_t kSearch2MaxBoards = (int64_t)0x7fffffff;   // per launch: one block per board, grid.x is a 31-bit number
-// `cells` of a board (bit 16a + j = move a is legal and cell j of c_a is empty), as search_wave forms it
-__device__ __forceinline__ u64 search2_cells(const Board& s) {
-  u64 cells = 0ull;
-#pragma unroll 1
-  for (int a = 0; a < 4; ++a) {
-    Board c = s;
-    uint32_t score;
-    if (move(c, a, score)) cells |= (u64)empty_mask(c) << (16 * a);
-  }
-  return cells;
-}
-// the fixed slot of the k-th live node (k < 2 * popcount(cells)): tile k & 1 of the (k >> 1)-th set bit
-__device__ __forceinline__ uint32_t search2_slot(u64 cells, uint32_t k) {
-  const uint32_t p0 = popc((uint32_t)cells & 0xffffu), p1 = p0 + popc((uint32_t)(cells >> 16) & 0xffffu);
-  const uint32_t p2 = p1 + popc((uint32_t)(cells >> 32) & 0xffffu);
-  const uint32_t r = k >> 1;
-  const uint32_t a = (uint32_t)(r >= p0) + (uint32_t)(r >= p1) + (uint32_t)(r >= p2);
-  const uint32_t before = a == 0u ? 0u : a == 1u ? p0 : a == 2u ? p1 : p2;
-  const uint32_t j = kth_set_bit16((uint32_t)(cells >> (16u * a)) & 0xffffu, r - before);
-  return a * 32u + j * 2u + (k & 1u);                     // < kSearchSlots: a < 4, j < 16
-}
 // the depth-2 row of the block's board.  `leaf` = this wave's kSearchSlots floats, `best1` = the block's.  Every
 // thread of the block calls it (two block barriers).
-template <int FAM>
-__device__ __forceinline__ SearchEval search2_block(const float* w, const Board& s, float* leaf, float* best1) {
+template <class EVAL>
+__device__ __forceinline__ SearchEval search2_block(const EVAL& eval, const Board& s, float* leaf, float* best1) {
   const uint32_t wave = threadIdx.x >> 6;
-  const u64 cells = search2_cells(s);
+  const u64 cells = search_cells(s);
   const uint32_t total = 2u * (uint32_t)__popcll(cells);  // <= 120
+  const SearchCounts n(cells);
 #pragma unroll 1
   for (uint32_t k = wave; k < total; k += (uint32_t)kSearch2Waves) {   // wave-uniform: no block barrier in here
-    const uint32_t slot = search2_slot(cells, k);
+    const uint32_t slot = search_slot(cells, n, k);
     Board node;
     search_node(s, slot, node);                           // (live by construction)
-    const float b = search_best_of(search_wave<FAM>(w, node, leaf));
+    const float b = search_best_of(search_wave(eval, node, leaf));
     if ((threadIdx.x & 63u) == 0u) best1[slot] = b;
   }
   __syncthreads();                                        // the level-one nodes are published before any lane sums them
@@ -2925,71 +2804,32 @@ __device__ __forceinline__ SearchEval search2_block(const float* w, const Board&
   return ev;
 }
 
-template <int FAM>
-__global__ __launch_bounds__(kBlock) void k_search2_lookup(const float* w, const uint8_t* boards, int64_t first, int64_t B,
+template <class EVAL>
+__global__ __launch_bounds__(kBlock) void k_search2_lookup(EVAL eval, const uint8_t* boards, int64_t first, int64_t B,
                                                            float* q_out, uint8_t* legal_out) {
   __shared__ float leaf[kSearch2Waves][kSearchSlots];
   __shared__ float best1[kSearchSlots];
   __shared__ Stage<4> st;
   const int64_t i = first + (int64_t)blockIdx.x;          // < B: the grid is the launch's boards
-  const SearchEval ev = search2_block<FAM>(w, load_board(boards, i, B, st), leaf[threadIdx.x >> 6], best1);
+  const SearchEval ev = search2_block(eval, load_board(boards, i, B, st), leaf[threadIdx.x >> 6], best1);
   if (threadIdx.x == 0u && i < B) {
     reinterpret_cast<float4*>(q_out)[i] = make_float4(ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3);
     legal_out[i] = (uint8_t)ev.legal;
   }
 }
 
-// k_search_play_rollout with the depth-2 row, a block per board
-template <int FAM, int ENV>
+// k_search_play_rollout with the depth-2 row: a block per board, thread 0 stores
+template <class EVAL, int ENV>
 __global__ __launch_bounds__(kBlock) void k_search2_play_rollout(
-    uint8_t* boards, q2048_aux* aux, const float* w, int64_t first, int64_t B, int steps, double eps, uint64_t seed,
+    uint8_t* boards, q2048_aux* aux, EVAL eval, int64_t first, int64_t B, int steps, double eps, uint64_t seed,
     uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
-  __shared__ BlockStats bs;
-  __shared__ Stage<4> st;
-  __shared__ LutImage lut_lds;
   __shared__ float leaf[kSearch2Waves][kSearchSlots];
   __shared__ float best1[kSearchSlots];
-  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
-  if (threadIdx.x < kLutImageDoubles)
-    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
-  stats_clear(bs);                                        // (its barrier publishes the image too)
-  const ImageLuts lut{&lut_lds};
-  const bool first_thread = threadIdx.x == 0u;
+  float* mine = leaf[threadIdx.x >> 6];
   const int64_t i = first + (int64_t)blockIdx.x;          // block-uniform, < B: the grid is the launch's boards
-  const uint64_t id = env_id0 + (uint64_t)i;
-  Board b = load_board(boards, i, B, st);
-  Aux a = ld_aux(aux, i);
-  uint32_t n_valid = 0, n_explore = 0, n_done = 0;        // of this BOARD: the same in every thread
-  double reward_sum = 0.0;
-  const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
-  const uint64_t eps_t = eps_threshold(eps);
-  for (int t = 0; t < steps; ++t) {
-    const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
-    Draws y{0u, 0u, 0u, 0u};
-    if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-    const SearchEval ev = search2_block<FAM>(w, b, leaf[threadIdx.x >> 6], best1);
-    bool explored;
-    const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
-    const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
-    if (o.done) {
-      if (first_thread) episode_stats(bs, a, o.max_log2);
-      begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
-    }
-    n_valid += o.valid != 0;
-    n_explore += explored;
-    n_done += o.done != 0;
-    reward_sum += (double)o.reward;
-  }
-  if (first_thread) {
-    store_board(boards, i, B, b, st);
-    st_aux(aux, i, a);
-    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
-    atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)steps);
-    atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
-    atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
-    atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
-  }
-  stats_flush(bs, stats_i, stats_f);
+  board_play_rollout<ENV>(boards, aux, i, true, threadIdx.x == 0u,
+                          [&](const Board& b) { return search2_block(eval, b, mine, best1); }, B, steps, eps, seed,
+                          env_id0, ctr0, stats_i, stats_f);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2999,10 +2839,8 @@ __global__ __launch_bounds__(kBlock) void k_search2_play_rollout(
 // forms anyway (16 field extracts and maxima, seven compares against the wave-uniform spec), and ONE
 // 64-bit offset (stage * 256 MiB) is added to the base before the 32 back-to-back loads -- the loads
 // themselves are NtLd's, unchanged.  The `stages` word is a kernel argument (an SGPR).  Relaxed
-// agent-scope atomic loads in the learner kernels, ordinary loads in the players.  The search has
-// kernels of its own that call search_row / search_node / search2_cells / search2_slot unchanged:
-// the spec would otherwise have to travel through search_wave<FAM> and every function built on it.
-// Kernels of their own; no existing kernel changes.
+// agent-scope atomic loads in the learner kernels, ordinary loads in the players.  The players and
+// the search are the shared kernels with NtsEvalOf, which carries the spec beside the weights.
 // ---------------------------------------------------------------------------------------------
 template <bool AGENT>
 struct NtsLdOf {
@@ -3250,235 +3088,17 @@ __global__ __launch_bounds__(kCarBlock) void k_car_commit(uint8_t* pool, u64* co
   if (threadIdx.x == 0u) counts[k] = count + m;
 }
 
-// the greedy player on the staged network (q2048_nts_play_rollout): k_nt_play_rollout with q2048_nts_lookup's row
-template <int ENV>
-__global__ __launch_bounds__(kBlock) void k_nts_play_rollout(
-    uint8_t* boards, q2048_aux* aux, const float* w, uint32_t stages, int64_t B, int steps, double eps, uint64_t seed,
-    uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
-  __shared__ BlockStats bs;
-  __shared__ Stage<4> st;
-  __shared__ LutImage lut_lds;
-  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
-  if (threadIdx.x < kLutImageDoubles)
-    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
-  stats_clear(bs);                                        // (its barrier publishes the image too)
-  const ImageLuts lut{&lut_lds};
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  Board b = load_board(boards, i, B, st);
-  if (i < B) {
-    const uint64_t id = env_id0 + (uint64_t)i;
-    Aux a = ld_aux(aux, i);
-    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
-    double reward_sum = 0.0;
-    const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
-    const uint64_t eps_t = eps_threshold(eps);
-    for (int t = 0; t < steps; ++t) {
-      const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
-      Draws y{0u, 0u, 0u, 0u};
-      if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-      const NtEval ev = nts_eval(b, stages, NtsLdOf<false>{w});
-      bool explored;
-      const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
-      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
-      if (o.done) {
-        episode_stats(bs, a, o.max_log2);
-        begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
-      }
-      n_valid += wave_count(o.valid != 0);
-      n_explore += wave_count(explored);
-      n_done += wave_count(o.done != 0);
-      reward_sum += (double)o.reward;
-    }
-    st_aux(aux, i, a);
-    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
-    const uint32_t n_active = wave_count(true);
-    if (wave_leader()) {
-      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
-      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
-      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
-      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
-    }
+// the player's and the search's evaluator (q2048_nts_play_rollout, q2048_nts_search_*): q2048_nts_lookup's row with
+// ordinary loads.  In the search every chance node and every leaf is evaluated with it, so each of ITS candidates reads
+// the table of its own stage (the spawn of a threshold tile, or a merge at either level, crosses into the next table).
+struct NtsEvalOf {
+  const float* w;
+  uint32_t stages;
+  __device__ __forceinline__ SearchEval operator()(const Board& b) const {
+    const NtEval ev = nts_eval(b, stages, NtsLdOf<false>{w});
+    return SearchEval{ev.q, ev.legal};
   }
-  store_board(boards, i, B, b, st);
-  stats_flush(bs, stats_i, stats_f);
-}
-
-// ---- the search on the staged network: search_wave / search2_block and their four kernels with the staged best.  Every
-// chance node and every leaf is evaluated with nts_eval, so each of ITS candidates reads the table of its own stage (the
-// spawn of a threshold tile, or a merge at either level, crosses into the next table).  The slots, the compaction
-// over lanes and waves, the LDS arrays and both orderings are those kernels'; see their comments.
-__device__ __forceinline__ float nts_search_best(const float* w, uint32_t stages, const Board& x) {
-  const NtEval ev = nts_eval(x, stages, NtsLdOf<false>{w});
-  return av_best(ev.legal, ev.q);
-}
-__device__ __forceinline__ SearchEval nts_search_wave(const float* w, uint32_t stages, const Board& s, float* best) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const u64 cells = search2_cells(s);
-  const uint32_t total = 2u * (uint32_t)__popcll(cells);  // <= 120
-#pragma unroll 1
-  for (uint32_t k = lane; k < total; k += 64u) {          // at most two rounds
-    const uint32_t slot = search2_slot(cells, k);         // < kSearchSlots
-    Board node;
-    if (search_node(s, slot, node)) best[slot] = nts_search_best(w, stages, node);   // (live by construction)
-  }
-  wave_lds_sync();                                        // the nodes are published before any lane sums them
-  const SearchEval ev = search_row(s, [best](uint32_t slot, const Board&) { return best[slot]; });
-  wave_lds_sync();                                        // and summed before the next step publishes again
-  return ev;
-}
-
-__global__ __launch_bounds__(kBlock) void k_nts_search_lookup(const float* w, uint32_t stages, const uint8_t* boards,
-                                                              int64_t first, int64_t B, float* q_out, uint8_t* legal_out) {
-  __shared__ float best[kSearchBoards][kSearchSlots];
-  __shared__ Stage<4> st;
-  const int wave = (int)(threadIdx.x >> 6);
-  const int64_t i = first + (int64_t)blockIdx.x * kSearchBoards + wave;
-  if (i >= B) return;                                     // (no block barrier in this kernel)
-  const SearchEval ev = nts_search_wave(w, stages, load_board(boards, i, B, st), best[wave]);
-  if ((threadIdx.x & 63u) == 0u) {
-    reinterpret_cast<float4*>(q_out)[i] = make_float4(ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3);
-    legal_out[i] = (uint8_t)ev.legal;
-  }
-}
-
-template <int ENV>
-__global__ __launch_bounds__(kBlock) void k_nts_search_play_rollout(
-    uint8_t* boards, q2048_aux* aux, const float* w, uint32_t stages, int64_t first, int64_t B, int steps, double eps,
-    uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
-  __shared__ BlockStats bs;
-  __shared__ Stage<4> st;
-  __shared__ LutImage lut_lds;
-  __shared__ float best[kSearchBoards][kSearchSlots];
-  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
-  if (threadIdx.x < kLutImageDoubles)
-    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
-  stats_clear(bs);                                        // (its barrier publishes the image too)
-  const ImageLuts lut{&lut_lds};
-  const int wave = (int)(threadIdx.x >> 6);
-  const bool first_lane = (threadIdx.x & 63u) == 0u;
-  const int64_t i = first + (int64_t)blockIdx.x * kSearchBoards + wave;   // wave-uniform
-  if (i < B) {
-    const uint64_t id = env_id0 + (uint64_t)i;
-    Board b = load_board(boards, i, B, st);
-    Aux a = ld_aux(aux, i);
-    uint32_t n_valid = 0, n_explore = 0, n_done = 0;      // of this BOARD: the same in every lane
-    double reward_sum = 0.0;
-    const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
-    const uint64_t eps_t = eps_threshold(eps);
-    for (int t = 0; t < steps; ++t) {
-      const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
-      Draws y{0u, 0u, 0u, 0u};
-      if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-      const SearchEval ev = nts_search_wave(w, stages, b, best[wave]);
-      bool explored;
-      const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
-      const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
-      if (o.done) {
-        if (first_lane) episode_stats(bs, a, o.max_log2);
-        begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
-      }
-      n_valid += o.valid != 0;
-      n_explore += explored;
-      n_done += o.done != 0;
-      reward_sum += (double)o.reward;
-    }
-    if (first_lane) {
-      store_board(boards, i, B, b, st);
-      st_aux(aux, i, a);
-      atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
-      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)steps);
-      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
-      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
-      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
-    }
-  }
-  stats_flush(bs, stats_i, stats_f);
-}
-
-// the depth-2 row of the block's board (search2_block with the staged leaves).  Every thread of the block calls it.
-__device__ __forceinline__ SearchEval nts_search2_block(const float* w, uint32_t stages, const Board& s, float* leaf,
-                                                        float* best1) {
-  const uint32_t wave = threadIdx.x >> 6;
-  const u64 cells = search2_cells(s);
-  const uint32_t total = 2u * (uint32_t)__popcll(cells);  // <= 120
-#pragma unroll 1
-  for (uint32_t k = wave; k < total; k += (uint32_t)kSearch2Waves) {   // wave-uniform: no block barrier in here
-    const uint32_t slot = search2_slot(cells, k);
-    Board node;
-    search_node(s, slot, node);                           // (live by construction)
-    const float b = search_best_of(nts_search_wave(w, stages, node, leaf));
-    if ((threadIdx.x & 63u) == 0u) best1[slot] = b;
-  }
-  __syncthreads();                                        // the level-one nodes are published before any lane sums them
-  const SearchEval ev = search_row(s, [best1](uint32_t slot, const Board&) { return best1[slot]; });
-  __syncthreads();                                        // and summed before the next step publishes again
-  return ev;
-}
-
-__global__ __launch_bounds__(kBlock) void k_nts_search2_lookup(const float* w, uint32_t stages, const uint8_t* boards,
-                                                               int64_t first, int64_t B, float* q_out, uint8_t* legal_out) {
-  __shared__ float leaf[kSearch2Waves][kSearchSlots];
-  __shared__ float best1[kSearchSlots];
-  __shared__ Stage<4> st;
-  const int64_t i = first + (int64_t)blockIdx.x;          // < B: the grid is the launch's boards
-  const SearchEval ev = nts_search2_block(w, stages, load_board(boards, i, B, st), leaf[threadIdx.x >> 6], best1);
-  if (threadIdx.x == 0u && i < B) {
-    reinterpret_cast<float4*>(q_out)[i] = make_float4(ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3);
-    legal_out[i] = (uint8_t)ev.legal;
-  }
-}
-
-template <int ENV>
-__global__ __launch_bounds__(kBlock) void k_nts_search2_play_rollout(
-    uint8_t* boards, q2048_aux* aux, const float* w, uint32_t stages, int64_t first, int64_t B, int steps, double eps,
-    uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f) {
-  __shared__ BlockStats bs;
-  __shared__ Stage<4> st;
-  __shared__ LutImage lut_lds;
-  __shared__ float leaf[kSearch2Waves][kSearchSlots];
-  __shared__ float best1[kSearchSlots];
-  static_assert(kBlock >= kLutImageDoubles, "one double of the image per thread");
-  if (threadIdx.x < kLutImageDoubles)
-    reinterpret_cast<double*>(&lut_lds)[threadIdx.x] = reinterpret_cast<const double*>(&g_lut_image)[threadIdx.x];
-  stats_clear(bs);                                        // (its barrier publishes the image too)
-  const ImageLuts lut{&lut_lds};
-  const bool first_thread = threadIdx.x == 0u;
-  const int64_t i = first + (int64_t)blockIdx.x;          // block-uniform, < B: the grid is the launch's boards
-  const uint64_t id = env_id0 + (uint64_t)i;
-  Board b = load_board(boards, i, B, st);
-  Aux a = ld_aux(aux, i);
-  uint32_t n_valid = 0, n_explore = 0, n_done = 0;        // of this BOARD: the same in every thread
-  double reward_sum = 0.0;
-  const DrawPrep prep_x = draws_prepare(seed, id, kStreamStep);
-  const uint64_t eps_t = eps_threshold(eps);
-  for (int t = 0; t < steps; ++t) {
-    const Draws x = draws_at(prep_x, ctr0 + (uint32_t)t);
-    Draws y{0u, 0u, 0u, 0u};
-    if constexpr ((ENV & kEnvDqn) != 0) y = draws(seed, id, ctr0 + (uint32_t)t, kStreamOver);
-    const SearchEval ev = nts_search2_block(w, stages, b, leaf[threadIdx.x >> 6], best1);
-    bool explored;
-    const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
-    const StepOut o = env_step_profile<ENV>(b, a, act, x.x2, x.x3, y.x0, y.x1, lut);
-    if (o.done) {
-      if (first_thread) episode_stats(bs, a, o.max_log2);
-      begin_episode(b, a, seed, id, (ENV & kEnvResetShaping) != 0);
-    }
-    n_valid += o.valid != 0;
-    n_explore += explored;
-    n_done += o.done != 0;
-    reward_sum += (double)o.reward;
-  }
-  if (first_thread) {
-    store_board(boards, i, B, b, st);
-    st_aux(aux, i, a);
-    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
-    atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)steps);
-    atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
-    atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
-    atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
-  }
-  stats_flush(bs, stats_i, stats_f);
-}
+};
 
 // ---- promotion (q2048_nts_promote): one streaming pass over two stage tables, 2^24 groups of four entries each.  A lane
 // takes kPromoteGroups groups, a block's lanes on consecutive groups: 16-byte loads of the destination and of the source
@@ -3926,6 +3546,69 @@ inline int fused_mode(uint32_t flags, int n, const void* side) {   // play-only 
   const bool frozen = (flags & Q2048_FLAG_NO_NEW_ROWS) != 0u;
   return sym | ((flags & Q2048_FLAG_TD_CAS) ? kModeCas : kModeLearn) | (frozen ? kModeFrozen : 0) |
          ((frozen && (n == 4 || side != nullptr) && (flags & Q2048_FLAG_LINE_SUMMARY)) ? kModeSummary : 0);   // (5x5: only with a side array)
+}
+// the players on weights: calls f(std::integral_constant<int, ENV>), ENV = the env profile bits of `flags`
+template <class F>
+void with_env_profile(uint32_t flags, F&& f) {
+  switch (env_bits(flags) & 3) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+  }
+}
+// q2048_{rt,lt,av,nt,nts}_play_rollout behind their argument checks
+template <class EVAL>
+int eval_play_launch(EVAL eval, uint8_t* boards, q2048_aux* aux, int64_t B, int64_t steps, double eps, uint64_t seed,
+                     uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i, double* stats_f, void* stream) {
+  if (B == 0 || steps == 0) return Q2048_OK;
+  with_env_profile(flags, [&](auto env) {
+    hipLaunchKernelGGL((k_eval_play_rollout<EVAL, decltype(env)::value>), dim3(grid_for(B)), dim3(kBlock), 0,
+                       (hipStream_t)stream, boards, aux, eval, B, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);
+  });
+  return launch_status();
+}
+// The search at a depth the caller has checked.  Depth 1 is a block per kSearchBoards boards, depth 2 a block per board,
+// and grid.x is a 31-bit number: a batch beyond kSearchMaxBoards / kSearch2MaxBoards takes more than one launch.
+// launch(grid, first, end): the boards of a launch are [first, end).
+template <class Launch>
+int search_launches(int64_t B, int depth, const Launch& launch) {
+  const int64_t per_block = depth == 1 ? kSearchBoards : 1;
+  const int64_t cap = depth == 1 ? kSearchMaxBoards : kSearch2MaxBoards;
+  for (int64_t first = 0; first < B; first += cap) {
+    const int64_t n = B - first < cap ? B - first : cap;
+    launch(dim3((unsigned)((n + per_block - 1) / per_block)), first, first + n);
+  }
+  return launch_status();
+}
+template <class EVAL>
+int search_lookup_launch(EVAL eval, int depth, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out,
+                         void* stream) {
+  if (B == 0) return Q2048_OK;
+  return search_launches(B, depth, [&](dim3 grid, int64_t first, int64_t end) {
+    if (depth == 1)
+      hipLaunchKernelGGL((k_search_lookup<EVAL>), grid, dim3(kBlock), 0, (hipStream_t)stream, eval, boards, first, end,
+                         q_out, legal_out);
+    else
+      hipLaunchKernelGGL((k_search2_lookup<EVAL>), grid, dim3(kBlock), 0, (hipStream_t)stream, eval, boards, first, end,
+                         q_out, legal_out);
+  });
+}
+template <class EVAL>
+int search_play_launch(EVAL eval, int depth, uint8_t* boards, q2048_aux* aux, int64_t B, int64_t steps, double eps,
+                       uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i, double* stats_f,
+                       void* stream) {
+  if (B == 0 || steps == 0) return Q2048_OK;
+  return search_launches(B, depth, [&](dim3 grid, int64_t first, int64_t end) {
+    with_env_profile(flags, [&](auto env) {
+      if (depth == 1)
+        hipLaunchKernelGGL((k_search_play_rollout<EVAL, decltype(env)::value>), grid, dim3(kBlock), 0, (hipStream_t)stream,
+                           boards, aux, eval, first, end, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);
+      else
+        hipLaunchKernelGGL((k_search2_play_rollout<EVAL, decltype(env)::value>), grid, dim3(kBlock), 0, (hipStream_t)stream,
+                           boards, aux, eval, first, end, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);
+    });
+  });
 }
 // merge, fold and unfold: `mode` / `fold` as a compile-time constant (f gets a std::integral_constant), and the one
 // launch they share -- a grid-stride pass over src in the growth's grid (8 blocks of 4 waves per CU)
@@ -4492,15 +4175,7 @@ int q2048_rt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights,
                           uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                           double* stats_f, uint32_t* status, void* stream) {
   if (int e = check_rt_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
-  if (B == 0 || steps == 0) return Q2048_OK;
-#define Q2048_LAUNCH_RT_PLAY(E)                                                                                    \
-  case E:                                                                                                          \
-    hipLaunchKernelGGL((k_rt_play_rollout<E>), dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, boards,    \
-                       aux, weights, B, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);                   \
-    break;
-  switch (env_bits(flags) & 3) { Q2048_LAUNCH_RT_PLAY(0) Q2048_LAUNCH_RT_PLAY(1) Q2048_LAUNCH_RT_PLAY(2) Q2048_LAUNCH_RT_PLAY(3) }
-#undef Q2048_LAUNCH_RT_PLAY
-  return launch_status();
+  return eval_play_launch(RtEvalOf{weights}, boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, stream);
 }
 
 int q2048_lt_choose(const float* weights, const uint8_t* boards, int64_t B, double eps, uint64_t seed,
@@ -4546,15 +4221,7 @@ int q2048_lt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights,
                           uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                           double* stats_f, uint32_t* status, void* stream) {
   if (int e = check_rt_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
-  if (B == 0 || steps == 0) return Q2048_OK;
-#define Q2048_LAUNCH_LT_PLAY(E)                                                                                    \
-  case E:                                                                                                          \
-    hipLaunchKernelGGL((k_lt_play_rollout<E>), dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, boards,    \
-                       aux, weights, B, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);                   \
-    break;
-  switch (env_bits(flags) & 3) { Q2048_LAUNCH_LT_PLAY(0) Q2048_LAUNCH_LT_PLAY(1) Q2048_LAUNCH_LT_PLAY(2) Q2048_LAUNCH_LT_PLAY(3) }
-#undef Q2048_LAUNCH_LT_PLAY
-  return launch_status();
+  return eval_play_launch(LtEvalOf{weights}, boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, stream);
 }
 
 int q2048_av_value(const float* weights, const uint8_t* boards, int64_t B, float* v_out, void* stream) {
@@ -4605,15 +4272,7 @@ int q2048_av_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights,
                           uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                           double* stats_f, uint32_t* status, void* stream) {
   if (int e = check_av_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
-  if (B == 0 || steps == 0) return Q2048_OK;
-#define Q2048_LAUNCH_AV_PLAY(E)                                                                                    \
-  case E:                                                                                                          \
-    hipLaunchKernelGGL((k_av_play_rollout<E>), dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, boards,    \
-                       aux, weights, B, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);                   \
-    break;
-  switch (env_bits(flags) & 3) { Q2048_LAUNCH_AV_PLAY(0) Q2048_LAUNCH_AV_PLAY(1) Q2048_LAUNCH_AV_PLAY(2) Q2048_LAUNCH_AV_PLAY(3) }
-#undef Q2048_LAUNCH_AV_PLAY
-  return launch_status();
+  return eval_play_launch(AvEvalOf{weights}, boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, stream);
 }
 
 int q2048_nt_value(const float* weights, const uint8_t* boards, int64_t B, float* v_out, void* stream) {
@@ -4686,138 +4345,57 @@ int q2048_nt_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights,
                           uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                           double* stats_f, uint32_t* status, void* stream) {
   if (int e = check_nt_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
-  if (B == 0 || steps == 0) return Q2048_OK;
-#define Q2048_LAUNCH_NT_PLAY(E)                                                                                    \
-  case E:                                                                                                          \
-    hipLaunchKernelGGL((k_nt_play_rollout<E>), dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, boards,    \
-                       aux, weights, B, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);                   \
-    break;
-  switch (env_bits(flags) & 3) { Q2048_LAUNCH_NT_PLAY(0) Q2048_LAUNCH_NT_PLAY(1) Q2048_LAUNCH_NT_PLAY(2) Q2048_LAUNCH_NT_PLAY(3) }
-#undef Q2048_LAUNCH_NT_PLAY
-  return launch_status();
+  return eval_play_launch(NtEvalOf{weights}, boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, stream);
 }
 
-// One-level expectimax: a block per kSearchBoards boards, so a batch beyond kSearchMaxBoards takes more than one launch
-// (the boards of a launch are [first, min(first + kSearchMaxBoards, B))).
-extern "C++" {
-template <int FAM>
-static int search_lookup_impl(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out,
-                              void* stream) {
-  if (int e = check_search_lookup(weights, boards, B, q_out, legal_out)) return e;
-  if (B == 0) return Q2048_OK;
-  for (int64_t first = 0; first < B; first += kSearchMaxBoards) {
-    const int64_t n = B - first < kSearchMaxBoards ? B - first : kSearchMaxBoards;
-    hipLaunchKernelGGL((k_search_lookup<FAM>), dim3((unsigned)((n + kSearchBoards - 1) / kSearchBoards)), dim3(kBlock), 0,
-                       (hipStream_t)stream, weights, boards, first, first + n, q_out, legal_out);
-  }
-  return launch_status();
-}
-template <int FAM>
-static int search_play_impl(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
-                            uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
-                            double* stats_f, uint32_t* status, void* stream) {
-  if (int e = check_search_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
-  if (B == 0 || steps == 0) return Q2048_OK;
-#define Q2048_LAUNCH_SEARCH_PLAY(E)                                                                                \
-  case E:                                                                                                          \
-    hipLaunchKernelGGL((k_search_play_rollout<FAM, E>), grid, dim3(kBlock), 0, (hipStream_t)stream, boards, aux,   \
-                       weights, first, first + n, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);         \
-    break;
-  for (int64_t first = 0; first < B; first += kSearchMaxBoards) {
-    const int64_t n = B - first < kSearchMaxBoards ? B - first : kSearchMaxBoards;
-    const dim3 grid((unsigned)((n + kSearchBoards - 1) / kSearchBoards));
-    switch (env_bits(flags) & 3) {
-      Q2048_LAUNCH_SEARCH_PLAY(0) Q2048_LAUNCH_SEARCH_PLAY(1) Q2048_LAUNCH_SEARCH_PLAY(2) Q2048_LAUNCH_SEARCH_PLAY(3)
-    }
-  }
-#undef Q2048_LAUNCH_SEARCH_PLAY
-  return launch_status();
-}
-// Two-level expectimax: a block per board, so a batch beyond kSearch2MaxBoards takes more than one launch.  The callers
-// have checked the arguments.
-template <int FAM>
-static int search2_lookup_impl(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out,
-                               void* stream) {
-  if (B == 0) return Q2048_OK;
-  for (int64_t first = 0; first < B; first += kSearch2MaxBoards) {
-    const int64_t n = B - first < kSearch2MaxBoards ? B - first : kSearch2MaxBoards;
-    hipLaunchKernelGGL((k_search2_lookup<FAM>), dim3((unsigned)n), dim3(kBlock), 0, (hipStream_t)stream, weights, boards,
-                       first, first + n, q_out, legal_out);
-  }
-  return launch_status();
-}
-template <int FAM>
-static int search2_play_impl(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
-                             uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
-                             double* stats_f, void* stream) {
-  if (B == 0 || steps == 0) return Q2048_OK;
-#define Q2048_LAUNCH_SEARCH2_PLAY(E)                                                                               \
-  case E:                                                                                                          \
-    hipLaunchKernelGGL((k_search2_play_rollout<FAM, E>), grid, dim3(kBlock), 0, (hipStream_t)stream, boards, aux,  \
-                       weights, first, first + n, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);         \
-    break;
-  for (int64_t first = 0; first < B; first += kSearch2MaxBoards) {
-    const int64_t n = B - first < kSearch2MaxBoards ? B - first : kSearch2MaxBoards;
-    const dim3 grid((unsigned)n);
-    switch (env_bits(flags) & 3) {
-      Q2048_LAUNCH_SEARCH2_PLAY(0) Q2048_LAUNCH_SEARCH2_PLAY(1) Q2048_LAUNCH_SEARCH2_PLAY(2) Q2048_LAUNCH_SEARCH2_PLAY(3)
-    }
-  }
-#undef Q2048_LAUNCH_SEARCH2_PLAY
-  return launch_status();
-}
-template <int FAM>
-static int search_lookup_depth(const float* weights, const uint8_t* boards, int64_t B, int depth, float* q_out,
-                               uint8_t* legal_out, void* stream) {
-  if (int e = check_search_lookup_depth(weights, boards, B, depth, q_out, legal_out)) return e;
-  if (depth == 1) return search_lookup_impl<FAM>(weights, boards, B, q_out, legal_out, stream);
-  return search2_lookup_impl<FAM>(weights, boards, B, q_out, legal_out, stream);
-}
-template <int FAM>
-static int search_play_depth(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, int depth,
-                             double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
-                             double* stats_f, uint32_t* status, void* stream) {
-  if (int e = check_search_play_depth(boards, aux, weights, B, steps, depth, eps, flags, status)) return e;
-  if (depth == 1)
-    return search_play_impl<FAM>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status, stream);
-  return search2_play_impl<FAM>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, stream);
-}
-}  // extern "C++"
+// the search (search_lookup_launch, search_play_launch: one launch per chunk of the batch)
 int q2048_av_search_lookup_depth(const float* weights, const uint8_t* boards, int64_t B, int depth, float* q_out,
                                  uint8_t* legal_out, void* stream) {
-  return search_lookup_depth<kFamAv>(weights, boards, B, depth, q_out, legal_out, stream);
+  if (int e = check_search_lookup_depth(weights, boards, B, depth, q_out, legal_out)) return e;
+  return search_lookup_launch(AvEvalOf{weights}, depth, boards, B, q_out, legal_out, stream);
 }
 int q2048_av_search_play_rollout_depth(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps,
                                        int depth, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
                                        int64_t* stats_i, double* stats_f, uint32_t* status, void* stream) {
-  return search_play_depth<kFamAv>(boards, aux, weights, B, steps, depth, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status, stream);
-}
-int q2048_nt_search_lookup_depth(const float* weights, const uint8_t* boards, int64_t B, int depth, float* q_out,
-                                 uint8_t* legal_out, void* stream) {
-  return search_lookup_depth<kFamNt>(weights, boards, B, depth, q_out, legal_out, stream);
-}
-int q2048_nt_search_play_rollout_depth(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps,
-                                       int depth, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
-                                       int64_t* stats_i, double* stats_f, uint32_t* status, void* stream) {
-  return search_play_depth<kFamNt>(boards, aux, weights, B, steps, depth, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status, stream);
+  if (int e = check_search_play_depth(boards, aux, weights, B, steps, depth, eps, flags, status)) return e;
+  return search_play_launch(AvEvalOf{weights}, depth, boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f,
+                            stream);
 }
 int q2048_av_search_lookup(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out,
                            void* stream) {
-  return search_lookup_impl<kFamAv>(weights, boards, B, q_out, legal_out, stream);
+  if (int e = check_search_lookup(weights, boards, B, q_out, legal_out)) return e;
+  return search_lookup_launch(AvEvalOf{weights}, 1, boards, B, q_out, legal_out, stream);
 }
 int q2048_av_search_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
                                  uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                                  double* stats_f, uint32_t* status, void* stream) {
-  return search_play_impl<kFamAv>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status, stream);
+  if (int e = check_search_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
+  return search_play_launch(AvEvalOf{weights}, 1, boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f,
+                            stream);
+}
+int q2048_nt_search_lookup_depth(const float* weights, const uint8_t* boards, int64_t B, int depth, float* q_out,
+                                 uint8_t* legal_out, void* stream) {
+  if (int e = check_search_lookup_depth(weights, boards, B, depth, q_out, legal_out)) return e;
+  return search_lookup_launch(NtEvalOf{weights}, depth, boards, B, q_out, legal_out, stream);
+}
+int q2048_nt_search_play_rollout_depth(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps,
+                                       int depth, double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags,
+                                       int64_t* stats_i, double* stats_f, uint32_t* status, void* stream) {
+  if (int e = check_search_play_depth(boards, aux, weights, B, steps, depth, eps, flags, status)) return e;
+  return search_play_launch(NtEvalOf{weights}, depth, boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f,
+                            stream);
 }
 int q2048_nt_search_lookup(const float* weights, const uint8_t* boards, int64_t B, float* q_out, uint8_t* legal_out,
                            void* stream) {
-  return search_lookup_impl<kFamNt>(weights, boards, B, q_out, legal_out, stream);
+  if (int e = check_search_lookup(weights, boards, B, q_out, legal_out)) return e;
+  return search_lookup_launch(NtEvalOf{weights}, 1, boards, B, q_out, legal_out, stream);
 }
 int q2048_nt_search_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights, int64_t B, int64_t steps, double eps,
                                  uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                                  double* stats_f, uint32_t* status, void* stream) {
-  return search_play_impl<kFamNt>(boards, aux, weights, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f, status, stream);
+  if (int e = check_search_play(boards, aux, weights, B, steps, eps, flags, status)) return e;
+  return search_play_launch(NtEvalOf{weights}, 1, boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f,
+                            stream);
 }
 
 // ---- the staged network: the q2048_nt_* entry points with `stages` directly after `weights` ----
@@ -4885,58 +4463,21 @@ int q2048_nts_play_rollout(uint8_t* boards, q2048_aux* aux, const float* weights
                            double eps, uint64_t seed, uint64_t env_id0, uint32_t ctr0, uint32_t flags, int64_t* stats_i,
                            double* stats_f, uint32_t* status, void* stream) {
   if (int e = check_nts_play(boards, aux, weights, stages, B, steps, eps, flags, status)) return e;
-  if (B == 0 || steps == 0) return Q2048_OK;
-#define Q2048_LAUNCH_NTS_PLAY(E)                                                                                   \
-  case E:                                                                                                          \
-    hipLaunchKernelGGL((k_nts_play_rollout<E>), dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, boards,   \
-                       aux, weights, stages, B, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f);           \
-    break;
-  switch (env_bits(flags) & 3) { Q2048_LAUNCH_NTS_PLAY(0) Q2048_LAUNCH_NTS_PLAY(1) Q2048_LAUNCH_NTS_PLAY(2) Q2048_LAUNCH_NTS_PLAY(3) }
-#undef Q2048_LAUNCH_NTS_PLAY
-  return launch_status();
+  return eval_play_launch(NtsEvalOf{weights, stages}, boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i, stats_f,
+                          stream);
 }
 int q2048_nts_search_lookup_depth(const float* weights, uint32_t stages, const uint8_t* boards, int64_t B, int depth,
                                   float* q_out, uint8_t* legal_out, void* stream) {
   if (int e = check_nts_search_lookup_depth(weights, stages, boards, B, depth, q_out, legal_out)) return e;
-  if (B == 0) return Q2048_OK;
-  const int64_t cap = depth == 1 ? kSearchMaxBoards : kSearch2MaxBoards;   // boards per launch
-  for (int64_t first = 0; first < B; first += cap) {
-    const int64_t n = B - first < cap ? B - first : cap;
-    if (depth == 1)
-      hipLaunchKernelGGL(k_nts_search_lookup, dim3((unsigned)((n + kSearchBoards - 1) / kSearchBoards)), dim3(kBlock), 0,
-                         (hipStream_t)stream, weights, stages, boards, first, first + n, q_out, legal_out);
-    else
-      hipLaunchKernelGGL(k_nts_search2_lookup, dim3((unsigned)n), dim3(kBlock), 0, (hipStream_t)stream, weights, stages,
-                         boards, first, first + n, q_out, legal_out);
-  }
-  return launch_status();
+  return search_lookup_launch(NtsEvalOf{weights, stages}, depth, boards, B, q_out, legal_out, stream);
 }
 int q2048_nts_search_play_rollout_depth(uint8_t* boards, q2048_aux* aux, const float* weights, uint32_t stages, int64_t B,
                                         int64_t steps, int depth, double eps, uint64_t seed, uint64_t env_id0,
                                         uint32_t ctr0, uint32_t flags, int64_t* stats_i, double* stats_f,
                                         uint32_t* status, void* stream) {
   if (int e = check_nts_search_play_depth(boards, aux, weights, stages, B, steps, depth, eps, flags, status)) return e;
-  if (B == 0 || steps == 0) return Q2048_OK;
-#define Q2048_LAUNCH_NTS_SEARCH_PLAY(E)                                                                            \
-  case E:                                                                                                          \
-    if (depth == 1)                                                                                                \
-      hipLaunchKernelGGL((k_nts_search_play_rollout<E>), grid, dim3(kBlock), 0, (hipStream_t)stream, boards, aux,  \
-                         weights, stages, first, first + n, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f); \
-    else                                                                                                           \
-      hipLaunchKernelGGL((k_nts_search2_play_rollout<E>), grid, dim3(kBlock), 0, (hipStream_t)stream, boards, aux, \
-                         weights, stages, first, first + n, (int)steps, eps, seed, env_id0, ctr0, stats_i, stats_f); \
-    break;
-  const int64_t cap = depth == 1 ? kSearchMaxBoards : kSearch2MaxBoards;   // boards per launch
-  for (int64_t first = 0; first < B; first += cap) {
-    const int64_t n = B - first < cap ? B - first : cap;
-    const dim3 grid((unsigned)(depth == 1 ? (n + kSearchBoards - 1) / kSearchBoards : n));
-    switch (env_bits(flags) & 3) {
-      Q2048_LAUNCH_NTS_SEARCH_PLAY(0) Q2048_LAUNCH_NTS_SEARCH_PLAY(1) Q2048_LAUNCH_NTS_SEARCH_PLAY(2)
-      Q2048_LAUNCH_NTS_SEARCH_PLAY(3)
-    }
-  }
-#undef Q2048_LAUNCH_NTS_SEARCH_PLAY
-  return launch_status();
+  return search_play_launch(NtsEvalOf{weights, stages}, depth, boards, aux, B, steps, eps, seed, env_id0, ctr0, flags, stats_i,
+                            stats_f, stream);
 }
 int q2048_nts_promote(float* weights, uint32_t stages, int from, int to, int64_t* count_out, void* stream) {
   if (int e = check_nts_promote(weights, stages, from, to)) return e;

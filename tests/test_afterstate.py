@@ -10,7 +10,7 @@ Which test executes which kernel (device) / function (CPU twin):
   k_av_update         test_update_where_lanes_cannot_race
   k_av_fused_rollout  test_fused_rollout_with_frozen_weights, test_fused_rollout_one_lane_many_steps (the carried-entry
                       rule), test_fused_rollout_one_learning_step, test_racing_learning_at_65536_boards_properties
-  k_av_play_rollout   test_player_equals_the_four_call_loop, test_player_exploration_against_a_model
+  k_eval_play_rollout<AvEvalOf, E>   test_player_equals_the_four_call_loop, test_player_exploration_against_a_model
   the argument checks test_abi, test_argument_errors_need_no_device, test_refused_calls_write_nothing
 
 The model (model_idx of the line-tuple test, model_v, model_eval, model_best, model_update) is plain numpy, takes the move

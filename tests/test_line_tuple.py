@@ -8,7 +8,7 @@ Which test executes which kernel (device) / function (CPU twin):
   k_lt_update         test_update_on_entries_that_cannot_race
   k_lt_fused_rollout  test_fused_rollout_with_frozen_weights, test_fused_rollout_one_lane_many_steps (the carried-entry rule,
                       per feature), test_fused_rollout_one_learning_step (lt_scatter inside the fused loop)
-  k_lt_play_rollout   test_player_equals_the_four_call_loop, test_player_exploration_against_a_model
+  k_eval_play_rollout<LtEvalOf, E>   test_player_equals_the_four_call_loop, test_player_exploration_against_a_model
   the argument checks test_abi, test_argument_errors_need_no_device
 
 The model (model_idx, model_q, model_update) is plain numpy and shares no code with csrc/; there is no oracle for this

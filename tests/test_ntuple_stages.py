@@ -8,9 +8,10 @@ Which test executes which kernel (device) / function (CPU twin):
   k_nts_update                              test_update_where_lanes_cannot_race, the loop of test_one_lane_300_steps
   k_nts_fused_rollout                       test_fused_one_learning_step, test_one_lane_300_steps,
                                             test_racing_learning_at_65536_boards_properties
-  k_nts_play_rollout                        test_player_equals_the_four_call_loop, test_player_exploration_against_the_model
-  k_nts_search_lookup / k_nts_search2_lookup          test_search_rows, test_search_batch_edges
-  k_nts_search_play_rollout / k_nts_search2_play_rollout   test_searched_player_against_the_model
+  k_eval_play_rollout<NtsEvalOf, E>         test_player_equals_the_four_call_loop, test_player_exploration_against_the_model
+  k_search_lookup<NtsEvalOf> / k_search2_lookup<NtsEvalOf>   test_search_rows, test_search_batch_edges
+  k_search_play_rollout<NtsEvalOf, E> / k_search2_play_rollout<NtsEvalOf, E>   test_searched_player_against_the_model (E = 0;
+                                            E = 0..3: test_search_depth.test_searched_player_equals_the_four_call_loop)
   k_nts_promote                             test_promotion, test_promotion_cascade
   the argument checks                       test_abi, test_malformed_specs_and_argument_errors, test_refused_calls_write_nothing
 

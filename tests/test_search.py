@@ -3,10 +3,11 @@ q2048_{av,nt}_search_play_rollout against a numpy model, and the agents' `search
 (The scripts: test_search_scripts.py.)
 
 Which test executes which kernel (device) / function (CPU twin):
-  k_search_lookup<av|nt>            test_crafted_boards, test_searched_and_greedy_choices_differ, test_batch_edges,
+  k_search_lookup<AvEvalOf|NtEvalOf>   test_crafted_boards, test_searched_and_greedy_choices_differ, test_batch_edges,
                                     test_device_equals_twin, test_python_surface
-  k_search_play_rollout<av|nt, E>   test_player_against_the_model (E = 0..3 on the afterstate family, 0 and 1 on the
-                                    network), test_python_surface
+  k_search_play_rollout<AvEvalOf|NtEvalOf, E>   test_player_against_the_model (E = 0..3 on the afterstate family, 0 and
+                                    1 on the network), test_python_surface; E = 0..3 on both:
+                                    test_search_depth.test_searched_player_equals_the_four_call_loop
   the argument checks               test_abi, test_argument_errors_need_no_device, test_refused_calls_write_nothing
 
 The model (model_search) is plain numpy: the afterstates come from the oracle's move (test_afterstate.model_moves), the

@@ -3,10 +3,12 @@ q2048_{av,nt}_search_play_rollout_depth against a numpy model, and the agents' `
 `search_rollout(depth=)`.  (The scripts: test_search_depth_scripts.py.)
 
 Which test executes which kernel (device) / function (CPU twin):
-  k_search2_lookup<av|nt>           test_crafted_boards, test_depths_disagree, test_batch_edges, test_device_equals_twin,
+  k_search2_lookup<AvEvalOf|NtEvalOf>   test_crafted_boards, test_depths_disagree, test_batch_edges, test_device_equals_twin,
                                     test_python_surface
-  k_search2_play_rollout<av|nt, E>  test_player_against_the_model (E = 0..3 on the afterstate family, 0 and 1 on the
-                                    network), test_player_device_equals_twin, test_python_surface
+  k_search2_play_rollout<AvEvalOf|NtEvalOf, E>   test_player_against_the_model (E = 0..3 on the afterstate family, 0 and
+                                    1 on the network), test_player_device_equals_twin, test_python_surface
+  k_search_play_rollout<EVAL, E> and k_search2_play_rollout<EVAL, E>, EVAL = AvEvalOf, NtEvalOf, NtsEvalOf, E = 0..3
+                                    test_searched_player_equals_the_four_call_loop
   depth 1 through the new entries   test_depth_one_is_the_existing_lookup, test_depth_one_is_the_existing_player
   the argument checks               test_abi, test_argument_errors_need_no_device, test_refused_calls_write_nothing
 
@@ -516,3 +518,61 @@ def test_python_surface(pkg, O, dev, fam, monkeypatch):
     with pytest.raises(ValueError):
         agent.search_rollout(pkg.BatchedGame2048Env(8, 5, dev, agent.seed, agent.env_id0), 1, depth=2)
     assert_base_unwritten(fam, dev, "the surface wrote to the weights")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 9. every searched player, every env profile: the rollout against the four-call loop
+# ---------------------------------------------------------------------------------------------------------------
+LOOP_B, STAGE_TILES = 5, (32, 128)
+LOOP_CASES = [(fam, depth, profile, rss) for fam in ("av", "nt", "nts") for depth in (1, 2)
+              for profile, rss in (("shaped", False), ("shaped", True), ("nopenalty", False), ("nopenalty", True))]
+
+
+class SearchedRows:
+    """What P.four_call_loop asks of an agent, with the searched row as the row: q_values = search_lookup(depth)[0]."""
+
+    def __init__(self, agent, depth):
+        self.agent, self.depth = agent, depth
+
+    def q_values(self, boards):
+        return self.agent.search_lookup(boards, depth=self.depth)[0]
+
+    def stats(self):
+        return self.agent.stats()
+
+
+def searched_agent(pkg, fam, dev):
+    """-> (agent on weights that are only read, the assertion that they still are).  "nts": the staged network with
+    tiles (32, 128) on test_ntuple_stages' three tables (that module imports this one, hence the import here)."""
+    if fam != "nts":
+        return random_agent(pkg, fam, dev), lambda what: assert_base_unwritten(fam, dev, what)
+    import test_ntuple_stages as ST
+    agent = ST.make_agent(pkg, dev, STAGE_TILES, weights=ST.tables_on(dev, 3))
+    return agent, lambda what: ST.assert_tables_unwritten(dev, 3, what)
+
+
+@pytest.mark.parametrize("dev", DEVICES)
+@pytest.mark.parametrize("fam,depth,profile,rss", LOOP_CASES)
+def test_searched_player_equals_the_four_call_loop(pkg, dev, fam, depth, profile, rss):
+    """B = 5 crowded boards (one dead board in front; a second block with one live wave at depth 1, five blocks at
+    depth 2), epsilon 0, 24 steps by search_rollout in launches of 1 + 7 + 16 and by the four-call loop on a twin env:
+    the search LOOKUP for the row, q2048_legal_moves, the env's own step and reset -- no player kernel.  Both families
+    and the staged network, both depths, all four env profiles: boards, aux, the statistics; nothing explored; the
+    weights are not written."""
+    start, dead = AV.midgame_env(pkg, "cpu", LOOP_B, profile, rss, dead=1)
+    env = S.env_from(pkg, dev, LOOP_B, profile, rss, start.state_dict())
+    env_loop = P.twin_of(pkg, env)
+    agent, assert_unwritten = searched_agent(pkg, fam, dev)
+    for c in CUTS:
+        agent.search_rollout(env, c, depth=depth)
+    st_loop = P.four_call_loop(SearchedRows(agent, depth), env_loop, STEPS)
+    P.sync(dev)
+    st = agent.play_stats()
+    assert torch.equal(env.boards, env_loop.boards), "boards differ"
+    assert torch.equal(env.aux, env_loop.aux), "aux records differ"
+    assert env.ctr == env_loop.ctr == P.WARM + STEPS
+    assert st["steps"] == st_loop["steps"] == LOOP_B * STEPS and st["valid_moves"] == st_loop["valid_moves"]
+    assert st["episodes"] == st_loop["episodes"] >= dead == 1, "the span must cover the reset path"
+    assert st["max_tile_hist"] == st_loop["max_tile_hist"]
+    assert st["explored"] == 0
+    assert_unwritten("the player wrote to the weights")
