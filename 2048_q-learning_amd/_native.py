@@ -267,6 +267,17 @@ _SIGNATURES = {
     "q2048_nt_tc_fused_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                             C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_uint64,
                                             C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # TD(lambda): q2048_nt_choose with `explored`; the learner's lists with `trace` after the weights, `cut` after
+    # `done`, and lambda and h after gamma
+    "q2048_nt_choose_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_uint64, C.c_uint64,
+                                     C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "q2048_nt_lambda_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int,
+                                         C.c_void_p, C.c_void_p]),
+    "q2048_nt_lambda_fused_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                                C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64,
+                                                C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]),
     "q2048_nt_play_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double,
                                         C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),

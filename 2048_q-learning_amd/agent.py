@@ -1918,15 +1918,38 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
     `fused_rollout`.  An "episode" of the statistics may then be a spliced game.  The four-call API, the players, the
     search and `promote()` are untouched.  The checkpoint keeps its kind and carries "carousel": {"pool", "counts"};
     a carousel agent loads a file without it (an empty pool), a plain staged agent ignores it, another P or S is
-    refused."""
+    refused.
+
+    `trace_lambda=0.5` makes the learner TD(lambda) WITH A TRUNCATED TRACE (q2048_nt_lambda_*): the TD error of a step
+    also moves the last `trace_depth` (0..3) afterstates the lane learned on in the current episode, the k-th of them by
+    lambda^k of the step, and an explored move cuts the trace (Watkins).  `None` is the agent above on its own entry
+    points.  The agent owns `self.trace`, int64 [B, 4] -- the count and three packed keys per lane -- allocated for the
+    B of the first `fused_rollout` (or `update_q_value`); another B is refused.  `choose_action` goes through
+    q2048_nt_choose_ex and keeps the flags as `last_explored`; `update_q_value(..., cut=None)` uses the flags of the
+    `choose_action` before it.  The checkpoint keeps its kind and carries "trace": {"lambda", "depth", "keys"}; a plain
+    agent ignores it, a trace agent loads a file without it and starts with empty traces, another B or depth is refused.
+    Not combined with `coherence=True` or `stage_tiles`."""
 
     _FAMILY, _SHAPE, _KIND, _WHAT = "nt", (4, 1 << 24), "ntuple6_afterstate", "a 6-tuple afterstate network"
     _ACC_SHAPE = (4, 1 << 24, 2)
 
     def __init__(self, total_epochs, action_space=4, learning_rate=0.1, discount_factor=0.9,
                  exploration_rate=1.0, exploration_min=0.01, device="cuda", seed: int = 0,
-                 env_id0: int = 0, coherence: bool = False, stage_tiles=(), carousel: int = 0):
+                 env_id0: int = 0, coherence: bool = False, stage_tiles=(), carousel: int = 0,
+                 trace_lambda=None, trace_depth: int = 3):
         self.stage_tiles = self._check_stage_tiles(stage_tiles)
+        if trace_lambda is not None:
+            if isinstance(trace_lambda, bool) or not isinstance(trace_lambda, (int, float)) \
+                    or not 0.0 <= float(trace_lambda) <= 1.0:
+                raise ValueError(f"trace_lambda must be a number in [0, 1] or None, not {trace_lambda!r}")
+            if isinstance(trace_depth, bool) or not isinstance(trace_depth, int) or not 0 <= trace_depth <= 3:
+                raise ValueError(f"trace_depth must be 0, 1, 2 or 3, not {trace_depth!r}")
+            if coherence or self.stage_tiles:
+                raise ValueError("trace_lambda is not combined with coherence=True or stage_tiles: q2048_nt_lambda_* "
+                                 "knows one table and one step size")
+        self.trace_lambda = None if trace_lambda is None else float(trace_lambda)
+        self.trace_depth = int(trace_depth) if trace_lambda is not None else 0
+        self.trace = self.last_explored = self._cut = None
         if isinstance(carousel, bool) or not isinstance(carousel, int) or carousel < 0 or carousel > 1 << 32:
             raise ValueError(f"carousel must be a number of records per stage from 0 (off) to 2^32, not {carousel!r}")
         if carousel and not self.stage_tiles:
@@ -1963,7 +1986,25 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
     def _nts(self, name: str):
         return getattr(self._L, "q2048_nts_" + name)
 
+    def _trace_for(self, B: int) -> torch.Tensor:
+        if self.trace is None:
+            self.trace = torch.zeros((B, 4), dtype=torch.int64, device=self.device)
+        if self.trace.shape[0] != B:
+            raise ValueError(f"this agent's traces are those of {self.trace.shape[0]} lanes, not of {B}")
+        return self.trace
+
     def choose_action(self, boards) -> torch.Tensor:
+        if self.trace_lambda is not None:
+            boards = self._boards(boards)
+            B = boards.shape[0]
+            actions = torch.empty(B, dtype=torch.uint8, device=self.device)
+            explored = torch.empty(B, dtype=torch.uint8, device=self.device)
+            N.check(self._L.q2048_nt_choose_ex(_ptr(self.weights), _ptr(boards), B, float(self.epsilon), self.seed,
+                                               self.env_id0, self.ctr & 0xFFFFFFFF, _ptr(actions), _ptr(explored),
+                                               _stream(self.device)), "nt_choose_ex")
+            self.ctr += 1
+            self.last_explored = self._cut = explored
+            return actions
         if not self.stage_tiles:
             return super().choose_action(boards)
         boards = self._boards(boards)
@@ -2033,7 +2074,30 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
                                          _stream(self.device)), "nts_promote")
         return [int(c) for c in counts.tolist()]
 
-    def update_q_value(self, boards, actions, reward, next_boards, done) -> None:
+    def update_q_value(self, boards, actions, reward, next_boards, done, cut=None) -> None:
+        if self.trace_lambda is None and cut is not None:
+            raise ValueError("cut is the trace learner's argument: this agent was built without trace_lambda")
+        if self.trace_lambda is not None:
+            boards, next_boards = self._boards(boards), self._boards(next_boards)
+            B = boards.shape[0]
+            vec = lambda v, dt: torch.as_tensor(v).to(device=self.device, dtype=dt).contiguous()  # noqa: E731
+            actions, done = vec(actions, torch.uint8), vec(done, torch.uint8)
+            if not (actions.shape == tuple(torch.as_tensor(reward).shape) == done.shape == (B,)):
+                raise ValueError("actions / reward / done must have shape (B,)")
+            if cut is None:
+                if self._cut is None or self._cut.shape[0] != B:
+                    raise ValueError("no choose_action of this batch size since the last update: pass cut=")
+                cut = self._cut
+            cut = vec(cut, torch.uint8)
+            if cut.shape != (B,):
+                raise ValueError("cut must have shape (B,)")
+            trace = self._trace_for(B) if self.trace_depth else None
+            N.check(self._L.q2048_nt_lambda_update(
+                _ptr(self.weights), _ptr(trace) if trace is not None else None, _ptr(boards), _ptr(actions),
+                _ptr(next_boards), _ptr(done), _ptr(cut), B, float(self.lr), float(self.gamma), self.trace_lambda,
+                self.trace_depth, _ptr(self.status), _stream(self.device)), "nt_lambda_update")
+            self._cut = None
+            return None
         if self.stage_tiles:
             boards, next_boards = self._boards(boards), self._boards(next_boards)
             B = boards.shape[0]
@@ -2058,7 +2122,7 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
                                            _ptr(self.status), _stream(self.device)), "nt_tc_update")
 
     def fused_rollout(self, env: BatchedGame2048Env, steps: int) -> None:
-        if self.coherence is None and not self.stage_tiles:
+        if self.coherence is None and not self.stage_tiles and self.trace_lambda is None:
             return super().fused_rollout(env, steps)
         if env.board_size != 4 or env.device != self.device:
             raise ValueError("the afterstate learner needs a 4x4 env on the same device")
@@ -2066,6 +2130,16 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
             raise ValueError("env profiles are supported by the hash-table agent only")
         if (env.seed, env.env_id0, env.ctr) != (self.seed, self.env_id0, self.ctr):
             raise ValueError("env and agent must share seed, env_id0 and step counter")
+        if self.trace_lambda is not None:
+            trace = self._trace_for(env.num_envs) if self.trace_depth else None
+            N.check(self._L.q2048_nt_lambda_fused_rollout(
+                _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), _ptr(trace) if trace is not None else None,
+                env.num_envs, int(steps), float(self.epsilon), float(self.lr), float(self.gamma), self.trace_lambda,
+                self.trace_depth, self.seed, self.env_id0, self.ctr & 0xFFFFFFFF, _ptr(self.stats_i),
+                _ptr(self.stats_f), _ptr(self.status), _stream(self.device)), "nt_lambda_fused_rollout")
+            env.ctr += int(steps)
+            self.ctr += int(steps)
+            return None
         if self.carousel:
             B, S = env.num_envs, len(self.stage_tiles) + 1
             if self.carousel_fresh is None or self.carousel_fresh.shape[1] != B:
@@ -2130,12 +2204,31 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
         if self.carousel:
             sd["carousel"] = {"pool": self.carousel_pool.to("cpu", copy=True),
                               "counts": self.carousel_counts.to("cpu", copy=True)}
+        if self.trace_lambda is not None:
+            keys = self.trace.to("cpu", copy=True) if self.trace is not None else torch.zeros((0, 4), dtype=torch.int64)
+            sd["trace"] = {"lambda": self.trace_lambda, "depth": self.trace_depth, "keys": keys}
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
         """Everything -- the pairs included, where this agent takes them -- is validated before anything of this agent
         is written.  A plain agent ignores a file's pairs; a coherence agent without pairs in the file zeroes its own."""
         file_tiles = tuple(sd.get("stage_tiles") or ())
+        tr = sd.get("trace") if self.trace_lambda is not None else None      # a plain agent ignores a file's traces
+        if tr is not None:
+            keys = tr.get("keys") if isinstance(tr, dict) else None
+            if not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64 or keys.dim() != 2 or keys.shape[1] != 4:
+                raise ValueError("trace keys must be an int64 tensor of shape (B, 4)")
+            if tr.get("depth") != self.trace_depth:
+                raise ValueError(f"this checkpoint's trace depth {tr.get('depth')!r} differs from the agent's "
+                                 f"{self.trace_depth}")
+            if self.trace is not None and keys.shape[0] not in (0, self.trace.shape[0]):
+                raise ValueError(f"this checkpoint holds the traces of {keys.shape[0]} lanes, the agent those of "
+                                 f"{self.trace.shape[0]}")
+            on_host = keys.cpu()
+            n = on_host[:, 0]
+            beyond = torch.arange(1, 4)[None, :] > n[:, None]
+            if bool(((n < 0) | (n > self.trace_depth)).any()) or bool((on_host[:, 1:][beyond] != 0).any()):
+                raise ValueError("trace keys hold a count outside 0..depth or a key beyond the count")
         car = sd.get("carousel") if self.carousel else None      # a plain staged agent ignores a file's pool
         if car is not None:
             want = tuple(self.carousel_pool.shape)
@@ -2147,6 +2240,12 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
                     or bool((counts < 0).any()):
                 raise ValueError(f"carousel counts must be a non-negative int64 tensor of shape {want[:1]}")
         self._load_weights_and_pairs(sd, file_tiles)             # validates the rest, then writes
+        if self.trace_lambda is not None:
+            self._cut = None
+            if tr is not None and tr["keys"].shape[0]:
+                self.trace = tr["keys"].to(self.device, copy=True)
+            elif self.trace is not None:
+                self.trace.zero_()
         if self.carousel:
             if car is None:
                 self.carousel_pool.zero_()

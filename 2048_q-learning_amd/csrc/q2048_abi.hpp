@@ -183,6 +183,32 @@ static inline int check_nt_tc_fused(const void* boards, const void* aux, const v
   return Q2048_OK;
 }
 
+// TD(lambda) for the network (q2048_nt_lambda_*): the checks of the q2048_nt_* counterparts in their order, `trace`
+// directly after `weights` in the NULL list (unless h == 0: no trace is touched) and in the alignment list, and h and
+// lambda with the scalars, last.  q2048_nt_choose_ex checks as q2048_nt_choose does: `explored` may be NULL.
+static inline bool nt_lambda_ok(double lambda, int h) {
+  return h >= 0 && h <= 3 && lambda >= 0.0 && lambda <= 1.0;          // (a NaN fails both comparisons)
+}
+static inline int check_nt_lambda_update(const void* weights, const void* trace, const void* boards_s,
+                                         const void* actions, const void* boards_s2, const void* done, int64_t B,
+                                         double lr, double gamma, double lambda, int h, const void* status) {
+  if (int e = check_batch(B, 4)) return e;
+  if (!weights || (!trace && h != 0) || !boards_s || !actions || !boards_s2 || !done || !status) return Q2048_ERR_NULL;
+  if (!aligned16(weights) || !aligned16(trace) || !aligned16(boards_s) || !aligned16(boards_s2)) return Q2048_ERR_ALIGN;
+  if (!(lr == lr) || !(gamma == gamma) || !nt_lambda_ok(lambda, h)) return Q2048_ERR_RANGE;
+  return Q2048_OK;
+}
+static inline int check_nt_lambda_fused(const void* boards, const void* aux, const void* weights, const void* trace,
+                                        int64_t B, int64_t steps, double eps, double lr, double gamma, double lambda,
+                                        int h, const void* status) {
+  if (int e = check_batch(B, 4)) return e;
+  if (!boards || !aux || !weights || (!trace && h != 0) || !status) return Q2048_ERR_NULL;
+  if (!aligned16(boards) || !aligned16(aux) || !aligned16(weights) || !aligned16(trace)) return Q2048_ERR_ALIGN;
+  if (steps < 0 || steps > (1 << 30)) return Q2048_ERR_SIZE;
+  if (!(eps >= 0.0 && eps <= 1.0) || !(lr == lr) || !(gamma == gamma) || !nt_lambda_ok(lambda, h)) return Q2048_ERR_RANGE;
+  return Q2048_OK;
+}
+
 // The searched row of both afterstate families (q2048_{av,nt}_search_*): the checks of q2048_{av,nt}_lookup and
 // q2048_{av,nt}_play_rollout, in their order, with their codes; the legality mask is one more required pointer.
 static inline int check_search_lookup(const void* weights, const void* boards, int64_t B, const void* q_out,

@@ -1103,16 +1103,20 @@ Q_HD uint32_t nt_index(uint64_t key, int p) {
   return (p & 2) ? ((k & 0xfffu) | ((k1 & 0xfffu) << 12)) : (k & 0xffffffu);
 }
 struct NtIdx { uint32_t i[kNtPatterns][kNtImages]; };
-Q_HD NtIdx nt_indices(const Board& x) {
-  bool overflow;                                  // a cell >= 16 aliases by its low nibble, as in the other families
+// the 32 indices of a board from its packed key: all an evaluation or an update needs of the board
+Q_HD NtIdx nt_indices_key(uint64_t key) {
   uint64_t img[kNtImages];
-  key_images(pack_key(x, overflow), img);
+  key_images(key, img);
   NtIdx ix;
 #pragma unroll
   for (int p = 0; p < kNtPatterns; ++p)
 #pragma unroll
     for (int g = 0; g < kNtImages; ++g) ix.i[p][g] = nt_index(img[g], p);
   return ix;
+}
+Q_HD NtIdx nt_indices(const Board& x) {
+  bool overflow;                                  // a cell >= 16 aliases by its low nibble, as in the other families
+  return nt_indices_key(pack_key(x, overflow));
 }
 struct NtEntries { float e[kNtPatterns][kNtImages]; };
 // all 32 entries of a board, loaded back to back: nothing between two loads but the next address
@@ -1174,6 +1178,68 @@ Q_HD void nt_td(const Board& x, const NtEval& en, bool done, double lr, double g
   for (int p = 0; p < kNtPatterns; ++p)
 #pragma unroll
     for (int g = 0; g < kNtImages; ++g) st(p, ix.i[p][g], n.e[p][g] + d);
+}
+
+// TD(lambda) WITH A TRUNCATED TRACE (q2048_nt_lambda_*): a lane remembers the packed keys of the last n <= h <= 3
+// afterstates it learned on in the current episode, newest first, and the error of a step also moves them:
+//   d_0 = (float)((lr / 32) * err)            on the 32 entries of x     (nt_delta's d bit for bit: nt_td's write)
+//   d_k = (float)(((lr / 32) * L_k) * err)    on the 32 entries of key k, k = 1..n;  L_1 = lambda, L_k = L_{k-1} * lambda
+// in ASCENDING k, each gather after the stores before it: a weight that x and an earlier afterstate share moves by d_0
+// and then by d_k (the definition is sequential; within one key a repeated weight moves once, the family's rule).
+// No value is summed for k >= 1.  `cut` (the move was explored: Watkins' cut) empties the trace BEFORE the step,
+// `done` after it.  In memory a trace is uint64_t[4] = {n, key_1, key_2, key_3}, every word beyond n zero.
+struct NtTrace { uint64_t k1, k2, k3; uint32_t n; };
+Q_HD void nt_trace_clear(NtTrace& tr) { tr.k1 = tr.k2 = tr.k3 = 0ull; tr.n = 0u; }
+// h >= 1 (h == 0 is nt_td and no trace: the callers' branch)
+template <class Ld, class St>
+Q_HD void nt_lambda_td(const Board& x, const NtEval& en, bool done, bool cut, double lr, double gamma, double lambda,
+                       uint32_t h, NtTrace& tr, Ld ld, St st) {
+  Q2048_NO_CONTRACT
+  if (cut) nt_trace_clear(tr);
+  bool overflow;
+  const uint64_t key = pack_key(x, overflow);
+  double err;
+  {
+    const NtIdx ix = nt_indices_key(key);
+    const NtEntries n = nt_gather(ix, ld);
+    const bool live = !done && en.legal != 0u;
+    const double target = (gamma * (double)av_best(en.legal, en.q)) * (live ? 1.0 : 0.0);   // nt_delta's
+    err = target - (double)nt_v(n);
+    const float d = (float)((lr * 0.03125) * err);
+#pragma unroll
+    for (int p = 0; p < kNtPatterns; ++p)
+#pragma unroll
+      for (int g = 0; g < kNtImages; ++g) st(p, ix.i[p][g], n.e[p][g] + d);
+  }
+  // The earlier afterstates are a LOOP (one copy of the 32 loads and 32 stores), and the key of turn k is always
+  // `cur`: the others move up behind it.  An array indexed by k would live in scratch memory (see nt_eval).
+  uint64_t cur = tr.k1, nx1 = tr.k2, nx2 = tr.k3;
+  double L = lambda;
+#pragma unroll 1
+  for (uint32_t k = 0; k < tr.n; ++k) {
+    const float d = (float)(((lr * 0.03125) * L) * err);
+    const NtIdx ix = nt_indices_key(cur);
+    const NtEntries n = nt_gather(ix, ld);
+#pragma unroll
+    for (int p = 0; p < kNtPatterns; ++p)
+#pragma unroll
+      for (int g = 0; g < kNtImages; ++g) st(p, ix.i[p][g], n.e[p][g] + d);
+    cur = nx1;
+    nx1 = nx2;
+    L = L * lambda;
+  }
+  if (done) { nt_trace_clear(tr); return; }
+  tr.k3 = h >= 3u ? tr.k2 : 0ull;
+  tr.k2 = h >= 2u ? tr.k1 : 0ull;
+  tr.k1 = key;
+  tr.n = tr.n + 1u < h ? tr.n + 1u : h;
+}
+// the memory image of a trace
+Q_HD void nt_trace_words(const NtTrace& tr, uint64_t w[4]) { w[0] = tr.n; w[1] = tr.k1; w[2] = tr.k2; w[3] = tr.k3; }
+// (a trace from memory is taken as it is found -- a caller may hand in more keys than h, the next push truncates
+// them -- but n, which decides how many keys are updated, is at most 3)
+Q_HD NtTrace nt_trace_from(uint64_t w0, uint64_t w1, uint64_t w2, uint64_t w3) {
+  return NtTrace{w1, w2, w3, w0 < 3u ? (uint32_t)w0 : 3u};
 }
 
 // THE STAGED NETWORK (q2048_nts_*): a table per stage of the game, V = float[S][4][2^24], 1 <= S <= 8.  The largest

@@ -2017,6 +2017,109 @@ int q2048_nt_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, int6
   stats_merge(parts, used, stats_i, stats_f);
   return Q2048_OK;
 }
+// ---- TD(lambda): q2048_nt_update / q2048_nt_fused_rollout with nt_lambda_td for nt_td and the lane's trace ----
+int q2048_nt_choose_ex(const float* weights, const uint8_t* boards, int64_t B, double eps, uint64_t seed, uint64_t env_id0,
+                       uint32_t ctr, uint8_t* actions, uint8_t* explored_out, void*) {
+  if (int e = check_nt_choose(weights, boards, B, eps, actions)) return e;
+  const uint64_t eps_t = eps_threshold(eps);
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Board b;
+      load_board(boards, i, b);
+      const Draws x = draws(seed, env_id0 + (uint64_t)i, ctr, kStreamStep);
+      const NtEval ev = nt_eval(b, NtLd{weights});
+      bool explored;
+      actions[i] = (uint8_t)play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+      if (explored_out != nullptr) explored_out[i] = explored ? 1 : 0;
+    }
+  });
+  return Q2048_OK;
+}
+static inline NtTrace ld_trace(const uint64_t* trace, int64_t i) {
+  return nt_trace_from(trace[4 * i], trace[4 * i + 1], trace[4 * i + 2], trace[4 * i + 3]);
+}
+static inline void st_trace(uint64_t* trace, int64_t i, const NtTrace& tr) { nt_trace_words(tr, trace + 4 * i); }
+int q2048_nt_lambda_update(float* weights, uint64_t* trace, const uint8_t* boards_s, const uint8_t* actions,
+                           const uint8_t* boards_s2, const uint8_t* done, const uint8_t* cut, int64_t B, double lr,
+                           double gamma, double lambda, int h, uint32_t* status, void* stream) {
+  if (int e = check_nt_lambda_update(weights, trace, boards_s, actions, boards_s2, done, B, lr, gamma, lambda, h, status))
+    return e;
+  if (h == 0) return q2048_nt_update(weights, boards_s, actions, boards_s2, done, B, lr, gamma, status, stream);
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      const int act = actions[i];
+      if (act > 3) { status_or(status, Q2048_STATUS_BAD_ACTION); continue; }
+      Board x, b_n;
+      load_board(boards_s, i, x);
+      load_board(boards_s2, i, b_n);
+      const bool over = done[i] != 0;
+      NtTrace tr = ld_trace(trace, i);
+      uint32_t score;
+      if (!move(x, act, score)) {         // the step on which the env reports the end: no weight moves, the trace ends
+        if (over) { nt_trace_clear(tr); st_trace(trace, i, tr); }
+        continue;
+      }
+      const NtEval en = nt_eval(b_n, NtLd{weights});
+      nt_lambda_td(x, en, over, cut != nullptr && cut[i] != 0, lr, gamma, lambda, (uint32_t)h, tr, NtLd{weights},
+                   NtSt{weights});
+      st_trace(trace, i, tr);
+    }
+  });
+  return Q2048_OK;
+}
+int q2048_nt_lambda_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, uint64_t* trace, int64_t B,
+                                  int64_t steps, double eps, double lr, double gamma, double lambda, int h,
+                                  uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f,
+                                  uint32_t* status, void* stream) {
+  if (int e = check_nt_lambda_fused(boards, aux, weights, trace, B, steps, eps, lr, gamma, lambda, h, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  if (h == 0)
+    return q2048_nt_fused_rollout(boards, aux, weights, B, steps, eps, lr, gamma, seed, env_id0, ctr0, stats_i, stats_f,
+                                  status, stream);
+  const uint64_t eps_t = eps_threshold(eps);
+  const int T = threads_for(B);
+  std::vector<Stats> parts((size_t)T);
+  Stats* sp = parts.data();
+  const int used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+    Stats& st = sp[tid];
+    for (int64_t i = lo; i < hi; ++i) {
+      const uint64_t id = env_id0 + (uint64_t)i;
+      Board b;
+      load_board(boards, i, b);
+      Aux a = ld_aux(aux, i);
+      NtTrace tr = ld_trace(trace, i);
+      double reward_sum = 0.0;
+      for (int64_t t = 0; t < steps; ++t) {
+        const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+        const NtEval ev = nt_eval(b, NtLd{weights});
+        bool explored;
+        const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+        Board c = b;                    // the afterstate of the move played
+        uint32_t score;
+        const bool legal = move(c, act, score);
+        const StepOut o = env_step(b, a, act, x.x2, x.x3);
+        const NtEval en = nt_eval(b, NtLd{weights});
+        if (legal) nt_lambda_td(c, en, o.done != 0, explored, lr, gamma, lambda, (uint32_t)h, tr, NtLd{weights}, NtSt{weights});
+        else if (o.done) nt_trace_clear(tr);
+        st.i[Q2048_ST_VALID] += o.valid != 0;
+        st.i[Q2048_ST_EXPLORE] += explored;
+        reward_sum += (double)o.reward;
+        if (o.done) {
+          st.i[Q2048_ST_EPISODES] += 1;
+          st.episode(a, o.max_log2);
+          begin_episode(b, a, seed, id);
+        }
+      }
+      st.i[Q2048_ST_STEPS] += (uint64_t)steps;
+      st.f[Q2048_SF_REWARD] += reward_sum;
+      store_board(boards, i, b);
+      st_aux(aux, i, a);
+      st_trace(trace, i, tr);
+    }
+  });
+  stats_merge(parts, used, stats_i, stats_f);
+  return Q2048_OK;
+}
 // ---- temporal-coherence step sizes: q2048_nt_update / q2048_nt_fused_rollout with nt_tc_td for nt_td ----
 int q2048_nt_tc_update(float* weights, float* acc, const uint8_t* boards_s, const uint8_t* actions,
                        const uint8_t* boards_s2, const uint8_t* done, int64_t B, double lr, double gamma,

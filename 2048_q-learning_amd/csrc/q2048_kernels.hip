@@ -2601,6 +2601,108 @@ __global__ __launch_bounds__(kBlock, 2) void k_nt_tc_fused_rollout(
   stats_flush(bs, stats_i, stats_f);
 }
 
+// TD(lambda) with a truncated trace (q2048_nt_lambda_*): k_nt_update / k_nt_fused_rollout with nt_lambda_td for nt_td
+// and the lane's trace -- three packed keys and a count, seven VGPRs -- in registers from the first step to the last;
+// kernels of their own (h == 0 never comes here: the entry points launch the plain kernels).  The trace is two 16-byte
+// loads at the start and two 16-byte stores at the end.  Loads of V are NtLd<true>, stores plain 4-byte stores.
+__device__ __forceinline__ NtTrace ld_trace(const uint64_t* trace, int64_t i) {
+  const ulonglong2 a = reinterpret_cast<const ulonglong2*>(trace)[2 * i], b = reinterpret_cast<const ulonglong2*>(trace)[2 * i + 1];
+  return nt_trace_from(a.x, a.y, b.x, b.y);
+}
+__device__ __forceinline__ void st_trace(uint64_t* trace, int64_t i, const NtTrace& tr) {
+  reinterpret_cast<ulonglong2*>(trace)[2 * i] = make_ulonglong2((uint64_t)tr.n, tr.k1);
+  reinterpret_cast<ulonglong2*>(trace)[2 * i + 1] = make_ulonglong2(tr.k2, tr.k3);
+}
+
+__global__ __launch_bounds__(kBlock) void k_nt_choose_ex(const float* w, const uint8_t* boards, int64_t B, double eps,
+                                                         uint64_t seed, uint64_t env_id0, uint32_t ctr, uint8_t* actions,
+                                                         uint8_t* explored_out) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const Board b = load_board(boards, i, B, st);
+  const Draws x = draws(seed, env_id0 + (uint64_t)i, ctr, kStreamStep);
+  const NtEval ev = nt_eval(b, NtLd<true>{w});
+  bool explored;
+  actions[i] = (uint8_t)play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_threshold(eps), x.x0, x.x1, explored);
+  if (explored_out != nullptr) explored_out[i] = explored ? 1 : 0;
+}
+
+__global__ __launch_bounds__(kBlock) void k_nt_lambda_update(float* w, uint64_t* trace, const uint8_t* s,
+                                                             const uint8_t* actions, const uint8_t* s2, const uint8_t* done,
+                                                             const uint8_t* cut, int64_t B, double lr, double gamma,
+                                                             double lambda, uint32_t h, uint32_t* status) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const int act = actions[i];
+  if (act > 3) { atomicOr(status, Q2048_STATUS_BAD_ACTION); return; }
+  Board x = load_board(s, i, B, st);
+  const Board b_n = load_board(s2, i, B, st);
+  const bool over = done[i] != 0;
+  NtTrace tr = ld_trace(trace, i);
+  uint32_t score;
+  if (!move(x, act, score)) {           // the step on which the env reports the end: no weight moves, the trace ends
+    if (over) { nt_trace_clear(tr); st_trace(trace, i, tr); }
+    return;
+  }
+  const NtEval en = nt_eval(b_n, NtLd<true>{w});
+  nt_lambda_td(x, en, over, cut != nullptr && cut[i] != 0, lr, gamma, lambda, h, tr, NtLd<true>{w}, NtSt{w});
+  st_trace(trace, i, tr);
+}
+
+__global__ __launch_bounds__(kBlock) void k_nt_lambda_fused_rollout(
+    uint8_t* boards, q2048_aux* aux, float* w, uint64_t* trace, int64_t B, int steps, double eps, double lr,
+    double gamma, double lambda, uint32_t h, uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i,
+    double* stats_f, uint32_t* /*status: as on k_nt_fused_rollout*/) {
+  __shared__ BlockStats bs;
+  stats_clear(bs);
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < B) {
+    Stage<4> st;
+    const uint64_t id = env_id0 + (uint64_t)i;
+    Board b = load_board(boards, i, B, st);
+    Aux a = ld_aux(aux, i);
+    NtTrace tr = ld_trace(trace, i);
+    uint32_t n_valid = 0, n_explore = 0, n_done = 0;
+    double reward_sum = 0.0;
+    const uint64_t eps_t = eps_threshold(eps);
+    for (int t = 0; t < steps; ++t) {
+      const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+      const NtEval ev = nt_eval(b, NtLd<true>{w});      // from memory on every step, as in k_nt_fused_rollout
+      bool explored;
+      const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+      Board c = b;                    // the afterstate of the move played
+      uint32_t score;
+      const bool legal = move(c, act, score);
+      const StepOut o = env_step(b, a, act, x.x2, x.x3);
+      const NtEval en = nt_eval(b, NtLd<true>{w});
+      if (legal) nt_lambda_td(c, en, o.done != 0, explored, lr, gamma, lambda, h, tr, NtLd<true>{w}, NtSt{w});
+      else if (o.done) nt_trace_clear(tr);
+      n_valid += wave_count(o.valid != 0);
+      n_explore += wave_count(explored);
+      n_done += wave_count(o.done != 0);
+      reward_sum += (double)o.reward;
+      if (o.done) {
+        episode_stats(bs, a, o.max_log2);
+        begin_episode(b, a, seed, id);
+      }
+    }
+    store_board(boards, i, B, b, st);
+    st_aux(aux, i, a);
+    st_trace(trace, i, tr);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], reward_sum);
+    const uint32_t n_active = wave_count(true);
+    if (wave_leader()) {
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active * (u64)steps);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  stats_flush(bs, stats_i, stats_f);
+}
+
 // the player's and the search's evaluator (q2048_nt_play_rollout, q2048_nt_search_*): q2048_nt_lookup's row with
 // ordinary loads
 struct NtEvalOf {
@@ -4316,6 +4418,48 @@ int q2048_nt_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, int6
   hipLaunchKernelGGL(k_nt_fused_rollout, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream,
                      boards, aux, weights, B, (int)steps, eps, lr, gamma, seed, env_id0, ctr0, stats_i,
                      stats_f, status);
+  return launch_status();
+}
+
+// ---- TD(lambda): h == 0 is the plain step and touches no trace, so it is launched as the plain kernel ----
+int q2048_nt_choose_ex(const float* weights, const uint8_t* boards, int64_t B, double eps, uint64_t seed,
+                       uint64_t env_id0, uint32_t ctr, uint8_t* actions, uint8_t* explored, void* stream) {
+  if (int e = check_nt_choose(weights, boards, B, eps, actions)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_nt_choose_ex, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights,
+                     boards, B, eps, seed, env_id0, ctr, actions, explored);
+  return launch_status();
+}
+
+int q2048_nt_lambda_update(float* weights, uint64_t* trace, const uint8_t* boards_s, const uint8_t* actions,
+                           const uint8_t* boards_s2, const uint8_t* done, const uint8_t* cut, int64_t B, double lr,
+                           double gamma, double lambda, int h, uint32_t* status, void* stream) {
+  if (int e = check_nt_lambda_update(weights, trace, boards_s, actions, boards_s2, done, B, lr, gamma, lambda, h, status))
+    return e;
+  if (B == 0) return Q2048_OK;
+  if (h == 0)
+    hipLaunchKernelGGL(k_nt_update, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights,
+                       boards_s, actions, boards_s2, done, B, lr, gamma, status);
+  else
+    hipLaunchKernelGGL(k_nt_lambda_update, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights, trace,
+                       boards_s, actions, boards_s2, done, cut, B, lr, gamma, lambda, (uint32_t)h, status);
+  return launch_status();
+}
+
+int q2048_nt_lambda_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, uint64_t* trace, int64_t B,
+                                  int64_t steps, double eps, double lr, double gamma, double lambda, int h,
+                                  uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f,
+                                  uint32_t* status, void* stream) {
+  if (int e = check_nt_lambda_fused(boards, aux, weights, trace, B, steps, eps, lr, gamma, lambda, h, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  if (h == 0)
+    hipLaunchKernelGGL(k_nt_fused_rollout, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream,
+                       boards, aux, weights, B, (int)steps, eps, lr, gamma, seed, env_id0, ctr0, stats_i,
+                       stats_f, status);
+  else
+    hipLaunchKernelGGL(k_nt_lambda_fused_rollout, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream,
+                       boards, aux, weights, trace, B, (int)steps, eps, lr, gamma, lambda, (uint32_t)h, seed, env_id0,
+                       ctr0, stats_i, stats_f, status);
   return launch_status();
 }
 

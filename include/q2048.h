@@ -952,6 +952,50 @@ int q2048_nt_tc_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weights, f
                               uint64_t env_id0, uint32_t ctr0, int64_t *stats_i, double *stats_f,
                               uint32_t *status, void *stream);
 
+/* ---- TD(lambda) for the 6-tuple network: a truncated eligibility trace per lane (q2048_nt_lambda_*) ---------------
+ * The TD error of a step also moves the last n <= h <= 3 afterstates the lane learned on in the current episode.
+ *   weights   V = float[4][16777216] of the family above, unchanged: every q2048_nt_* reader works on a V trained here.
+ *   trace     uint64_t[B][4], 32 bytes per lane, 16-byte aligned, caller-owned; lane i uses trace[i].  Word 0 is n,
+ *             words 1..3 are the packed keys (cell 4r + c in nibble 4r + c) of x_{t-1}, x_{t-2}, x_{t-3}, newest
+ *             first.  Every word beyond n is 0 in what these entry points store, so the array compares byte for byte;
+ *             all zero = no history.  (On input n is read as min(n, 3) and the keys as they are: more than h keys are
+ *             updated once and truncated by the push.)  h == 0: never read or written, may be NULL.
+ *   TD step   on an afterstate x with the evaluation of the next state, `done` and a flag `cut`, in this order:
+ *             1. cut: n = 0 and the three keys 0 (Watkins' cut: the error of an explored move says nothing about the
+ *                afterstates before it);
+ *             2. err = target - (double)v(x), live, target and gather those of q2048_nt_update;
+ *             3. d_0 = (float)((lr * 0.03125) * err), q2048_nt_update's d bit for bit; the 32 entries of x are written
+ *                as gathered + d_0 (a weight x reads several times moves once: the family's rule);
+ *             4. for k = 1..n in ascending order, each after the stores of k - 1: the 32 entries of key k are gathered
+ *                and each is stored as gathered + d_k, d_k = (float)(((lr * 0.03125) * L_k) * err), L_1 = lambda,
+ *                L_2 = lambda * lambda, L_3 = (lambda * lambda) * lambda in double, no contraction; nothing is summed.
+ *                A weight x shares with an earlier afterstate moves by d_0 and then by d_k;
+ *             5. push: the keys become (key(x), key_1, key_2) truncated to h words, n = min(n + 1, h);
+ *             6. done: the lane's four words are zeroed.
+ *             h == 0 is step 3 alone: q2048_nt_update / q2048_nt_fused_rollout byte for byte.
+ *   update    q2048_nt_lambda_update has q2048_nt_update's skip rules: an action > 3 sets Q2048_STATUS_BAD_ACTION and
+ *             skips the lane; an action that does not change s writes no weight and pushes nothing -- but a set `done`
+ *             still zeroes the lane's trace (the env reports the end of a game on exactly such a step, and a trace
+ *             never crosses an episode).  cut[i] != 0 is the flag of lane i; cut == NULL: no cuts.
+ *   fused     q2048_nt_lambda_fused_rollout is q2048_nt_fused_rollout step for step -- evaluation from memory on every
+ *             step, draws, env step, statistics, reset -- with this TD step and cut = the `explored` flag of the
+ *             step's choice.  The trace is loaded at launch and stored at the end, so launches chain, and B = 1 is
+ *             exactly the loop q2048_nt_choose_ex / env step / q2048_nt_lambda_update / reset.
+ *   choose_ex q2048_nt_choose with the `explored` flag of the draw contract per lane (0 / 1; may be NULL).
+ * Argument checks are the q2048_nt_* counterpart's in its order, with trace checked for NULL (unless h == 0) and for
+ * 16-byte alignment directly after weights; last, Q2048_ERR_RANGE for h outside 0..3 or lambda outside [0, 1] or not
+ * finite.  A refused call writes nothing; B == 0 or steps == 0 is Q2048_OK. */
+int q2048_nt_choose_ex(const float *weights, const uint8_t *boards, int64_t B, double eps,
+                       uint64_t seed, uint64_t env_id0, uint32_t ctr, uint8_t *actions,
+                       uint8_t *explored, void *stream);
+int q2048_nt_lambda_update(float *weights, uint64_t *trace, const uint8_t *boards_s, const uint8_t *actions,
+                           const uint8_t *boards_s2, const uint8_t *done, const uint8_t *cut, int64_t B,
+                           double lr, double gamma, double lambda, int h, uint32_t *status, void *stream);
+int q2048_nt_lambda_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weights, uint64_t *trace, int64_t B,
+                                  int64_t steps, double eps, double lr, double gamma, double lambda, int h,
+                                  uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t *stats_i,
+                                  double *stats_f, uint32_t *status, void *stream);
+
 /* ---- one-level expectimax over the spawn, for both afterstate families -------------------------------------------
  * The SEARCHED ROW of a state s replaces q_a = score_a + v(c_a) by the mean of best over the spawns of c_a.  For
  * a = 0..3, with c_a, score_a, legal_a and best as the family defines them above:

@@ -104,6 +104,15 @@ def parse_args(argv=None):
                         "the stage its largest tile has reached, 256 MiB per stage.  --save records the tiles; --resume of "
                         "a plain ntuple file splits it (every stage starts as the file); a file with other tiles is "
                         "refused.  Not combined with --coherence")
+    p.add_argument("--trace-lambda", type=float, default=None, metavar="L",
+                   help="--agent ntuple only: TD(lambda) WITH A TRUNCATED TRACE (q2048_nt_lambda_*).  The TD error of a "
+                        "step also moves the last --trace-depth afterstates of the lane's episode, the k-th by L^k of "
+                        "the step; an explored move cuts the trace.  L in [0, 1] (0.5 is the usual setting).  --save "
+                        "keeps the traces; --resume of a file without them starts them empty.  Not combined with "
+                        "--coherence or --stage-tiles")
+    p.add_argument("--trace-depth", type=int, default=None, metavar="H",
+                   help="with --trace-lambda: how many earlier afterstates a lane remembers, 0..3 (default 3; 0 is the "
+                        "plain learner)")
     p.add_argument("--promote-every", type=int, default=None, metavar="N",
                    help="with --stage-tiles: every N epochs, copy what each stage has learned into the entries of the next "
                         "stage that are still zero (agent.promote()).  Default 1; 0 = never")
@@ -267,7 +276,9 @@ def train_batched(args, pkg):
     elif args.agent == "ntuple":
         agent = pkg.BatchedNTupleAgent(args.episodes, 4, args.alpha, args.gamma, args.epsilon,
                                        args.epsilon_min, dev, args.seed, shard.env_id0, coherence=args.coherence,
-                                       stage_tiles=args.stage_tiles, **({"carousel": args.carousel} if args.carousel else {}))
+                                       stage_tiles=args.stage_tiles, **({"carousel": args.carousel} if args.carousel else {}),
+                                       **({"trace_lambda": args.trace_lambda, "trace_depth": args.trace_depth}
+                                          if args.trace_lambda is not None else {}))
     else:
         agent = pkg.BatchedQLearningAgent(args.episodes, 4, args.alpha, args.gamma, args.epsilon,
                                           args.epsilon_min, cap, dev, args.seed, shard.env_id0,
@@ -287,6 +298,9 @@ def train_batched(args, pkg):
             if args.coherence and "coherence" not in sd and rank == 0:
                 print(f"{args.resume} holds no temporal-coherence accumulators: the weights continue, the accumulators "
                       "start at zero (every rate restarts at 1)", flush=True)
+            if "trace" in sd and args.trace_lambda is None:
+                raise SystemExit(f"{args.resume} holds eligibility traces: resume it with --trace-lambda "
+                                 "(without the flag a --save would silently drop them)")
             if args.stage_tiles and not sd.get("stage_tiles") and rank == 0:
                 print(f"{args.resume} holds a plain network: every one of the {len(args.stage_tiles) + 1} stages starts "
                       "as the file (stage 0 loaded, the later ones promoted from it)", flush=True)
@@ -592,6 +606,22 @@ def main(argv=None):
             raise SystemExit("--carousel applies with --stage-tiles")
         if args.carousel < 1 or args.carousel > 1 << 32:
             raise SystemExit("--carousel counts the records of a stage's pool: 1 to 2^32")
+    if args.trace_lambda is not None:
+        if args.agent != "ntuple":
+            raise SystemExit(f"--trace-lambda applies to --agent ntuple (the 6-tuple afterstate network), not to --agent {args.agent}")
+        if args.coherence or args.stage_tiles:
+            raise SystemExit("--trace-lambda is not combined with --coherence or --stage-tiles: the TD(lambda) step knows "
+                             "one table and one step size")
+        if args.num_envs == 1 and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+            raise SystemExit("--trace-lambda needs the batched mode (--num-envs > 1): the one-state loop runs the hash-table agent")
+        if not 0.0 <= args.trace_lambda <= 1.0:
+            raise SystemExit(f"--trace-lambda is a number in [0, 1], not {args.trace_lambda}")
+        if args.trace_depth is None:
+            args.trace_depth = 3
+        if not 0 <= args.trace_depth <= 3:
+            raise SystemExit(f"--trace-depth is 0, 1, 2 or 3, not {args.trace_depth}")
+    elif args.trace_depth is not None:
+        raise SystemExit("--trace-depth applies with --trace-lambda")
     if args.coherence:
         if args.agent != "ntuple":
             raise SystemExit(f"--coherence applies to --agent ntuple (the 6-tuple afterstate network), not to --agent {args.agent}")
