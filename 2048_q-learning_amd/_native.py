@@ -278,6 +278,12 @@ _SIGNATURES = {
                                                 C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64,
                                                 C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p]),
+    # the synchronous batch step: the plain learner's lists with `acc` (and `pend`) after the weights
+    "q2048_nt_sync_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "q2048_nt_sync_fused_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                              C.c_int64, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_uint64,
+                                              C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "q2048_nt_play_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double,
                                         C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),

@@ -1928,7 +1928,16 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
     q2048_nt_choose_ex and keeps the flags as `last_explored`; `update_q_value(..., cut=None)` uses the flags of the
     `choose_action` before it.  The checkpoint keeps its kind and carries "trace": {"lambda", "depth", "keys"}; a plain
     agent ignores it, a trace agent loads a file without it and starts with empty traces, another B or depth is refused.
-    Not combined with `coherence=True` or `stage_tiles`."""
+    Not combined with `coherence=True` or `stage_tiles`.
+
+    `synchronous=True` makes the learner the SYNCHRONOUS BATCH STEP (q2048_nt_sync_*): in one step every lane evaluates
+    against the same frozen weights, the TD errors that fall on a weight are summed exactly, as integers, and the weight
+    moves once by their mean -- a pure function of its inputs at any batch size, the same bytes on the device and on
+    "cpu" with any number of threads.  The agent owns `self.sync_acc`, int64 [4, 16777216, 2] (1 GiB), all zero between
+    calls, and allocates `self.sync_pend`, int64 [B], for the B of the first `fused_rollout`; another B is refused, and
+    B is at most 1,048,576.  Everything that only reads V is inherited, and the checkpoint is the plain agent's: plain
+    and synchronous agents load each other's files.  Not combined with `coherence=True`, `stage_tiles`, `carousel` or
+    `trace_lambda`."""
 
     _FAMILY, _SHAPE, _KIND, _WHAT = "nt", (4, 1 << 24), "ntuple6_afterstate", "a 6-tuple afterstate network"
     _ACC_SHAPE = (4, 1 << 24, 2)
@@ -1936,8 +1945,18 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
     def __init__(self, total_epochs, action_space=4, learning_rate=0.1, discount_factor=0.9,
                  exploration_rate=1.0, exploration_min=0.01, device="cuda", seed: int = 0,
                  env_id0: int = 0, coherence: bool = False, stage_tiles=(), carousel: int = 0,
-                 trace_lambda=None, trace_depth: int = 3):
+                 trace_lambda=None, trace_depth: int = 3, synchronous: bool = False):
         self.stage_tiles = self._check_stage_tiles(stage_tiles)
+        if not isinstance(synchronous, bool):
+            raise ValueError(f"synchronous must be True or False, not {synchronous!r}")
+        if synchronous:
+            for name, given in (("coherence=True", coherence), ("stage_tiles", self.stage_tiles),
+                                ("carousel", carousel), ("trace_lambda", trace_lambda is not None)):
+                if given:
+                    raise ValueError(f"synchronous=True is not combined with {name}: q2048_nt_sync_* is the plain "
+                                     "network's step")
+        self.synchronous = synchronous
+        self.sync_acc = self.sync_pend = None
         if trace_lambda is not None:
             if isinstance(trace_lambda, bool) or not isinstance(trace_lambda, (int, float)) \
                     or not 0.0 <= float(trace_lambda) <= 1.0:
@@ -1964,6 +1983,8 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
         super().__init__(total_epochs, action_space, learning_rate, discount_factor, exploration_rate,
                          exploration_min, device, seed, env_id0)
         self.coherence = torch.zeros(self._ACC_SHAPE, dtype=torch.float32, device=self.device) if coherence else None
+        if self.synchronous:
+            self.sync_acc = torch.zeros(self._ACC_SHAPE, dtype=torch.int64, device=self.device)
         self.carousel_pool = self.carousel_counts = self.carousel_fresh = None
         if self.carousel:
             S = len(self.stage_tiles) + 1
@@ -2077,6 +2098,17 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
     def update_q_value(self, boards, actions, reward, next_boards, done, cut=None) -> None:
         if self.trace_lambda is None and cut is not None:
             raise ValueError("cut is the trace learner's argument: this agent was built without trace_lambda")
+        if self.synchronous:
+            boards, next_boards = self._boards(boards), self._boards(next_boards)
+            B = boards.shape[0]
+            vec = lambda v, dt: torch.as_tensor(v).to(device=self.device, dtype=dt).contiguous()  # noqa: E731
+            actions, done = vec(actions, torch.uint8), vec(done, torch.uint8)
+            if not (actions.shape == tuple(torch.as_tensor(reward).shape) == done.shape == (B,)):
+                raise ValueError("actions / reward / done must have shape (B,)")
+            N.check(self._L.q2048_nt_sync_update(_ptr(self.weights), _ptr(self.sync_acc), _ptr(boards), _ptr(actions),
+                                                 _ptr(next_boards), _ptr(done), B, float(self.lr), float(self.gamma),
+                                                 _ptr(self.status), _stream(self.device)), "nt_sync_update")
+            return None
         if self.trace_lambda is not None:
             boards, next_boards = self._boards(boards), self._boards(next_boards)
             B = boards.shape[0]
@@ -2122,7 +2154,7 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
                                            _ptr(self.status), _stream(self.device)), "nt_tc_update")
 
     def fused_rollout(self, env: BatchedGame2048Env, steps: int) -> None:
-        if self.coherence is None and not self.stage_tiles and self.trace_lambda is None:
+        if self.coherence is None and not self.stage_tiles and self.trace_lambda is None and not self.synchronous:
             return super().fused_rollout(env, steps)
         if env.board_size != 4 or env.device != self.device:
             raise ValueError("the afterstate learner needs a 4x4 env on the same device")
@@ -2130,6 +2162,20 @@ class BatchedNTupleAgent(BatchedAfterstateAgent):
             raise ValueError("env profiles are supported by the hash-table agent only")
         if (env.seed, env.env_id0, env.ctr) != (self.seed, self.env_id0, self.ctr):
             raise ValueError("env and agent must share seed, env_id0 and step counter")
+        if self.synchronous:
+            if self.sync_pend is None:
+                self.sync_pend = torch.zeros(env.num_envs, dtype=torch.int64, device=self.device)
+            if self.sync_pend.shape[0] != env.num_envs:
+                raise ValueError(f"this agent's step scratch is that of {self.sync_pend.shape[0]} lanes, not of "
+                                 f"{env.num_envs}")
+            N.check(self._L.q2048_nt_sync_fused_rollout(
+                _ptr(env.boards), _ptr(env.aux), _ptr(self.weights), _ptr(self.sync_acc), _ptr(self.sync_pend),
+                env.num_envs, int(steps), float(self.epsilon), float(self.lr), float(self.gamma), self.seed,
+                self.env_id0, self.ctr & 0xFFFFFFFF, _ptr(self.stats_i), _ptr(self.stats_f), _ptr(self.status),
+                _stream(self.device)), "nt_sync_fused_rollout")
+            env.ctr += int(steps)
+            self.ctr += int(steps)
+            return None
         if self.trace_lambda is not None:
             trace = self._trace_for(env.num_envs) if self.trace_depth else None
             N.check(self._L.q2048_nt_lambda_fused_rollout(

@@ -183,6 +183,38 @@ static inline int check_nt_tc_fused(const void* boards, const void* aux, const v
   return Q2048_OK;
 }
 
+// The synchronous batch step of the network (q2048_nt_sync_*): the checks of the q2048_nt_* counterparts in their
+// order, `acc` (then `pend`) directly after `weights` in the NULL and in the alignment list, and after the alignment
+// checks two of their own: B <= 2^20 (the bound that keeps every sum exact), and V (256 MiB) and acc (1 GiB) may not
+// overlap.
+static inline bool nt_sync_overlap(const void* weights, const void* acc) {
+  const uintptr_t w0 = reinterpret_cast<uintptr_t>(weights), a0 = reinterpret_cast<uintptr_t>(acc);
+  const uintptr_t w1 = w0 + ((uintptr_t)1 << 28), a1 = a0 + ((uintptr_t)1 << 30);
+  return a0 < w1 && w0 < a1;
+}
+static inline int check_nt_sync_update(const void* weights, const void* acc, const void* boards_s, const void* actions,
+                                       const void* boards_s2, const void* done, int64_t B, double lr, double gamma,
+                                       const void* status) {
+  if (int e = check_batch(B, 4)) return e;
+  if (!weights || !acc || !boards_s || !actions || !boards_s2 || !done || !status) return Q2048_ERR_NULL;
+  if (!aligned16(weights) || !aligned16(acc) || !aligned16(boards_s) || !aligned16(boards_s2)) return Q2048_ERR_ALIGN;
+  if (B > ((int64_t)1 << 20) || nt_sync_overlap(weights, acc)) return Q2048_ERR_RANGE;
+  if (!(lr == lr) || !(gamma == gamma)) return Q2048_ERR_RANGE;
+  return Q2048_OK;
+}
+static inline int check_nt_sync_fused(const void* boards, const void* aux, const void* weights, const void* acc,
+                                      const void* pend, int64_t B, int64_t steps, double eps, double lr, double gamma,
+                                      const void* status) {
+  if (int e = check_batch(B, 4)) return e;
+  if (!boards || !aux || !weights || !acc || !pend || !status) return Q2048_ERR_NULL;
+  if (!aligned16(boards) || !aligned16(aux) || !aligned16(weights) || !aligned16(acc) || !aligned16(pend))
+    return Q2048_ERR_ALIGN;
+  if (B > ((int64_t)1 << 20) || nt_sync_overlap(weights, acc)) return Q2048_ERR_RANGE;
+  if (steps < 0 || steps > (1 << 30)) return Q2048_ERR_SIZE;
+  if (!(eps >= 0.0 && eps <= 1.0) || !(lr == lr) || !(gamma == gamma)) return Q2048_ERR_RANGE;
+  return Q2048_OK;
+}
+
 // TD(lambda) for the network (q2048_nt_lambda_*): the checks of the q2048_nt_* counterparts in their order, `trace`
 // directly after `weights` in the NULL list (unless h == 0: no trace is touched) and in the alignment list, and h and
 // lambda with the scalars, last.  q2048_nt_choose_ex checks as q2048_nt_choose does: `explored` may be NULL.

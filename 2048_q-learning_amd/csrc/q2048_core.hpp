@@ -1458,6 +1458,75 @@ Q_HD void nt_tc_td(const Board& x, const NtEval& en, bool done, double lr, doubl
   }
 }
 
+// THE SYNCHRONOUS BATCH STEP (q2048_nt_sync_*): every lane evaluates against the same frozen V, the errors that fall
+// on a weight are summed exactly, as integers, and the weight then moves once by their mean.  Beside V sits
+// acc = uint64_t[4][2^24][2], acc[p][idx] = {S, C}: the two's-complement sum of the quantised errors and the number of
+// contributions; all zero between steps.
+//   phase A  a lane with a TD sample: err as nt_delta forms it, q = nt_sync_quantise(err), and for each of its 32
+//            entries, PER OCCURRENCE, `add(p, idx, q)`: S += q, C += 1 (both atomic).  V is only read.
+//   phase B  every weight with C != 0 is written exactly once: `claim(p, idx)` returns C and leaves 0 there, so of all
+//            occurrences of a weight in the batch exactly one sees C != 0; its lane takes S (`take(p, idx)`: returns S,
+//            leaves 0) and stores V + nt_sync_step(S, C, lr).
+// The sums are integers (B <= 2^20: |S| <= 2^30 * 2^23 = 2^53, C <= 2^23, both exact in double), so the bytes do not
+// depend on the order or the mechanism that forms them.  Between A and B every lane of A has finished: the callers'
+// kernel boundary, or a join of the threads.
+constexpr int64_t kNtSyncMaxB = (int64_t)1 << 20;
+constexpr double kNtSyncClamp = 262144.0, kNtSyncScale = 4096.0;     // |err| <= 2^18 on a grid of 2^-12
+// the clamp is exact, the product (by a power of two, below 2^31) is exact, llrint rounds to nearest even; a NaN is 0
+Q_HD int64_t nt_sync_quantise(double err) {
+  Q2048_NO_CONTRACT
+  const double e = (err != err) ? 0.0 : err;
+  const double c = e < -kNtSyncClamp ? -kNtSyncClamp : (e > kNtSyncClamp ? kNtSyncClamp : e);
+  return (int64_t)llrint(c * kNtSyncScale);
+}
+// d of a weight from its sums: one division, one rounding to float32
+Q_HD float nt_sync_step(int64_t S, uint64_t C, double lr) {
+  Q2048_NO_CONTRACT
+  const double m = (double)S / ((double)C * kNtSyncScale);
+  return (float)((lr * 0.03125) * m);
+}
+// phase A on the afterstate x, given the evaluation of the next state; returns the packed key of x (never 0: an
+// afterstate of a legal move is not the empty board), which is all phase B needs of the lane
+template <class Ld, class Add>
+Q_HD uint64_t nt_sync_acc(const Board& x, const NtEval& en, bool done, double gamma, Ld ld, Add add) {
+  Q2048_NO_CONTRACT
+  bool overflow;
+  const uint64_t key = pack_key(x, overflow);
+  const NtIdx ix = nt_indices_key(key);
+  const NtEntries n = nt_gather(ix, ld);
+  const bool live = !done && en.legal != 0u;
+  const double target = (gamma * (double)av_best(en.legal, en.q)) * (live ? 1.0 : 0.0);   // nt_delta's
+  const int64_t q = nt_sync_quantise(target - (double)nt_v(n));
+#pragma unroll
+  for (int p = 0; p < kNtPatterns; ++p)
+#pragma unroll
+    for (int g = 0; g < kNtImages; ++g) add(p, ix.i[p][g], q);
+  return key;
+}
+// phase B of a lane that contributed `key`.  The patterns are a LOOP (see nt_tc_td): eight claims are in flight
+// together, and V is loaded beside them whether the claim succeeds or not (a load of an entry nobody else writes
+// before its one owner does, so the owner reads the frozen value).
+template <class Ld, class St, class Claim, class Take>
+Q_HD void nt_sync_apply(uint64_t key, double lr, Ld ld, St st, Claim claim, Take take) {
+  uint64_t img[kNtImages];
+  key_images(key, img);
+#pragma unroll 1
+  for (int p = 0; p < kNtPatterns; ++p) {
+    uint64_t c[kNtImages];
+    float v[kNtImages];
+#pragma unroll
+    for (int g = 0; g < kNtImages; ++g) c[g] = claim(p, nt_index_at(img[g], (uint32_t)p));
+#pragma unroll
+    for (int g = 0; g < kNtImages; ++g) v[g] = ld(p, nt_index_at(img[g], (uint32_t)p));
+#pragma unroll
+    for (int g = 0; g < kNtImages; ++g) {
+      if (c[g] == 0u) continue;
+      const uint32_t idx = nt_index_at(img[g], (uint32_t)p);
+      st(p, idx, v[g] + nt_sync_step(take(p, idx), c[g], lr));
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // ONE-LEVEL EXPECTIMAX over the spawn, for both afterstate families (q2048_av_search_*, q2048_nt_search_*): the row
 // a player hands to play_action is, instead of q_a = score_a + v(c_a),

@@ -880,6 +880,27 @@ struct NtSt {
   float* v;
   void operator()(int p, uint32_t idx, float x) const { st_f32(v + ((size_t)p * kNtIdx + idx), x); }
 };
+// the pair {S, C} of acc = uint64_t[4][2^24][2] (q2048_nt_sync_*): relaxed 64-bit atomics, as on the device
+struct NtSyncAdd {
+  uint64_t* acc;
+  void operator()(int p, uint32_t idx, int64_t q) const {
+    uint64_t* e = acc + 2 * ((size_t)p * kNtIdx + idx);
+    __atomic_fetch_add(e, (uint64_t)q, __ATOMIC_RELAXED);
+    __atomic_fetch_add(e + 1, (uint64_t)1, __ATOMIC_RELAXED);
+  }
+};
+struct NtSyncClaim {
+  uint64_t* acc;
+  uint64_t operator()(int p, uint32_t idx) const {
+    return __atomic_exchange_n(acc + 2 * ((size_t)p * kNtIdx + idx) + 1, (uint64_t)0, __ATOMIC_RELAXED);
+  }
+};
+struct NtSyncTake {
+  uint64_t* acc;
+  int64_t operator()(int p, uint32_t idx) const {
+    return (int64_t)__atomic_exchange_n(acc + 2 * ((size_t)p * kNtIdx + idx), (uint64_t)0, __ATOMIC_RELAXED);
+  }
+};
 // a pair {E, A} of acc = float[4][2^24][2]: one relaxed 64-bit atomic each way, packed through memcpy (a struct of two
 // floats may be split into two accesses by the compiler)
 struct NtTcLd {
@@ -2117,6 +2138,86 @@ int q2048_nt_lambda_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weight
       st_trace(trace, i, tr);
     }
   });
+  stats_merge(parts, used, stats_i, stats_f);
+  return Q2048_OK;
+}
+// ---- the synchronous batch step: phase A over the thread ranges, a join, phase B over the same ranges ----
+int q2048_nt_sync_update(float* weights, uint64_t* acc, const uint8_t* boards_s, const uint8_t* actions,
+                         const uint8_t* boards_s2, const uint8_t* done, int64_t B, double lr, double gamma,
+                         uint32_t* status, void*) {
+  if (int e = check_nt_sync_update(weights, acc, boards_s, actions, boards_s2, done, B, lr, gamma, status)) return e;
+  if (B == 0) return Q2048_OK;
+  std::vector<uint64_t> keys((size_t)B);      // the afterstate each lane contributed, 0 = none
+  uint64_t* kp = keys.data();
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i) {
+      kp[i] = 0ull;
+      const int act = actions[i];
+      if (act > 3) { status_or(status, Q2048_STATUS_BAD_ACTION); continue; }
+      Board x, b_n;
+      load_board(boards_s, i, x);
+      load_board(boards_s2, i, b_n);
+      uint32_t score;
+      if (!move(x, act, score)) continue;   // the step on which the env reports the end
+      const NtEval en = nt_eval(b_n, NtLd{weights});
+      kp[i] = nt_sync_acc(x, en, done[i] != 0, gamma, NtLd{weights}, NtSyncAdd{acc});
+    }
+  });
+  parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+    for (int64_t i = lo; i < hi; ++i)
+      if (kp[i] != 0ull) nt_sync_apply(kp[i], lr, NtLd{weights}, NtSt{weights}, NtSyncClaim{acc}, NtSyncTake{acc});
+  });
+  return Q2048_OK;
+}
+int q2048_nt_sync_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, uint64_t* acc, uint64_t* pend, int64_t B,
+                                int64_t steps, double eps, double lr, double gamma, uint64_t seed, uint64_t env_id0,
+                                uint32_t ctr0, int64_t* stats_i, double* stats_f, uint32_t* status, void*) {
+  if (int e = check_nt_sync_fused(boards, aux, weights, acc, pend, B, steps, eps, lr, gamma, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  const uint64_t eps_t = eps_threshold(eps);
+  const int T = threads_for(B);
+  std::vector<Stats> parts((size_t)T);
+  Stats* sp = parts.data();
+  int used = 0;
+  for (int64_t t = 0; t < steps; ++t) {
+    used = parallel_ranges(B, [=](int64_t lo, int64_t hi, int tid) {
+      Stats& st = sp[tid];
+      for (int64_t i = lo; i < hi; ++i) {
+        const uint64_t id = env_id0 + (uint64_t)i;
+        Board b;
+        load_board(boards, i, b);
+        Aux a = ld_aux(aux, i);
+        const Draws x = draws(seed, id, ctr0 + (uint32_t)t, kStreamStep);
+        const NtEval ev = nt_eval(b, NtLd{weights});
+        bool explored;
+        const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_t, x.x0, x.x1, explored);
+        Board c = b;                    // the afterstate of the move played
+        uint32_t score;
+        const bool legal = move(c, act, score);
+        const StepOut o = env_step(b, a, act, x.x2, x.x3);
+        const NtEval en = nt_eval(b, NtLd{weights});
+        pend[i] = legal ? nt_sync_acc(c, en, o.done != 0, gamma, NtLd{weights}, NtSyncAdd{acc}) : 0ull;
+        st.i[Q2048_ST_VALID] += o.valid != 0;
+        st.i[Q2048_ST_EXPLORE] += explored;
+        st.i[Q2048_ST_STEPS] += 1;
+        st.f[Q2048_SF_REWARD] += (double)o.reward;
+        if (o.done) {
+          st.i[Q2048_ST_EPISODES] += 1;
+          st.episode(a, o.max_log2);
+          begin_episode(b, a, seed, id);
+        }
+        store_board(boards, i, b);
+        st_aux(aux, i, a);
+      }
+    });
+    parallel_ranges(B, [=](int64_t lo, int64_t hi, int) {
+      for (int64_t i = lo; i < hi; ++i) {
+        const uint64_t key = pend[i];
+        pend[i] = 0ull;
+        if (key != 0ull) nt_sync_apply(key, lr, NtLd{weights}, NtSt{weights}, NtSyncClaim{acc}, NtSyncTake{acc});
+      }
+    });
+  }
   stats_merge(parts, used, stats_i, stats_f);
   return Q2048_OK;
 }

@@ -2505,6 +2505,120 @@ __global__ __launch_bounds__(kBlock) void k_nt_fused_rollout(
   stats_flush(bs, stats_i, stats_f);
 }
 
+// The synchronous batch step (q2048_nt_sync_*): acc = uint64_t[4][2^24][2] beside V, a pair {S, C} per weight.  Phase A
+// adds with 64-bit integer atomics whose result nobody reads (global_atomic_add_x2 without return); phase B claims a
+// weight by exchanging its C for 0, and the one lane that receives a count takes S the same way and writes V.  Every
+// access to acc is an agent-scope atomic, so no reasoning about caches is needed; V is loaded as in the learner
+// kernels and stored by plain stores.  The ordering between the phases is the kernel boundary: two launches per step.
+struct NtSyncAdd {
+  uint64_t* acc;
+  __device__ __forceinline__ void operator()(int p, uint32_t idx, int64_t q) const {
+    u64* e = reinterpret_cast<u64*>(acc) + 2 * ((size_t)p * kNtIdx + idx);
+    __hip_atomic_fetch_add(e, (u64)q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(e + 1, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
+struct NtSyncClaim {
+  uint64_t* acc;
+  __device__ __forceinline__ uint64_t operator()(int p, uint32_t idx) const {
+    u64* e = reinterpret_cast<u64*>(acc) + 2 * ((size_t)p * kNtIdx + idx);
+    return __hip_atomic_exchange(e + 1, (u64)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
+struct NtSyncTake {
+  uint64_t* acc;
+  __device__ __forceinline__ int64_t operator()(int p, uint32_t idx) const {
+    u64* e = reinterpret_cast<u64*>(acc) + 2 * ((size_t)p * kNtIdx + idx);
+    return (int64_t)__hip_atomic_exchange(e, (u64)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
+
+// phase A of q2048_nt_sync_update: k_nt_update's lane, contributing instead of writing
+__global__ __launch_bounds__(kBlock) void k_nt_sync_update_acc(const float* w, uint64_t* acc, const uint8_t* s,
+                                                               const uint8_t* actions, const uint8_t* s2,
+                                                               const uint8_t* done, int64_t B, double gamma,
+                                                               uint32_t* status) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  Stage<4> st;
+  const int act = actions[i];
+  if (act > 3) { atomicOr(status, Q2048_STATUS_BAD_ACTION); return; }
+  Board x = load_board(s, i, B, st);
+  const Board b_n = load_board(s2, i, B, st);
+  uint32_t score;
+  if (!move(x, act, score)) return;   // the step on which the env reports the end
+  const NtEval en = nt_eval(b_n, NtLd<true>{w});
+  nt_sync_acc(x, en, done[i] != 0, gamma, NtLd<true>{w}, NtSyncAdd{acc});
+}
+
+// phase A of one step of q2048_nt_sync_fused_rollout: k_nt_fused_rollout's step with draw counter `ctr`, the board
+// and aux through memory, and the afterstate's key left in pend[i] for phase B (0: the move was not legal)
+__global__ __launch_bounds__(kBlock) void k_nt_sync_step(
+    uint8_t* boards, q2048_aux* aux, const float* w, uint64_t* acc, uint64_t* pend, int64_t B, double eps,
+    double gamma, uint64_t seed, uint64_t env_id0, uint32_t ctr, int64_t* stats_i, double* stats_f) {
+  __shared__ BlockStats bs;
+  stats_clear(bs);
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < B) {
+    Stage<4> st;
+    const uint64_t id = env_id0 + (uint64_t)i;
+    Board b = load_board(boards, i, B, st);
+    Aux a = ld_aux(aux, i);
+    const Draws x = draws(seed, id, ctr, kStreamStep);
+    const NtEval ev = nt_eval(b, NtLd<true>{w});
+    bool explored;
+    const int act = play_action(ev.legal, ev.q.q0, ev.q.q1, ev.q.q2, ev.q.q3, eps_threshold(eps), x.x0, x.x1, explored);
+    Board c = b;                    // the afterstate of the move played
+    uint32_t score;
+    const bool legal = move(c, act, score);
+    const StepOut o = env_step(b, a, act, x.x2, x.x3);
+    const NtEval en = nt_eval(b, NtLd<true>{w});
+    uint64_t key = 0ull;
+    if (legal) key = nt_sync_acc(c, en, o.done != 0, gamma, NtLd<true>{w}, NtSyncAdd{acc});
+    pend[i] = key;
+    const uint32_t n_valid = wave_count(o.valid != 0), n_explore = wave_count(explored), n_done = wave_count(o.done != 0);
+    if (o.done) {
+      episode_stats(bs, a, o.max_log2);
+      begin_episode(b, a, seed, id);
+    }
+    store_board(boards, i, B, b, st);
+    st_aux(aux, i, a);
+    atomicAdd(&bs.f[Q2048_SF_REWARD], (double)o.reward);
+    const uint32_t n_active = wave_count(true);
+    if (wave_leader()) {
+      atomicAdd(&bs.i[Q2048_ST_STEPS], (u64)n_active);
+      atomicAdd(&bs.i[Q2048_ST_VALID], (u64)n_valid);
+      atomicAdd(&bs.i[Q2048_ST_EXPLORE], (u64)n_explore);
+      atomicAdd(&bs.i[Q2048_ST_EPISODES], (u64)n_done);
+    }
+  }
+  stats_flush(bs, stats_i, stats_f);
+}
+
+// phase B of both: the lane's afterstate is the key in pend[i] (fused; the word is zeroed), or, pend == NULL, the move
+// of s by its action again (update: the lanes phase A skipped are skipped here by the same two rules)
+__global__ __launch_bounds__(kBlock) void k_nt_sync_apply(float* w, uint64_t* acc, uint64_t* pend, const uint8_t* s,
+                                                          const uint8_t* actions, int64_t B, double lr) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  uint64_t key;
+  if (pend != nullptr) {
+    key = pend[i];
+    pend[i] = 0ull;
+  } else {
+    Stage<4> st;
+    const int act = actions[i];
+    if (act > 3) return;
+    Board x = load_board(s, i, B, st);
+    uint32_t score;
+    if (!move(x, act, score)) return;
+    bool overflow;
+    key = pack_key(x, overflow);
+  }
+  if (key == 0ull) return;
+  nt_sync_apply(key, lr, NtLd<true>{w}, NtSt{w}, NtSyncClaim{acc}, NtSyncTake{acc});
+}
+
 // Temporal-coherence step sizes (q2048_nt_tc_*): acc = float[4][2^24][2] beside V, a pair {E, A} per weight,
 // interleaved so that a weight's history is ONE request each way (two arrays would be two): a relaxed agent-scope
 // 64-bit atomic load, and one ordinary 8-byte vector store from plain C++.  Neither can tear, so a pair a reader
@@ -4460,6 +4574,35 @@ int q2048_nt_lambda_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weight
     hipLaunchKernelGGL(k_nt_lambda_fused_rollout, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream,
                        boards, aux, weights, trace, B, (int)steps, eps, lr, gamma, lambda, (uint32_t)h, seed, env_id0,
                        ctr0, stats_i, stats_f, status);
+  return launch_status();
+}
+
+// ---- the synchronous batch step: phase A and phase B are two launches on the caller's stream, per step ----
+int q2048_nt_sync_update(float* weights, uint64_t* acc, const uint8_t* boards_s, const uint8_t* actions,
+                         const uint8_t* boards_s2, const uint8_t* done, int64_t B, double lr, double gamma,
+                         uint32_t* status, void* stream) {
+  if (int e = check_nt_sync_update(weights, acc, boards_s, actions, boards_s2, done, B, lr, gamma, status)) return e;
+  if (B == 0) return Q2048_OK;
+  hipLaunchKernelGGL(k_nt_sync_update_acc, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights, acc,
+                     boards_s, actions, boards_s2, done, B, gamma, status);
+  hipLaunchKernelGGL(k_nt_sync_apply, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights, acc,
+                     (uint64_t*)nullptr, boards_s, actions, B, lr);
+  return launch_status();
+}
+
+int q2048_nt_sync_fused_rollout(uint8_t* boards, q2048_aux* aux, float* weights, uint64_t* acc, uint64_t* pend,
+                                int64_t B, int64_t steps, double eps, double lr, double gamma, uint64_t seed,
+                                uint64_t env_id0, uint32_t ctr0, int64_t* stats_i, double* stats_f,
+                                uint32_t* status, void* stream) {
+  if (int e = check_nt_sync_fused(boards, aux, weights, acc, pend, B, steps, eps, lr, gamma, status)) return e;
+  if (B == 0 || steps == 0) return Q2048_OK;
+  for (int64_t t = 0; t < steps; ++t) {
+    hipLaunchKernelGGL(k_nt_sync_step, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, boards, aux,
+                       (const float*)weights, acc, pend, B, eps, gamma, seed, env_id0, ctr0 + (uint32_t)t, stats_i,
+                       stats_f);
+    hipLaunchKernelGGL(k_nt_sync_apply, dim3(grid_for(B)), dim3(kBlock), 0, (hipStream_t)stream, weights, acc, pend,
+                       (const uint8_t*)nullptr, (const uint8_t*)nullptr, B, lr);
+  }
   return launch_status();
 }
 

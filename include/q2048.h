@@ -996,6 +996,46 @@ int q2048_nt_lambda_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weight
                                   uint64_t seed, uint64_t env_id0, uint32_t ctr0, int64_t *stats_i,
                                   double *stats_f, uint32_t *status, void *stream);
 
+/* ---- the synchronous batch step of the 6-tuple network: reproducible training (q2048_nt_sync_*) --------------------
+ * In one step every lane evaluates against the same frozen weights, the TD errors that fall on a weight are summed
+ * exactly, as integers, and the weight then moves once, by the mean of those errors.  The result is a pure function
+ * of the inputs: it does not depend on scheduling, on the number of threads or on which lane arrives first, and it
+ * is the same bytes on the device and in the CPU twin.
+ *   weights   V = float[4][16777216] of the family above, unchanged: every q2048_nt_* reader works on a V trained here.
+ *   acc       uint64_t[4][16777216][2], 1 GiB, 16-byte aligned, caller-owned; acc[p][idx] = {S, C}: the two's-complement
+ *             sum of the quantised errors of weight idx of pattern p and the number of contributions.  It must be all
+ *             zero on entry (not checked) and is all zero again when a call returns: it is never saved.
+ *   pend      (fused only) uint64_t[B], 16-byte aligned, caller-owned scratch: the packed key (cell 4r + c in nibble
+ *             4r + c) of the afterstate each lane learned on in the current step.  Ignored on entry, every word 0 on
+ *             return.  An afterstate of a legal move is never the empty board, so key 0 is "none".
+ *   phase A   V is only read.  A lane with a TD sample (x, s', done) forms live, target and
+ *             err = target - (double)v(x) in double, exactly as q2048_nt_update does, and quantises it:
+ *             q = isnan(err) ? 0 : llrint(clamp(err, -262144.0, 262144.0) * 4096.0) -- the product is exact, the
+ *             rounding to nearest even.  For each of its 32 entries, PER OCCURRENCE, S += q and C += 1: a weight a
+ *             symmetric board reads m times receives m * q and m, so a lone lane still moves it once (the family's
+ *             rule).  With B <= 2^20, |S| <= 2^53 and C <= 2^23: exact in double, and nothing wraps.
+ *   phase B   after every lane of phase A.  Every weight with C != 0 is written exactly once:
+ *             m = (double)S / ((double)C * 4096.0), one IEEE division; d = (float)((lr * 0.03125) * m), rounded once,
+ *             no contraction; V[p][idx] = V[p][idx] + d; the pair is zeroed.  Weights with C == 0 are not touched.
+ *   update    q2048_nt_sync_update has q2048_nt_update's skip rules (an action > 3 sets Q2048_STATUS_BAD_ACTION and
+ *             the lane contributes nothing; a move that does not change s contributes nothing); it is one phase A
+ *             over the batch, then one phase B.
+ *   fused     q2048_nt_sync_fused_rollout is q2048_nt_fused_rollout step for step with the same draws ctr0 + t --
+ *             evaluation of s from memory, the draw contract, env step, evaluation of s', statistics, reset -- with
+ *             the TD write replaced by a phase-A contribution and a phase B after every step.  So at ANY B it is
+ *             exactly the loop q2048_nt_choose / env step / q2048_nt_sync_update / reset, and steps = n in one call
+ *             equals any split of n over several calls.  On the device a step is two launches on `stream`.
+ * Argument checks are the q2048_nt_* counterpart's in its order, with acc (then pend) checked for NULL and for 16-byte
+ * alignment directly after weights; after the alignment checks, Q2048_ERR_RANGE for B > 1048576 and for overlapping
+ * byte ranges of weights and acc.  A refused call writes nothing; B == 0 or steps == 0 is Q2048_OK and writes nothing. */
+int q2048_nt_sync_update(float *weights, uint64_t *acc, const uint8_t *boards_s, const uint8_t *actions,
+                         const uint8_t *boards_s2, const uint8_t *done, int64_t B, double lr, double gamma,
+                         uint32_t *status, void *stream);
+int q2048_nt_sync_fused_rollout(uint8_t *boards, q2048_aux *aux, float *weights, uint64_t *acc, uint64_t *pend,
+                                int64_t B, int64_t steps, double eps, double lr, double gamma, uint64_t seed,
+                                uint64_t env_id0, uint32_t ctr0, int64_t *stats_i, double *stats_f,
+                                uint32_t *status, void *stream);
+
 /* ---- one-level expectimax over the spawn, for both afterstate families -------------------------------------------
  * The SEARCHED ROW of a state s replaces q_a = score_a + v(c_a) by the mean of best over the spawns of c_a.  For
  * a = 0..3, with c_a, score_a, legal_a and best as the family defines them above:

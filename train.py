@@ -113,6 +113,13 @@ def parse_args(argv=None):
     p.add_argument("--trace-depth", type=int, default=None, metavar="H",
                    help="with --trace-lambda: how many earlier afterstates a lane remembers, 0..3 (default 3; 0 is the "
                         "plain learner)")
+    p.add_argument("--synchronous", action="store_true",
+                   help="--agent ntuple only: the SYNCHRONOUS BATCH STEP (q2048_nt_sync_*).  In one step every env is "
+                        "evaluated against the same frozen weights, the TD errors that fall on a weight are summed exactly "
+                        "and the weight moves once by their mean: a run is a pure function of its arguments and repeats "
+                        "bit for bit, on the GPU and on --device cpu with any number of threads.  At most 1048576 envs; "
+                        "1 GiB of accumulators, never saved: the file is the plain network's.  Not combined with "
+                        "--coherence, --stage-tiles, --carousel or --trace-lambda")
     p.add_argument("--promote-every", type=int, default=None, metavar="N",
                    help="with --stage-tiles: every N epochs, copy what each stage has learned into the entries of the next "
                         "stage that are still zero (agent.promote()).  Default 1; 0 = never")
@@ -278,7 +285,8 @@ def train_batched(args, pkg):
                                        args.epsilon_min, dev, args.seed, shard.env_id0, coherence=args.coherence,
                                        stage_tiles=args.stage_tiles, **({"carousel": args.carousel} if args.carousel else {}),
                                        **({"trace_lambda": args.trace_lambda, "trace_depth": args.trace_depth}
-                                          if args.trace_lambda is not None else {}))
+                                          if args.trace_lambda is not None else {}),
+                                       **({"synchronous": True} if args.synchronous else {}))
     else:
         agent = pkg.BatchedQLearningAgent(args.episodes, 4, args.alpha, args.gamma, args.epsilon,
                                           args.epsilon_min, cap, dev, args.seed, shard.env_id0,
@@ -585,6 +593,18 @@ def main(argv=None):
         args.stage_tiles = tuple(int(t) for t in args.stage_tiles.split(",") if t.strip())
     except ValueError:
         raise SystemExit(f"--stage-tiles takes tile values separated by commas, not {args.stage_tiles!r}")
+    if args.synchronous:
+        if args.agent != "ntuple":
+            raise SystemExit(f"--synchronous applies to --agent ntuple (the 6-tuple afterstate network), not to --agent {args.agent}")
+        for flag, given in (("--coherence", args.coherence), ("--stage-tiles", args.stage_tiles),
+                            ("--carousel", args.carousel is not None), ("--trace-lambda", args.trace_lambda is not None)):
+            if given:
+                raise SystemExit(f"--synchronous is not combined with {flag}: the synchronous batch step is the plain "
+                                 "network's")
+        if args.num_envs == 1 and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+            raise SystemExit("--synchronous needs the batched mode (--num-envs > 1): the one-state loop runs the hash-table agent")
+        if args.num_envs > 1 << 20:
+            raise SystemExit("--synchronous sums at most 1048576 envs' errors exactly: fewer --num-envs")
     if args.stage_tiles:
         if args.agent != "ntuple":
             raise SystemExit(f"--stage-tiles applies to --agent ntuple (the 6-tuple afterstate network), not to --agent {args.agent}")
